@@ -4,7 +4,11 @@
     python bench.py --gpus 1 --steps K --warmup W [--workload W]     (N > 1: launched by torch.distributed.run)
 
 Rank 0 prints ONE JSON line.  `value` = pose evaluations by all ranks / max-over-ranks wall time of
-exactly K steps between barrier + synchronize on both sides.  Workloads (a "step" = one pass of
+exactly K steps between barrier + synchronize on both sides; `ms_per_step` = that wall time / K.  A plain run does
+only that: set up, warm up, time the K steps, print the line.  `--full` adds what takes work of its own: the counting
+launch (in-cutoff pairs, blocks), the spread of the timed steps, the GSO K1 / K2 split, `roofline` and `cpu_baseline`
+with the parity gate against the CPU oracle.  `--dump-outputs DIR` writes what the timed path computed in its last
+step as DIR/<name>.npy (float64; the inputs are seeded, so two builds can be compared output for output).  Workloads (a "step" = one pass of
 the hot path over one batch that already lives in HBM):
 
   1k4c (default)  BASELINE.json's metric configuration: ONE launch of the batched DFIRE pose-energy
@@ -96,6 +100,33 @@ WORKLOADS = {  # name -> (system, kind, default batch / swarms)
 
 def read_positions(path, cols):
     return np.array([[float(v) for v in line.split(" ")] for line in open(path).read().splitlines()])[:, :cols]
+
+
+DUMP_LIMIT_BYTES = 64000000
+
+
+def gso_state(gso):
+    """What a caller of the GSO loop receives: every swarm's glowworms (poses, luciferin, vision range, scoring, neighbour
+    count, moved flag, target), one row per swarm."""
+    states = [gso.read(s) for s in range(gso.n_swarms)]
+    return {k: np.stack([st[k] for st in states]) for k in states[0]}
+
+
+def dump_outputs(directory, arrays):
+    """`--dump-outputs`: each array as <directory>/<name>.npy in float64.  Every array has one row per pose (pose-energy
+    workloads) or per swarm (GSO); past 64 MB in all, a fixed seeded sample of the rows is written, their indices as
+    `sample_rows`."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(n, 1)
+    if row_bytes * n > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 4096 * (len(arrays) + 1)) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(20240611).choice(n, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def cpu_model():
@@ -257,7 +288,7 @@ def main():
     ap.add_argument("--workload", default="1k4c", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="poses per GPU per step (pose-energy workloads; 0 = the workload's default)")
     ap.add_argument("--swarms", type=int, default=0, help="GSO workloads: swarms (gso-1ppe: in total, sharded; gso-1k4c: per GPU)")
-    ap.add_argument("--cpu-seconds", type=float, default=200.0, help="CPU-baseline budget in core-seconds (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=200.0, help="--full: CPU-baseline budget in core-seconds (0 = skip)")
     ap.add_argument("--zero-last-bin", action="store_true",
                     help="DFIRE: zero bin 19 (14..15 A) of the synthetic table, as DFIRE's reference state does by construction; "
                          "NOT the headline configuration, reported separately in DESIGN.md")
@@ -267,9 +298,16 @@ def main():
                          "distance only (VERDICT r05 item 8).  NOT the headline configuration, reported separately in DESIGN.md")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo for dry runs)")
     ap.add_argument("--no-stats", action="store_true",
-                    help="skip the counting launch (in-cutoff pairs, blocks) in front of the timed region: for profiler runs, whose per-kernel "
+                    help="--full: skip the counting launch (in-cutoff pairs, blocks) in front of the timed region: for profiler runs, whose per-kernel "
                          "means then cover one population of launches; the byte model is not reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what takes work beyond the timed steps: counting launch, per-step spread, GSO K1 / K2 split, "
+                         "roofline, CPU baseline + parity gate")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     system, kind, default_size = WORKLOADS[args.workload]
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus, sys.argv[1:])          # does not return
@@ -336,7 +374,7 @@ def main():
 
         # pairs inside the outer cutoff of this batch (a counting launch, outside the timed region)
         blocks = None
-        if args.no_stats:
+        if args.no_stats or not args.full:
             p_cut = np.zeros(batch, dtype=np.int64)
         else:
             step(counts=True)
@@ -351,31 +389,40 @@ def main():
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
-        scorer.enable_timing(True)
-        scorer.pair_kernel_time()          # reset
+        if args.full:
+            scorer.enable_timing(True)
+            scorer.pair_kernel_time()          # reset
 
-        # the spread of the timed steps: one event per step boundary on the launch stream (the scorer runs on torch's current
-        # stream here, so torch events see it); recorded inside the timed region, read after it
-        marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+            # the spread of the timed steps: one event per step boundary on the launch stream (the scorer runs on torch's current
+            # stream here, so torch events see it); recorded inside the timed region, read after it
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
 
-        def timed():
-            marks[0].record(stream)
-            for k in range(args.steps):
-                step()
-                marks[k + 1].record(stream)
+            def timed():
+                marks[0].record(stream)
+                for k in range(args.steps):
+                    step()
+                    marks[k + 1].record(stream)
+        else:
+            def timed():
+                for _ in range(args.steps):
+                    step()
 
         elapsed = multi.timed_region(timed, dist, sync=torch.cuda.synchronize)     # barrier + synchronize both sides, MAX over ranks
-        step_ms = np.array([marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps)])
-        kern_ms, launches = scorer.pair_kernel_time()
-        scorer.enable_timing(False)
         energies = d_out.cpu().numpy()
+        outputs = {"energies": energies}
+        step_ms = None
+        if args.full:
+            step_ms = np.array([marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps)])
+            kern_ms, launches = scorer.pair_kernel_time()
+            scorer.enable_timing(False)
         total_evals = batch * args.steps * world
         scaling = "weak"
         shape = "%s %s pose-energy batch, %d poses/GPU/step, %d x %d atoms%s" % (
             system, case["method"].upper(), batch, n_rec, n_lig, ((", synthetic DCparams" + (" with bin 19 zeroed" if args.zero_last_bin else "") + (" with the membrane beads' rows (type 167) zeroed" if args.zero_bead_rows else "")) if table is not None else "") + (", 10 + 10 ANM modes" if case["kw"].get("use_anm") else ""))
-        extra = {"poses_per_step_per_gpu": batch, "nominal_pair_tests_per_pose": info["pair_tests_per_pose"],
-                 "mean_pairs_in_cutoff": float(p_cut.mean()), "mean_8x8_blocks_evaluated": blocks}
-        if case["method"] == "dfire" and scorer.bm_quiet_subtiles():
+        extra = {"poses_per_step_per_gpu": batch, "nominal_pair_tests_per_pose": info["pair_tests_per_pose"]}
+        if args.full:
+            extra.update({"mean_pairs_in_cutoff": float(p_cut.mean()), "mean_8x8_blocks_evaluated": blocks})
+        if args.full and case["method"] == "dfire" and scorer.bm_quiet_subtiles():
             # (receptor subtiles whose rows of the potential are zero: listed within the interface distance only; the block
             # count above is the counting launch's, which tests every box against the full cutoff)
             extra["quiet_receptor_subtiles"] = scorer.bm_quiet_subtiles()
@@ -407,6 +454,13 @@ def main():
         step_ms = None                            # (a GSO run is one asynchronous call: no per-step marks)
         evals = gso.num_evals - e0
         total_evals = int(multi.sum_over_ranks(evals, dist))
+        outputs = gso_state(gso) if args.dump_outputs and rank == 0 else None
+        scaling_note = " sharded over the ranks" if scaling == "strong" else " per GPU"
+        extra = {"swarms_this_rank": len(mine), "glowworms": 200, "gso_steps_per_s": args.steps / elapsed}
+        shape = "%s DFIRE GSO, %d swarms x 200 glowworms%s, %d x %d atoms, synthetic DCparams%s" % (
+            system, swarms_total, scaling_note, n_rec, n_lig,
+            (" with bin 19 zeroed" if args.zero_last_bin else "") + (" with the membrane beads' rows (type 167) zeroed" if args.zero_bead_rows else ""))
+    if kind == "gso" and args.full:
         # K1 / K2 split of this rank: a few more steps with events around the pair kernel
         scorer.enable_timing(True)
         scorer.pair_kernel_time()
@@ -429,9 +483,6 @@ def main():
         energies = d_out.cpu().numpy()
         evals_per_launch = (e2 - e1) / max(launches, 1)
         algo_bytes_launch = float((info["stream_bytes_per_pose"] + 8 * mean_cut) * evals_per_launch)
-        shape = "%s DFIRE GSO, %d swarms x 200 glowworms%s, %d x %d atoms, synthetic DCparams%s" % (
-            system, swarms_total, " sharded over the ranks" if scaling == "strong" else " per GPU", n_rec, n_lig,
-            (" with bin 19 zeroed" if args.zero_last_bin else "") + (" with the membrane beads' rows (type 167) zeroed" if args.zero_bead_rows else ""))
         extra = {"swarms_this_rank": len(mine), "glowworms": 200, "mean_pairs_in_cutoff_of_start_poses": mean_cut,
                  "gso_steps_per_s": args.steps / elapsed,
                  "k1_k2_split": {"pair_kernel_ms_per_step": kern_ms / max(launches, 1), "whole_step_ms": 1e3 * dt10 / 10,
@@ -442,7 +493,27 @@ def main():
         blocks = None
         cpu_poses = pos.reshape(-1, pos.shape[-1])
 
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
+    # `dtype` names the type of the reference's arithmetic and of the OUTPUT; what the timed kernels compute in:
+    if info["pair_kernel_name"].startswith("dfire_bm"):
+        arithmetic = ("f32 filter (affine-map posing, packed-f32 distance form, 1/16-unit cell LUT), i64 fixed-point sums (table values "
+                      "rounded once to 2^-40), f64 exact path for every pair whose cell holds a bin step / the cutoff / an interface decision; "
+                      "decisions (cutoff, bin, interface flag, pair count) = the reference's f64 decisions, bit for bit")
+    elif info["pair_kernel_name"].startswith("dfire_packed"):
+        arithmetic = "f32 filter, f64 sums, f64 exact path for every doubtful pair; decisions = the reference's f64 decisions"
+    else:
+        arithmetic = "f64 throughout, the reference's operation order (one v_rcp_f64 + Newton step in the DNA pair term)"
+    head = {
+        "metric": "pose-energy evals/sec (%s, %s)" % (case["method"].upper(), args.workload),
+        "value": total_evals / elapsed, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+        "dtype": "f64", "arithmetic": arithmetic, "data": "synthetic",
+        "config": dict({"workload": shape, "parallelism": "swarm-sharded x%d, no collectives" % world}, **extra),
+    }
+    if rank == 0 and not args.full:
+        print(json.dumps(head))
+    elif rank == 0:
         kern_s = kern_ms / 1e3 / max(launches, 1)
         achieved = algo_bytes_launch / kern_s / 1e9
         flags = ("" if not args.zero_last_bin else ":zero-last-bin") + ("" if not args.zero_bead_rows else ":zero-bead-rows")
@@ -515,23 +586,7 @@ def main():
                      "profile_stale": stale, "hbm_model": hbm_model, "binding": binding, "compute": compute, "lds": lds, "l1": l1, "l2": l2,
                      "nominal_pair_tests_per_s": info["pair_tests_per_pose"] * units_per_launch / kern_s,
                      "evaluated_pair_tests_per_s": (64.0 * blocks * units_per_launch / kern_s) if blocks else None})
-        # `dtype` names the type of the reference's arithmetic and of the OUTPUT; what the timed kernels compute in:
-        if info["pair_kernel_name"].startswith("dfire_bm"):
-            arithmetic = ("f32 filter (affine-map posing, packed-f32 distance form, 1/16-unit cell LUT), i64 fixed-point sums (table values "
-                          "rounded once to 2^-40), f64 exact path for every pair whose cell holds a bin step / the cutoff / an interface decision; "
-                          "decisions (cutoff, bin, interface flag, pair count) = the reference's f64 decisions, bit for bit")
-        elif info["pair_kernel_name"].startswith("dfire_packed"):
-            arithmetic = "f32 filter, f64 sums, f64 exact path for every doubtful pair; decisions = the reference's f64 decisions"
-        else:
-            arithmetic = "f64 throughout, the reference's operation order (one v_rcp_f64 + Newton step in the DNA pair term)"
-        out = {
-            "metric": "pose-energy evals/sec (%s, %s)" % (case["method"].upper(), args.workload),
-            "value": total_evals / elapsed, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-            "dtype": "f64", "arithmetic": arithmetic, "data": "synthetic",
-            "config": dict({"workload": shape, "parallelism": "swarm-sharded x%d, no collectives" % world}, **extra),
-            "roofline": roof,
-        }
+        out = dict(head, roofline=roof)
         if step_ms is not None and len(step_ms):
             # how much a single run's mean can be trusted: the spread of the K timed steps (events between steps on the launch stream)
             out["ms_per_step_min"] = float(step_ms.min())

@@ -418,9 +418,8 @@ def test_tile_order_keeps_the_blocks_a_pose_has_low(pkg, orc, table):
 def test_dfire_tables_equal_reference():
     """tools/check_dfire_tables.py: the reference's r3_to_numerical / ATOMNUMBER / ATOMRES / DIST_TO_BINS
     literals (src/dfire.rs:18-101) against the oracle's restated tables and the product's closed-form
-    host model builder, over every (residue, atom) key.  Needs the reference tree: build container only."""
-    if not os.path.exists("/root/reference/src/dfire.rs"):
-        pytest.skip("reference tree not present (GPU box)")
+    host model builder, over every (residue, atom) key.  The reference's literals are the fixture
+    tests/golden/unit/dfire_tables.json."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_dfire_tables.py")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "equal the reference" in r.stdout

@@ -9,7 +9,7 @@ trap 'cp /tmp/keep.so $L/liblightdock_hip.so' EXIT INT TERM   # an interrupted r
 for round in 1 2; do
   for v in $L/variants/*.so; do
     cp $v $L/liblightdock_hip.so
-    r=$(timeout 90 python bench.py --cpu-seconds 0 "$@" 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.0f evals/s kernel %.3f ms' % (d['value'], d['roofline']['kernel_ms']))" 2>&1 | tail -1)
+    r=$(timeout 90 python bench.py --full --cpu-seconds 0 "$@" 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.0f evals/s kernel %.3f ms' % (d['value'], d['roofline']['kernel_ms']))" 2>&1 | tail -1)
     echo "$(basename $v) $r"
   done
 done

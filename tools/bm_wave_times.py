@@ -4,7 +4,7 @@ import os, sys, subprocess
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ["LIGHTDOCK_BM_DEBUG"] = "/tmp/bm_debug.txt"
-subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-seconds", "0"] + sys.argv[1:], check=True, stdout=subprocess.DEVNULL)
+subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0"] + sys.argv[1:], check=True, stdout=subprocess.DEVNULL)
 d = np.loadtxt("/tmp/bm_debug.txt")
 t0, t1, jobs, batches = d[:, 0], d[:, 1], d[:, 2], d[:, 3]
 start = t0.min()

@@ -1,5 +1,5 @@
 import sys, os, time, numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as ge
 import torch; torch.cuda.init()
 pkg, orc = ge.package(), ge.oracle(); pkg.init(0)

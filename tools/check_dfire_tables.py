@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """DFIRE typing and binning tables: the reference's literals against the oracle and the product.
 
-Build container only (reads /root/reference/src/dfire.rs; nothing of it is copied).  The real
-`data/DCparams` is missing from the reference mount, so DFIRE energies cannot be pinned against
+The reference's literals are read from tests/golden/unit/dfire_tables.json, a data fixture taken from the
+reference's src/dfire.rs (`--write-fixture <path to src/dfire.rs>` regenerates it; nothing else of that file is
+copied).  The real `data/DCparams` is missing from the reference mount, so DFIRE energies cannot be pinned against
 the reference's goldens; what CAN be pinned is everything else the DFIRE model builder does:
 
   * `r3_to_numerical` (src/dfire.rs:18-46), `ATOMNUMBER` (:56-77), `ATOMRES` (:80-101):
@@ -14,8 +15,8 @@ the reference's goldens; what CAN be pinned is everything else the DFIRE model b
     product's cell LUT + exact steps must give DIST_TO_BINS[idx] - 1 for every index a distance
     inside the cutoff can produce (idx 0..29), and the oracle's copy must equal all 51 literals.
 
-Exit code 0 = all equal.  `tests/test_host_cpu.py::test_dfire_tables_equal_reference` runs this and
-skips where /root/reference does not exist (the GPU box)."""
+Exit code 0 = all equal.  `tests/test_host_cpu.py::test_dfire_tables_equal_reference` runs this."""
+import json
 import os
 import re
 import sys
@@ -23,10 +24,11 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-REF = "/root/reference/src/dfire.rs"
+FIXTURE = os.path.join(ROOT, "tests", "golden", "unit", "dfire_tables.json")
 
 
-def parse_reference(path=REF):
+def parse_reference(path):
+    """The four literal tables out of the reference's src/dfire.rs."""
     text = open(path).read()
     r3 = {m.group(1): int(m.group(2)) for m in re.finditer(r'"([A-Z]{3})"\s*=>\s*(\d+),', text[text.index("fn r3_to_numerical"):text.index("const DIST_TO_BINS")])}
     bins = [int(v) for v in re.search(r"const DIST_TO_BINS: &\[usize\] = &\[(.*?)\];", text, re.S).group(1).replace("\n", " ").split(",") if v.strip()]
@@ -35,6 +37,18 @@ def parse_reference(path=REF):
     rows = re.search(r"static ref ATOMRES: Vec<Vec<usize>> = vec!\[(.*?)\];\s*\}", text, re.S).group(1)
     atomres = [[int(v) for v in r.split(",")] for r in re.findall(r"vec!\[([0-9, ]+)\]", rows)]
     return r3, bins, atomnumber, atomres
+
+
+def write_fixture(path):
+    r3, bins, atomnumber, atomres = parse_reference(path)
+    with open(FIXTURE, "w") as f:
+        json.dump({"r3_to_numerical": r3, "DIST_TO_BINS": bins, "ATOMNUMBER": atomnumber, "ATOMRES": atomres}, f, indent=0, sort_keys=True)
+        f.write("\n")
+
+
+def load_fixture():
+    t = json.load(open(FIXTURE))
+    return t["r3_to_numerical"], t["DIST_TO_BINS"], t["ATOMNUMBER"], t["ATOMRES"]
 
 
 def parse_oracle_literals():
@@ -67,7 +81,7 @@ def one_atom_per_key_pdb(keys, r3):
 def main():
     import numpy as np
     import __graft_entry__ as ge
-    r3, bins, atomnumber, atomres = parse_reference()
+    r3, bins, atomnumber, atomres = load_fixture()
     problems = []
     if len(bins) != 51 or len(atomres) != 22 or len(r3) != 22:
         problems.append("unexpected table sizes in the reference: %d bins, %d ATOMRES rows, %d residues" % (len(bins), len(atomres), len(r3)))
@@ -116,4 +130,7 @@ def main():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "--write-fixture":
+        write_fixture(sys.argv[2])
+        sys.exit(0)
     sys.exit(main())

@@ -1,5 +1,5 @@
 import os, sys, subprocess, numpy as np
-ROOT=os.environ.get("GRAFT_REPO_ROOT","/root/repo")
+ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ["LIGHTDOCK_BM_DEBUG"]="/tmp/cull_debug.txt"; os.environ["LIGHTDOCK_HIP_VARIANT"]="culltimes"
 subprocess.run([sys.executable, os.path.join(ROOT,"bench.py"),"--steps","2","--warmup","1","--cpu-seconds","0","--no-stats"]+sys.argv[1:],check=True,stdout=subprocess.DEVNULL)
 d=np.loadtxt("/tmp/cull_debug.txt")

@@ -1,8 +1,9 @@
 """GPU box: 200 GSO steps of 2uuy (DFIRE + ANM, 10 + 10 modes: the block-major path's ANM form) against the oracle -- neighbour
 counts and targets identical at every checked step, energies and poses compared.  Usage: python tools/long_run_check_anm.py [steps]"""
 import sys, os, numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
-sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tests"))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as ge
 import torch; torch.cuda.init()
 from conftest import case_kwargs, case_positions

@@ -1,6 +1,6 @@
 # L1 (TCP) vs L2 (TCC) request counters of the tiled kernel (own --pmc passes, no tracing)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/pmc_l1
-B="python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0"
+B="python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 0"
 timeout 200 rocprofv3 --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_TOTAL_ACCESSES_sum TCP_PENDING_STALL_CYCLES_sum --output-format csv -d gpurun_out/pmc_l1/p1 -- $B > /dev/null 2>gpurun_out/pmc_l1/e1.log
 timeout 200 rocprofv3 --pmc TCC_REQ_sum TCC_READ_sum TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_LATENCY_sum --output-format csv -d gpurun_out/pmc_l1/p2 -- $B > /dev/null 2>gpurun_out/pmc_l1/e2.log
 python3 - <<'P'

@@ -2,7 +2,7 @@
 # Usage (GPU box): bash tools/pmc_packed.sh <tag> [bench args]   -> gpurun_out/pmc_<tag>/
 tag=${1:-x}; shift
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT; out=gpurun_out/pmc_$tag; mkdir -p $out
-B="python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 $*"
+B="python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 $*"
 rocprofv3 --list-avail > $out/avail.txt 2>&1
 i=0
 while read -r set; do

@@ -8,9 +8,9 @@ wls=${@:-1k4c 1ppe 1azp-dna gso-1ppe gso-1k4c 2uuy}
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 for w in $wls; do
   out=gpurun_out/prof_$tag/$w; mkdir -p $out
-  B="python3 bench.py --workload $w --steps 10 --warmup 3 --cpu-seconds 0 --no-stats"
+  B="python3 bench.py --full --workload $w --steps 10 --warmup 3 --cpu-seconds 0 --no-stats"
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- $B > $out/bench_traced.json 2> $out/trace.log
-  P="python3 bench.py --workload $w --steps 3 --warmup 1 --cpu-seconds 0 --no-stats"
+  P="python3 bench.py --full --workload $w --steps 3 --warmup 1 --cpu-seconds 0 --no-stats"
   i=0
   while read -r set; do
     i=$((i+1))
@@ -23,7 +23,7 @@ SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_IN
 SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_SCA
 TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_TOTAL_ACCESSES_sum TCP_PENDING_STALL_CYCLES_sum
 SETS
-  timeout 300 python3 bench.py --workload $w --steps 10 --warmup 3 > $out/bench.json 2> $out/bench.err
+  timeout 300 python3 bench.py --full --workload $w --steps 10 --warmup 3 > $out/bench.json 2> $out/bench.err
   python3 tools/summarize_profile.py $out > $out/summary.txt
   cat $out/summary.txt
 done

@@ -8,7 +8,7 @@ for v in $L/variants/*.so; do
   n=$(basename $v .so); cp $v $L/liblightdock_hip.so
   out=gpurun_out/r05abt/$n; mkdir -p $out
   for w in ${@:-1k4c}; do
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$w -- python3 bench.py --workload $w --steps 10 --warmup 3 --cpu-seconds 0 --no-stats > $out/bench_traced_$w.json 2> $out/trace_$w.log
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$w -- python3 bench.py --full --workload $w --steps 10 --warmup 3 --cpu-seconds 0 --no-stats > $out/bench_traced_$w.json 2> $out/trace_$w.log
   f=$(find $out/trace_$w -name '*kernel_stats.csv' | head -1)
   echo "== $n $w"; python3 - "$f" <<'PY'
 import csv, sys

@@ -11,13 +11,13 @@ cp $L/liblightdock_hip.so /tmp/keep.so
 trap 'cp /tmp/keep.so $L/liblightdock_hip.so' EXIT INT TERM   # an interrupted run must not leave a variant installed; tools/ab6.sh never installs one
 line() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%s: %.2f M evals/s, K1 %.3f ms, kernel %s' % ('$1', d['value'] / 1e6, d['roofline']['kernel_ms'], d['roofline']['kernel']))"; }
 for round in 1 2; do
-  timeout 120 python bench.py --workload 2uuy --cpu-seconds 0 --no-stats 2>/dev/null | line "(a) pose-major, ANM"
-  LIGHTDOCK_BM_DIAG_IGNORE_ANM=1 timeout 120 python bench.py --workload 2uuy --cpu-seconds 0 --no-stats 2>/dev/null | line "(b) block-major, rigid (floor)"
+  timeout 120 python bench.py --full --workload 2uuy --cpu-seconds 0 --no-stats 2>/dev/null | line "(a) pose-major, ANM"
+  LIGHTDOCK_BM_DIAG_IGNORE_ANM=1 timeout 120 python bench.py --full --workload 2uuy --cpu-seconds 0 --no-stats 2>/dev/null | line "(b) block-major, rigid (floor)"
   cp $L/variants/s_anm_cost.so $L/liblightdock_hip.so
-  LIGHTDOCK_BM_DIAG_IGNORE_ANM=1 timeout 120 python bench.py --workload 2uuy --cpu-seconds 0 --no-stats 2>/dev/null | line "(c) block-major + per-lane flexing cost"
+  LIGHTDOCK_BM_DIAG_IGNORE_ANM=1 timeout 120 python bench.py --full --workload 2uuy --cpu-seconds 0 --no-stats 2>/dev/null | line "(c) block-major + per-lane flexing cost"
   if [ -f $L/variants/t_anm_lds.so ]; then   # (d): (c) with the 480 mode components of a batch delivered from LDS (120 broadcast reads of 16 bytes)
     cp $L/variants/t_anm_lds.so $L/liblightdock_hip.so
-    LIGHTDOCK_BM_DIAG_IGNORE_ANM=1 timeout 120 python bench.py --workload 2uuy --cpu-seconds 0 --no-stats 2>/dev/null | line "(d) ... with the modes read from LDS"
+    LIGHTDOCK_BM_DIAG_IGNORE_ANM=1 timeout 120 python bench.py --full --workload 2uuy --cpu-seconds 0 --no-stats 2>/dev/null | line "(d) ... with the modes read from LDS"
   fi
   cp /tmp/keep.so $L/liblightdock_hip.so
 done

@@ -1,7 +1,7 @@
 # round 5: kernel trace of the 2uuy bench (block-major ANM form), and the wave timers of its pair kernel
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 out=gpurun_out/r05anm/trace; mkdir -p $out
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/t -- python3 bench.py --workload 2uuy --steps 10 --warmup 3 --cpu-seconds 0 --no-stats > $out/bench_traced.json 2> $out/trace.log
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/t -- python3 bench.py --full --workload 2uuy --steps 10 --warmup 3 --cpu-seconds 0 --no-stats > $out/bench_traced.json 2> $out/trace.log
 f=$(find $out/t -name '*kernel_stats.csv' | head -1)
 python3 - "$f" <<'PY'
 import csv, sys

@@ -10,7 +10,7 @@ vs=$(ls $L/variants/*.so 2>/dev/null); [ -z "$vs" ] && vs=/tmp/keep.so
 for v in $vs; do
   n=$(basename $v .so); cp $v $L/liblightdock_hip.so
   out=gpurun_out/$tag/$n; mkdir -p $out
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --steps 10 --warmup 3 --cpu-seconds 0 --no-stats > $out/bench_traced.json 2> $out/trace.log
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --steps 10 --warmup 3 --cpu-seconds 0 --no-stats > $out/bench_traced.json 2> $out/trace.log
   f=$(find $out/trace -name '*kernel_stats.csv' | head -1)
   echo "== $n"; python3 - "$f" <<'PY'
 import csv, sys

@@ -7,14 +7,14 @@ cd "${GRAFT_REPO_ROOT:?}" || exit 1
 out=gpurun_out/r06_final; mkdir -p $out
 for w in 1k4c 1ppe 1azp-dna gso-1ppe gso-1k4c 2uuy; do
   n=$(echo $w | tr - _)
-  timeout 600 python bench.py --workload $w > $out/${n}_bench.json 2> $out/${n}_bench.err
+  timeout 600 python bench.py --full --workload $w > $out/${n}_bench.json 2> $out/${n}_bench.err
   tail -1 $out/${n}_bench.json | cut -c1-110
 done
-for i in 2 3; do timeout 300 python bench.py > $out/1k4c_bench_run$i.json 2>/dev/null; tail -1 $out/1k4c_bench_run$i.json | cut -c1-110; done
+for i in 2 3; do timeout 300 python bench.py --full > $out/1k4c_bench_run$i.json 2>/dev/null; tail -1 $out/1k4c_bench_run$i.json | cut -c1-110; done
 # separately labelled lines (never the headline): the synthetic table with bin 19 zeroed / with the membrane beads' rows zeroed; the headline complex at other batch sizes
-timeout 300 python bench.py --zero-last-bin --cpu-seconds 0 > $out/1k4c_zero_last_bin.json 2>/dev/null; tail -1 $out/1k4c_zero_last_bin.json | cut -c1-110
-timeout 300 python bench.py --zero-bead-rows --cpu-seconds 0 > $out/1k4c_zero_bead_rows.json 2>/dev/null; tail -1 $out/1k4c_zero_bead_rows.json | cut -c1-110
-timeout 300 python bench.py --workload gso-1k4c --zero-bead-rows --cpu-seconds 0 > $out/gso_1k4c_zero_bead_rows.json 2>/dev/null; tail -1 $out/gso_1k4c_zero_bead_rows.json | cut -c1-110
+timeout 300 python bench.py --full --zero-last-bin --cpu-seconds 0 > $out/1k4c_zero_last_bin.json 2>/dev/null; tail -1 $out/1k4c_zero_last_bin.json | cut -c1-110
+timeout 300 python bench.py --full --zero-bead-rows --cpu-seconds 0 > $out/1k4c_zero_bead_rows.json 2>/dev/null; tail -1 $out/1k4c_zero_bead_rows.json | cut -c1-110
+timeout 300 python bench.py --full --workload gso-1k4c --zero-bead-rows --cpu-seconds 0 > $out/gso_1k4c_zero_bead_rows.json 2>/dev/null; tail -1 $out/gso_1k4c_zero_bead_rows.json | cut -c1-110
 for b in 4096 8192 16384 19456 32768 65536; do echo "1k4c, $b poses a launch: $(timeout 200 python3 bench.py --cpu-seconds 0 --batch $b 2>/dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.0f evals/s, step %.4f ms' % (d['value'], d['ms_per_step']))")"; done | tee $out/batch_sweep.txt
 for w in 1k4c 1ppe 2uuy; do
   echo "== $w" > $out/bm_wave_times_$w.txt
@@ -28,7 +28,7 @@ for live in 0 0.01 0.1 1; do
 done
 cat $out/gso_tail.txt
 for s in 1024 512 256 128; do
-  timeout 400 python bench.py --workload gso-1ppe --swarms $s --steps 40 --warmup 6 --cpu-seconds 0 > $out/gso_1ppe_share_$s.json 2> $out/gso_1ppe_share_$s.err
+  timeout 400 python bench.py --full --workload gso-1ppe --swarms $s --steps 40 --warmup 6 --cpu-seconds 0 > $out/gso_1ppe_share_$s.json 2> $out/gso_1ppe_share_$s.err
   python -c "import json,sys; d=json.loads(open('$out/gso_1ppe_share_$s.json').read().strip().splitlines()[-1]); print('swarms %4d: %.2f M evals/s, %.3f ms per step, moved %.2f' % ($s, d['value']/1e6, d['ms_per_step'], d['config']['k1_k2_split']['moved_fraction']))" | tee -a $out/share.txt
 done
 timeout 900 python3 tools/fuzz_parity.py 200 1 anm > $out/fuzz_anm.txt 2>&1; tail -2 $out/fuzz_anm.txt

@@ -8,7 +8,7 @@ tail -3 $O/pytest.txt
 ( cd tools/microbench && timeout 300 ./mfma_batch 2000 10 26 ) > $O/mfma_batch.txt 2>&1; tail -8 $O/mfma_batch.txt
 bash tools/ab6.sh 3 > $O/ab_1k4c.txt 2>&1; cat $O/ab_1k4c.txt
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 10 --warmup 3 --cpu-seconds 0 --no-stats > $O/bench_traced.json 2> $O/trace.log
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --full --steps 10 --warmup 3 --cpu-seconds 0 --no-stats > $O/bench_traced.json 2> $O/trace.log
 find $O/trace -name "*kernel_stats.csv" | head -1 | xargs cat | cut -d, -f1-6 | head -14
-LIGHTDOCK_HIP_VARIANT=r5 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_r5 -- python3 bench.py --steps 10 --warmup 3 --cpu-seconds 0 --no-stats > $O/bench_traced_r5.json 2> $O/trace_r5.log
+LIGHTDOCK_HIP_VARIANT=r5 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_r5 -- python3 bench.py --full --steps 10 --warmup 3 --cpu-seconds 0 --no-stats > $O/bench_traced_r5.json 2> $O/trace_r5.log
 find $O/trace_r5 -name "*kernel_stats.csv" | head -1 | xargs cat | cut -d, -f1-6 | head -14
