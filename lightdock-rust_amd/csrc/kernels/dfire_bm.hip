@@ -644,7 +644,7 @@ __global__ __launch_bounds__(kBmCullWaves * 64) void dfire_bm_cull(const BmLaunc
     {
         const size_t w = (size_t)blockIdx.x * kBmCullWaves + wave;
         if (T->debug != nullptr && lane == 0 && w % 5 == 0 && w / 5 < 2048) {   // (every fifth wave: all workgroups of the launch are sampled)
-            unsigned long long *d = T->debug + w / 5 * 8;
+            unsigned long long *d = T->debug + w / 5 * kBmDebugWords;
             d[0] = ct_start; d[1] = __builtin_amdgcn_s_memrealtime(); d[2] = ct_items; d[3] = ct_draw; d[4] = ct_box; d[5] = ct_loop; d[6] = ct_flush; d[7] = w;
         }
     }
@@ -1133,6 +1133,8 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
     const unsigned char *table_rows = reinterpret_cast<const unsigned char *>(T->count_mode ? T->m.rows_ones : T->m.rows);
     const unsigned long long dbg_t0 = DEBUG ? __builtin_amdgcn_s_memrealtime() : 0ull;
     unsigned long long dbg_jobs = 0, dbg_batches = 0, dbg_t_batch = 0, dbg_t_drain = 0, dbg_t_scan = 0, dbg_t_block = 0;
+    // block set-up: the rows' copy issued; the item list formed; the first loads' chain; a block's first batch's wait
+    unsigned long long dbg_t_dma = 0, dbg_t_compact = 0, dbg_t_compact_read = 0, dbg_t_chain = 0, dbg_t_wait = 0, dbg_blocks = 0;
     auto now = [] { return DEBUG ? __builtin_amdgcn_s_memrealtime() : 0ull; };
 
     // A wave's FIRST job is its own number in the launch -- no draw: the 2048 waves of a launch all start at once, and their 2048
@@ -1156,7 +1158,6 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
         const size_t tp = (size_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)rec.x);
         const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.y), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.z);
         const int a = __builtin_amdgcn_readfirstlane((int)rec.w);   // ligand subtile a of the tile = partial-sum row of the entry
-        const int n_chunks = (int)((hi - lo + 63) / 64);
         const int lt = (int)(tp / (unsigned)n_rt), RT = (int)(tp % (unsigned)n_rt);
         const int ls = lt * 8 + a;
 
@@ -1178,7 +1179,7 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
 #pragma unroll
             for (int k = 0; k < kChunks; k++) {
                 const uint32_t bits = (uint32_t)(k * 64 + lane) < n_mine ? (uint32_t)(m[k] >> (8 * a)) & 0xffu : 0u;
-                if (k < n_chunks) WS.row_bits[k * 64 + lane] = (unsigned char)bits;
+                WS.row_bits[k * 64 + lane] = (unsigned char)bits;   // (all chunks, zeros beyond the part's end: a block's scan reads them unconditionally)
                 any_bits |= bits;
             }
         }
@@ -1264,6 +1265,16 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
         for (int b = 0; b < 8; b++) {
             if (!((any_bits >> b) & 1u)) continue;
             const unsigned long long dbg_tblk = now();
+            // the job's entries' block bits for the scan below, read FIRST: the copy's wait for its row sources (a round trip
+            // through the LDS, which the other waves' batches keep busy) then covers these reads too, instead of a second round trip.
+            // Lane l scans entries kPer l .. kPer l + kPer - 1: their bytes are kPer / 4 words.
+            constexpr int kPer = BmWaveSharedT<ANM>::kPart / 64;
+            static_assert(kPer % 4 == 0 && kPer < 32, "a lane's block bits are whole words; its count fits in five bits");
+            static_assert(offsetof(BmSharedT<ANM>, w) % 4 == 0 && sizeof(BmWaveSharedT<ANM>) % 4 == 0 && offsetof(BmWaveSharedT<ANM>, row_bits) == 0,
+                          "the block bits are read as words");
+            uint32_t bits4[kPer / 4];
+#pragma unroll
+            for (int j = 0; j < kPer / 4; j++) bits4[j] = reinterpret_cast<const uint32_t *>(WS.row_bits + kPer * lane)[j];
             {   // stage the block's rows; they land while the entries are scanned
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the previous block's reads are done
                 // lane r: where row r = (i, j) = (r / 8, r % 8) of the block starts in the table
@@ -1279,29 +1290,52 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
                 LD_BM_DMA_ASM(dma_exec, dma_m0, dma_tmp, dma_rowsel, row_src, dma_piece, table_rows, cube_lds, 0x007fffffffffffffull, 0x00000fffffffffffull);
 #endif
             }
+            const unsigned long long dbg_tdma = now();
+            if (DEBUG) { dbg_t_dma += dbg_tdma - dbg_tblk; dbg_blocks++; }
             if (ANM) {   // the block's receptor subtile's modes -> LDS, behind the job's ligand modes
                 if (lane < kBmModeFloats / 4)
                     reinterpret_cast<float4 *>(WS.modes + kBmModeFloats)[lane] = reinterpret_cast<const float4 *>(T->m.rec_modes_f32 + ((size_t)RT * 8 + (size_t)b) * kBmModeFloats)[lane];
             }
             const bool tracked = lig_tracked || __builtin_amdgcn_readlane((int)my_tracked, b) != 0;
             constexpr float seed = (float)kBmCellZero + 0.5f;
-            // ---- the job's entries that hold block (a, b), in entry order (all 16 chunks' bytes in flight, then the ballots)
+            // ---- the job's entries that hold block (a, b), in entry order.  Lane-major: a lane counts its kPer entries' bits, five
+            // ballots give every lane the count of the lanes before it (its first slot) and the list's length, and the lane writes
+            // its entries in order.  (Chunk-major -- a ballot, two mbcnt, a scalar count and a masked write per 64 entries, each
+            // chunk's slots behind the previous chunk's count -- it was a chain of 28 vector-to-scalar-to-vector round trips, the
+            // largest part of a block set-up: LIGHTDOCK_BM_DEBUG's item-list timer.)
             uint32_t n_items = 0;
             {
-                constexpr int kChunks = BmWaveSharedT<ANM>::kPart / 64;
-                uint32_t bits16[kChunks];
+                if (DEBUG) {   // (the reads' round trip on its own)
 #pragma unroll
-                for (int k = 0; k < kChunks; k++) bits16[k] = k < n_chunks ? (uint32_t)WS.row_bits[k * 64 + lane] : 0u;
+                    for (int j = 0; j < kPer / 4; j++) asm volatile("" :: "v"(bits4[j]));
+                    dbg_t_compact_read += now() - dbg_tdma;
+                }
+                const uint32_t sel = 0x01010101u << b;   // bit b of each of a word's four bytes
+                uint32_t count = 0;
 #pragma unroll
-                for (int k = 0; k < kChunks; k++) {
-                    const uint32_t bits = bits16[k];
-                    const bool act = (bits >> b) & 1u;
-                    const unsigned long long m = __builtin_amdgcn_ballot_w64(act);
-                    if (act) {   // (the entry's number only: whether this is its first or last block of the job is worked out per batch, read_row)
-                        const uint32_t at = n_items + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                        WS.items[at] = (unsigned short)(k * 64 + lane);
-                    }
-                    n_items += (uint32_t)__popcll(m);
+                for (int j = 0; j < kPer / 4; j++) count += (uint32_t)__builtin_popcount(bits4[j] & sel);
+                uint32_t at = 0;   // the lane's first slot
+#pragma unroll
+                for (int i = 0; i < 5; i++) {
+                    const unsigned long long m = __builtin_amdgcn_ballot_w64((count >> i) & 1u);
+                    at += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) << i;
+                    n_items += (uint32_t)__popcll(m) << i;
+                }
+                // (the entry's number only: whether this is its first or last block of the job is worked out per batch, read_row.)
+                // Every entry is written: one that does not hold the block goes to the lane's slot behind the part's room, where the
+                // fillers go -- slot = dummy + bit (at - dummy), one multiply-add (a compare and a v_cndmask_b32 cost the vector port
+                // five plain instructions' time, profiles/r06_valu_issue_rates.txt; a branch per entry the execution mask's saving,
+                // setting and restoring)
+                int dummy = kPer * 64 + lane, first = kPer * lane;
+                asm("" : "+v"(dummy), "+v"(first));   // (formed here: hoisted out of the loops, the 28 entry numbers took 28 registers for the kernel's life)
+                int rel = (int)at - dummy;   // (at - dummy: from -(kPart + 63) to 0, within 24 bits)
+#pragma unroll
+                for (int k = 0; k < kPer; k++) {
+                    const int bit = (int)((bits4[k >> 2] >> (8 * (k & 3) + b)) & 1u);
+                    int slot;
+                    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(slot) : "v"(bit), "v"(rel), "v"(dummy));
+                    WS.items[slot] = (unsigned short)(first + k);
+                    rel += bit;
                 }
                 // 64 fillers behind the list's end: entry 0 of the part (a real entry, so everything a lane loads for it is valid
                 // memory; what the lane computes is dropped, `valid`).  A batch's lanes beyond the end read these instead of picking
@@ -1309,6 +1343,8 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
                 // a plain instruction (tools/microbench/valu_rate.hip, profiles/r06_valu_issue_rates.txt) -- per look-up.
                 WS.items[n_items + (uint32_t)lane] = 0;
             }
+            const unsigned long long dbg_tcompact = now();
+            if (DEBUG) dbg_t_compact += dbg_tcompact - dbg_tdma;
             // what a lane of a batch needs from memory, loaded one batch ahead: the pose's affine map out of the [row][12] table
             // (L2: the pass's table is 48 bytes a pose) and the entry's partial sum so far
             struct BatchLoads {
@@ -1399,7 +1435,11 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
                 Rx[q] = v2f{ops[24 + 2 * q], ops[25 + 2 * q]};
             }
             const float cbx = ops[32], cby = ops[33], cbz = ops[34];
-            if (DEBUG) dbg_t_block += now() - dbg_tblk;   // block set-up
+            if (DEBUG) {   // block set-up
+                const unsigned long long t = now();
+                dbg_t_block += t - dbg_tblk;
+                dbg_t_chain += t - dbg_tcompact;
+            }
 
             // ---- one batch: lane = entry.  Three pieces: the posing (code all waves share), the 64 pairs (once per wave of the
             // workgroup: WAVE is a constant of that code, see the switch below), the markers (shared again).
@@ -1578,6 +1618,7 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
                 // (also the row of the batch after this one, a load from the entry list: its wait belongs here too, not behind the stores below)
                 asm volatile("" :: "v"(look_row.row));
                 if constexpr (ANM) asm volatile("" :: "v"(next.amp[0].x), "v"(next.amp[1].x), "v"(next.amp[2].x), "v"(next.amp[3].x), "v"(next.amp[4].x), "v"(next.amp[5].x));
+                if (DEBUG && done == 0) dbg_t_wait += now() - dbg_tb;   // (a block's first batch: its wait for the rows and the first loads)
 #ifdef LD_BM_DIAG_WAIT   // (diagnostic builds: the drain timer holds the time a wave waits at the head of its batches for their loads)
                 if (DEBUG) dbg_t_drain += now() - dbg_tb;
 #endif
@@ -1647,7 +1688,7 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
     }
 #ifndef LD_BM_DIAG_CULL_TIMES
     if (DEBUG && T->debug != nullptr && lane == 0) {
-        unsigned long long *d = T->debug + ((size_t)blockIdx.x * kBmWaves + wave) * 8;
+        unsigned long long *d = T->debug + ((size_t)blockIdx.x * kBmWaves + wave) * kBmDebugWords;
         d[0] = dbg_t0;
         d[1] = __builtin_amdgcn_s_memrealtime();
         d[2] = dbg_jobs;
@@ -1656,6 +1697,12 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
         d[5] = dbg_t_drain;
         d[6] = dbg_t_block;
         d[7] = dbg_t_scan;
+        d[8] = dbg_t_dma;
+        d[9] = dbg_t_compact;
+        d[10] = dbg_t_chain;
+        d[11] = dbg_t_wait;
+        d[12] = dbg_blocks;
+        d[13] = dbg_t_compact_read;
     }
 #endif
 }

@@ -76,6 +76,7 @@ __host__ __device__ inline uint32_t bm_code_of_bin(uint32_t bin) { return 8 * bi
 constexpr int kBmMarkerShift = 51;           // a lane keeps two sums of 32 pairs each: below 2^50 under it, 32 markers of at most 127 above it: 63 bits
 constexpr int kBmJobRows = 8;                // a job = (tile pair, part of its entries, ligand subtile a): the blocks (a, 0..7); one partial sum per (entry, a)
 constexpr int kBmPartEntries = 1792;         // entries of a tile pair in one job: what a wave's share of the LDS holds at 3 bytes an entry (the block bits, the item list)
+constexpr int kBmDebugWords = 14;          // words of a wave's record in the LIGHTDOCK_BM_DEBUG buffer (dfire_bm_pairs' phase timers)
 constexpr int kBmEntryMask = 0x7ff;          // an entry's number in its part
 constexpr int kBmPassQuantum = 1024;         // poses per pass: a multiple of this
 constexpr int kBmOpsFloats = 36;             // BmModel::rec_ops: Rs[4][2], Rz[4][2], Ry[4][2], Rx[4][2], cx, cy, cz, 0
@@ -217,7 +218,7 @@ struct BmLaunch {
     uint32_t *job_order = nullptr;         // the jobs ((tile pair, part) index * kBmJobRows + row) that have work, longest first
     unsigned long long *queue = nullptr;   // [waves of dfire_bm_pairs][kBmQueueCap]: pairs waiting for the exact path
     int pairs_groups = 0;                  // CUs dfire_bm_pairs / dfire_bm_cull may fill (0: the 256 of an MI355X)
-    unsigned long long *debug = nullptr;   // diagnostics (LIGHTDOCK_BM_DEBUG): per wave of dfire_bm_pairs {start, end (100 MHz), jobs, batches, ...}
+    unsigned long long *debug = nullptr;   // diagnostics (LIGHTDOCK_BM_DEBUG): per wave of dfire_bm_pairs kBmDebugWords words {start, end (100 MHz), jobs, batches, ...}
     long long *tile_sum = nullptr;         // [lig tile][cap rows], zeroed by dfire_bm_pose: the pair kernel adds every finished (entry, ligand subtile) sum (fixed point);
                                            // rows contiguous: a batch's lanes are runs of consecutive rows, whose atomics then share 64-byte requests
     uint32_t *tile_tested = nullptr;       // [row][lig tiles]: 8x8 blocks let through (diagnostics) or nullptr

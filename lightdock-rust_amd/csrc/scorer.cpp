@@ -1190,8 +1190,10 @@ void Scorer::run_bm(size_t n, const double *d_poses, size_t stride, const uint8_
     }
     const char *dbg = std::getenv("LIGHTDOCK_BM_DEBUG");
     if (dbg) {
-        ws_bm_debug_.reserve(waves * 8 * sizeof(unsigned long long));
+        ws_bm_debug_.reserve(waves * kBmDebugWords * sizeof(unsigned long long));
         t.debug = static_cast<unsigned long long *>(ws_bm_debug_.ptr);
+        // (zeroed: a wave that draws no job, and the culling kernel's sampled records, leave words unwritten)
+        hip_check(hipMemsetAsync(t.debug, 0, waves * kBmDebugWords * sizeof(unsigned long long), stream_), "hipMemsetAsync debug");
     }
     // Passes of at most `cap` poses (poses are independent), alternating between this handle's stream and a second
     // one: fork behind what the stream holds so far, join before what follows.
@@ -1245,11 +1247,11 @@ void Scorer::run_bm(size_t n, const double *d_poses, size_t stride, const uint8_
     }
     if (dbg) {   // diagnostics: wave lifetimes of the last pass, one text line per wave
         hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        std::vector<unsigned long long> h(waves * 8);
+        std::vector<unsigned long long> h(waves * kBmDebugWords);
         hip_check(hipMemcpy(h.data(), t.debug, h.size() * 8, hipMemcpyDeviceToHost), "D2H debug");
         if (FILE *f = std::fopen(dbg, "w")) {
-            for (size_t i = 0; i < h.size(); i += 8)
-                std::fprintf(f, "%llu %llu %llu %llu %llu %llu %llu %llu\n", h[i], h[i + 1], h[i + 2], h[i + 3], h[i + 4], h[i + 5], h[i + 6], h[i + 7]);
+            for (size_t i = 0; i < h.size(); i += kBmDebugWords)
+                for (int k = 0; k < kBmDebugWords; k++) std::fprintf(f, k + 1 < kBmDebugWords ? "%llu " : "%llu\n", h[i + (size_t)k]);
             std::fclose(f);
         }
     }

@@ -16,6 +16,11 @@ print("us per batch (lifetime / batches): mean %.2f" % (life.sum() / batches.sum
 h, edges = np.histogram(end, bins=10)
 print("wave end-time histogram (us):", " ".join("%d@%.0f" % (c, e) for c, e in zip(h, edges[1:])))
 print("time in batches: mean %.1f us per wave (%.2f us per batch); in exact-path drains %.1f us; in block set-up %.1f us; in job set-up %.1f us (%.2f us per job)" % ((d[:, 4] / 100).mean(), d[:, 4].sum() / 100 / batches.sum(), (d[:, 5] / 100).mean(), (d[:, 6] / 100).mean(), (d[:, 7] / 100).mean(), d[:, 7].sum() / 100 / max(jobs.sum(), 1)))
+if d.shape[1] >= 14:   # the block set-up split (words 8-13): the rows' copy issued, the item list formed (of it: the reads' round trip), the first loads' chain; the first batch's wait
+    blocks = np.maximum(d[:, 12].sum(), 1)
+    us = lambda k: (d[:, k] / 100).mean()
+    print("block set-ups per wave mean %.1f (%.2f us each): rows' copy issued %.1f us, item list %.1f us (its reads' round trip %.1f us), first loads' chain %.1f us per wave; first batches' wait for rows and loads %.1f us per wave (%.2f us per block)" % (
+        d[:, 12].mean(), d[:, 6].sum() / 100 / blocks, us(8), us(9), us(13), us(10), us(11), d[:, 11].sum() / 100 / blocks))
 late = end > np.percentile(end, 90)
 print("slowest 10%% of waves: batches %.0f, batch time %.0f us, drain time %.0f us, jobs %.1f" % (batches[late].mean(), (d[late, 4] / 100).mean(), (d[late, 5] / 100).mean(), jobs[late].mean()))
 per_cu = batches.reshape(-1, 8).sum(1)
