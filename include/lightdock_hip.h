@@ -154,7 +154,7 @@ int ld_dfire_bm_lut(double ubound, double lig_extent, uint8_t *codes_out, double
  * value beyond 1024 or not finite, or a count beyond 2^23) -- such a scorer runs the pose-major kernels. */
 int ld_dfire_bm_fix_scale(const double *rec_xyz /* n_rec x 3 */, size_t n_rec, double reach, double table_vmax,
                           uint64_t *reach_count_out, int *extra_bits_out, double *scale_out);
-/* The atom order the tiled DFIRE kernel uses (host-side, no GPU): order_out[slot] = original atom
+/* The atom order the culled DFIRE kernels use (host-side, no GPU): order_out[slot] = original atom
  * index, UINT32_MAX for padding; length = ceil(n/64)*64.  Consecutive 8 slots ("subtile") and 64
  * slots ("tile") are spatially compact; padding only at the tail.  The energy is a plain sum over
  * pairs (src/dfire.rs:325-345), so the order is free.  Returns the padded length. */
@@ -206,10 +206,11 @@ int ld_scorer_energy_batch(ld_scorer *s, size_t n, const double *poses, size_t s
 int ld_scorer_energy_batch_device(ld_scorer *s, size_t n, const double *d_poses, size_t stride,
                                   const uint8_t *d_active, double *d_energies_out, uint32_t *d_pair_counts);
 
-/* Diagnostics of the box-culled DFIRE kernel: after a ld_scorer_energy_batch_device call WITH
- * pair_counts, the number of 8x8 atom-pair blocks each of those n poses actually evaluated
- * (64 pair tests each; compare with n_rec*n_lig/64 for all pairs).  Synchronises.  Returns
- * LD_ERR_UNSUPPORTED for scorers that run the all-pairs kernel. */
+/* Diagnostics of the box-culled DFIRE kernels (block-major and pose-major): after a
+ * ld_scorer_energy_batch_device call WITH pair_counts, the number of 8x8 atom-pair blocks each of
+ * those n poses actually evaluated (64 pair tests each; compare with n_rec*n_lig/64 for all pairs).
+ * Synchronises.  Returns LD_ERR_UNSUPPORTED for scorers that run the all-pairs kernel (DNA,
+ * LIGHTDOCK_DFIRE_KERNEL=allpairs, receptors too long for the packed f32 frame). */
 int ld_scorer_last_block_counts(ld_scorer *s, size_t n, uint32_t *blocks_out_host);
 
 /* Diagnostics of the block-major DFIRE path: the number of receptor subtiles (8 atoms of the tile order) whose atoms' rows of the

@@ -433,7 +433,7 @@ class Scorer:
         return ms.value, n.value
 
     def last_block_counts(self, n):
-        """8x8 atom-pair blocks evaluated per pose in the last counting launch (tiled DFIRE kernel)."""
+        """8x8 atom-pair blocks evaluated per pose in the last counting launch (culled DFIRE kernels)."""
         out = np.zeros(n, dtype=np.uint32)
         _check(self.lib.ld_scorer_last_block_counts(self._h, n, _ptr(out)))
         return out

@@ -1,7 +1,7 @@
-// spatial_order.hpp -- atom ordering for the tiled pose-energy kernel.
+// spatial_order.hpp -- atom ordering for the culled DFIRE pose-energy kernels.
 //
 // The reference walks atoms in PDB order (src/dfire.rs:325-345); the energy is a plain sum
-// over pairs, so any order gives the same value up to f64 rounding.  The tiled kernel wants
+// over pairs, so any order gives the same value up to f64 rounding.  The culled kernels want
 // atoms that are close in space to be close in memory: leaves of 8 atoms ("subtiles") and
 // runs of 8 leaves ("tiles", 64 atoms) with small bounding boxes, so that whole 8x8 and
 // 64x64 blocks of pairs can be discarded with one box-distance test.
@@ -21,7 +21,7 @@ namespace ld {
 // subtiles follow (round 6: 10 % fewer 8x8 blocks per 1k4c pose; tools/cluster_sim.py).  Deterministic.
 std::vector<uint32_t> spatial_tile_order(const double *xyz /* n x 3 */, size_t n);
 
-// Renumbering of the DFIRE atom types (0..168) of one molecule for the tiled kernel's table
+// Renumbering of the DFIRE atom types (0..168) of one molecule for the culled kernels' table
 // layout, which keeps the potential of two consecutive type numbers in the same 128-byte patch
 // (kernels/dfire_tiled.hpp): types that sit close together inside the subtiles of `order` (bonded
 // atoms of one residue, mostly) become the pairs (2k, 2k+1).  Greedy matching on a closeness-

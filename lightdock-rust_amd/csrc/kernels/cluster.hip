@@ -302,7 +302,8 @@ struct ld_complex {
     size_t pose_len() const { return 7 + (size_t)dev.anm_rec + (size_t)dev.anm_lig; }
 
     ~ld_complex() {
-        for (ld::DeviceBuffer *b : {&d_poses, &d_scores, &d_out, &d_ws, &d_ids}) b->release();
+        // the buffers are freed after this body: nothing queued (a call that threw halfway) may still use them
+        if (stream) (void)hipStreamSynchronize(stream);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (stream) (void)hipStreamDestroy(stream);

@@ -49,7 +49,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "dfire_packed.hpp"
+#include "dfire_tiled.hpp"
 
 namespace ld {
 

@@ -1,7 +1,7 @@
 // dfire_packed.hpp -- launch interface of the default DFIRE pose-energy kernel (K1, DFIRE).
 //
-// Same sum as src/dfire.rs:325-345 and the same culling as dfire_tiled.hpp (64x64 tile boxes, 8x8
-// subtile boxes), but the pair test runs in packed f32 on 16-byte records and only the pairs whose
+// Same sum as src/dfire.rs:325-345, culled in the tile order of dfire_tiled.hpp (64x64 tile boxes, 8x8
+// subtile boxes); the pair test runs in packed f32 on 16-byte records and only the pairs whose
 // f32 distance cannot decide the reference's f64 result are recomputed in f64:
 //
 //   record coordinate  u = fl32(kappa (x - c))      c = centre of the receptor's box, kappa = 2 sqrt(SC)
@@ -62,15 +62,6 @@ constexpr uint32_t kPackedCodeStep = 0x2u;    // full path: a bin step inside, i
 constexpr uint32_t kPackedCodeIface = 0x4u;   // full path: the cell reaches down to the interface distance
 constexpr uint32_t kPackedCodeCutoff = 0x8u;  // full path: the cutoff inside
 
-// Two receptor atoms as one lane of the pair loop reads them: the atoms (2 q, 2 q + 1) of subtile j
-// of a tile (record index 4 j + q).  The operands of v_pk_add_f32 / v_pk_fma_f32 are (x0, x1),
-// (y0, y1), (z0, z1) as they lie here.
-struct alignas(32) PackedRecPair {
-    float x0, x1, y0, y1, z0, z1;
-    uint32_t t0, t1;  // tiled_rec_term(type): byte offset of the type's column in a table patch
-};
-static_assert(sizeof(PackedRecPair) == 32, "PackedRecPair must be 32 bytes");
-
 struct PackedReceptor {
     int n_real = 0;
     int n_tiles = 0;
@@ -118,24 +109,6 @@ struct PackedLaunch {
     uint32_t *exact_partial = nullptr;   // [pose][group]: pairs recomputed in f64 (diagnostics) or nullptr
 };
 
-struct PackedPrepareLaunch {
-    int n_real = 0, n_tiles = 0;
-    const double *x = nullptr, *y = nullptr, *z = nullptr;  // tile order, padded
-    const uint32_t *tindex = nullptr;
-    const int32_t *slot = nullptr;
-    int num_anm = 0;
-    const double *modes = nullptr;  // [mode][xyz][n_tiles*64]
-    const double *poses = nullptr;
-    size_t stride = 0;
-    const uint8_t *active = nullptr;
-    size_t n_poses = 0;
-    double cx = 0, cy = 0, cz = 0;
-    double kappa = 2.0;
-    float ubound = 0.f;
-    PackedRecPair *pairs_out = nullptr;
-    TiledBox *sub_out = nullptr, *tile_out = nullptr;
-};
-
 // Bound on |D_f32 - 4 d2| (units of 4 d2) for two records inside `ubound` (record units) whose true
 // 4 d2 is below 1100, with the kernel's operation order (three packed subtractions, one fma chain
 // seeded with 1/2).
@@ -143,6 +116,5 @@ double dfire_f32_error_bound(double ubound, int cells_per_unit);
 
 size_t packed_kernel_lds_bytes(int cells_per_unit);
 hipError_t launch_dfire_packed(const PackedLaunch &t, hipStream_t stream);
-hipError_t launch_packed_prepare(const PackedPrepareLaunch &p, hipStream_t stream);
 
 }  // namespace ld

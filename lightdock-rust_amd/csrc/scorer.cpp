@@ -301,17 +301,21 @@ Scorer::Scorer(const ld_scorer_desc &desc) {
     pair_.split_j = (n_groups % kWaves != 0 && n_groups < 4 * kWaves) ? 1 : 0;
 
     if (method_ == LD_METHOD_DFIRE) {
-        const char *k = std::getenv("LIGHTDOCK_DFIRE_KERNEL");
-        // "packed" (default): culling + packed-f32 pair test with exact f64 path; "tiled": the same
-        // culling with an all-f64 pair test; "allpairs": no culling
-        use_tiled_ = !(k && std::strcmp(k, "allpairs") == 0);
-        if (use_tiled_) build_tiled(desc);
-        if (use_tiled_ && !(k && std::strcmp(k, "tiled") == 0)) build_packed(desc);
-        // "bm" / default: the block-major path (kernels/dfire_bm.hpp; its ANM form for molecules that flex); "packed": the pose-major
-        // kernel for everything (what LIGHTDOCK_TILED_LATENCY=1, the single-swarm CLI, and the complexes build_bm declines use anyway)
-        const char *latency = std::getenv("LIGHTDOCK_TILED_LATENCY");
-        if (use_packed_ && !(k && std::strcmp(k, "packed") == 0) && !(latency && std::atoi(latency) > 0 && !(k && std::strcmp(k, "bm") == 0)))
-            build_bm(desc);
+        // LIGHTDOCK_DFIRE_KERNEL: "bm" (and any other value, the default): the block-major path (kernels/dfire_bm.hpp; its ANM
+        // form for molecules that flex); "packed": the pose-major kernel for everything (what LIGHTDOCK_TILED_LATENCY=1, the
+        // single-swarm CLI, and the complexes build_bm declines use anyway); "allpairs": no culling (what the receptors
+        // build_packed declines use too)
+        const char *env = std::getenv("LIGHTDOCK_DFIRE_KERNEL");
+        const std::string kernel = env ? env : "";
+        const char *latency_env = std::getenv("LIGHTDOCK_TILED_LATENCY");
+        const bool latency = latency_env && std::atoi(latency_env) > 0;
+        if (kernel != "allpairs") {
+            build_tile_order(desc, latency);
+            if (build_packed(desc)) {
+                route_ = PairRoute::packed;
+                if (kernel != "packed" && (kernel == "bm" || !latency) && build_bm(desc)) route_ = PairRoute::block_major;
+            }
+        }
     }
 }
 
@@ -371,25 +375,22 @@ void Scorer::upload_tiled_molecule(const ld_molecule &m, bool is_receptor, Tiled
     }
 }
 
-void Scorer::build_tiled(const ld_scorer_desc &desc) {
+// What the pose-major and block-major paths share: both molecules in tile order, the potential in patches, the ligand
+// as the kernels read it, and the pose-major kernel's split.
+void Scorer::build_tile_order(const ld_scorer_desc &desc, bool latency) {
     upload_tiled_molecule(desc.receptor, true, tiled_rec_soa_);
-    TiledSoA &lig = tiled_lig_soa_;
-    upload_tiled_molecule(desc.ligand, false, lig);
-    tiled_.lig.n_real = lig.n_real;
-    tiled_.lig.n_tiles = lig.n_tiles;
-    tiled_.lig.x = lig.x;
-    tiled_.lig.y = lig.y;
-    tiled_.lig.z = lig.z;
-    tiled_.lig.tindex = lig.tindex;
-    tiled_.lig.slot = lig.slot;
-    tiled_.lig.num_anm = lig.num_anm;
-    tiled_.lig.modes = lig.modes;
-    tiled_.lig.flag_words = pair_.lig.flag_words;
-    tiled_.rec.n_real = tiled_rec_soa_.n_real;
-    tiled_.rec.n_tiles = tiled_rec_soa_.n_tiles;
-    tiled_.rec.flag_words = pair_.rec.flag_words;
-    tiled_.use_anm = use_anm_ ? 1 : 0;
-    tiled_.anm_rec = (int)anm_rec();
+    upload_tiled_molecule(desc.ligand, false, tiled_lig_soa_);
+    const TiledSoA &lig = tiled_lig_soa_;
+    tiled_lig_.n_real = lig.n_real;
+    tiled_lig_.n_tiles = lig.n_tiles;
+    tiled_lig_.x = lig.x;
+    tiled_lig_.y = lig.y;
+    tiled_lig_.z = lig.z;
+    tiled_lig_.tindex = lig.tindex;
+    tiled_lig_.slot = lig.slot;
+    tiled_lig_.num_anm = lig.num_anm;
+    tiled_lig_.modes = lig.modes;
+    tiled_lig_.flag_words = pair_.lig.flag_words;
     {   // potential re-laid out in 2 x 2 x 4 patches, see dfire_tiled.hpp
         std::vector<double> t2(kTiledTableDoubles, 0.0);
         for (uint32_t l = 0; l < 168; l++)
@@ -397,68 +398,22 @@ void Scorer::build_tiled(const ld_scorer_desc &desc) {
                 for (uint32_t r = 0; r < 168; r++)
                     t2[(tiled_lig_term(type_perm_lig_[l]) + tiled_rec_term(type_perm_rec_[r]) + tiled_bin_term(b)) / 8] =
                         desc.potential[(size_t)r * kDfireRowStride + l * 20 + b];
-        tiled_.table = arena_.upload(t2);
+        tiled_table_ = arena_.upload(t2);
     }
-    tiled_.bin_step = pair_.bin_step;
-    tiled_.iface_d2 = pair_.iface_d2;
-    tiled_.iface_scaled = 4.0 * pair_.iface_d2;
-    {   // cell code = bin at the cell's lower edge | 0x80 when a bin step falls inside the cell
-        // | 0x40 when the cell reaches below the interface distance (src/dfire.rs:339)
-        const DfireBinning b = build_dfire_binning();
-        std::vector<uint8_t> code(b.lut);
-        for (int c = 0; c <= 900; c++) {
-            const int bin = b.lut[c];
-            if (b.step[bin + 1] < (c + 1) * 0.25) code[c] |= 0x80u;
-            if (c * 0.25 <= pair_.iface_d2) code[c] |= 0x40u;
-        }
-        std::vector<uint32_t> words(kDfireLutCells, kTiledLutMiss);
-        for (int c = 0; c <= 900; c++)  // cell 900 holds the cutoff itself: d2 = 225 is in, the rest of the cell out
-            words[c] = (code[c] & 0xc0u) || c == 900 ? kTiledLutSlow | code[c] : tiled_bin_term(code[c]);
-        tiled_.lut = arena_.upload(words);
-    }
-    int waves = 4;  // measured on MI355X (1k4c, 1ppe): 4 waves per workgroup beat 1, 2 and 8
-    if (const char *e = std::getenv("LIGHTDOCK_TILED_WAVES")) {
-        int v = std::atoi(e);
-        if (v >= 1 && v <= kTiledMaxWaves) waves = v;
-    }
-    // `split` items share one ligand tile, each taking every split-th surviving receptor tile.
+    // `split` waves share one ligand tile, each taking every split-th surviving receptor tile.
     // With thousands of poses per launch there are enough waves anyway and split = 1 is best or
     // equal (measured on MI355X at 16 384+ poses: 2uuy, 7 ligand tiles, +12 % over split 3; 1k4c,
     // 52 tiles, +11 %; 1ppe, 4 tiles, +5 % with the packed kernel).  A launch of one swarm (200 poses) of a small ligand
     // does not fill the GPU: split 3 halves its latency on 1ppe.  The split is fixed per scorer (a
     // pose's energy must not depend on the batch it travels in), so the default serves
     // throughput and LIGHTDOCK_TILED_LATENCY=1 -- set by the single-swarm CLI -- serves latency.
-    // Splits sharing a factor with the 4 waves of a workgroup (2, 4) are consistently slower.
-    const char *latency = std::getenv("LIGHTDOCK_TILED_LATENCY");
-    const int small_ligand = (latency && std::atoi(latency) > 0) ? 32 : 0;
-    int split = tiled_.lig.n_tiles < small_ligand ? 3 : 1;
+    int split = latency && tiled_lig_.n_tiles < 32 ? 3 : 1;
     if (const char *e = std::getenv("LIGHTDOCK_TILED_SPLIT")) {
         int v = std::atoi(e);
         if (v >= 1 && v <= 8) split = v;
     }
-    tiled_.waves = waves;
-    tiled_.split = split;
-    tiled_.n_groups = (tiled_.lig.n_tiles * split + waves - 1) / waves;
-
+    tiled_split_ = split;
     rec_anm_per_pose_ = use_anm_ && tiled_rec_soa_.num_anm > 0;
-    if (!rec_anm_per_pose_) {
-        // static receptor image (records + subtile/tile boxes), built once by the same kernel
-        // that builds the per-pose images when the receptor has ANM
-        const size_t pad = (size_t)tiled_.rec.n_tiles * 64;
-        TiledAtom *atoms = static_cast<TiledAtom *>(arena_.alloc_bytes(pad * sizeof(TiledAtom)));
-        TiledBox *sub = static_cast<TiledBox *>(arena_.alloc_bytes(pad / 8 * sizeof(TiledBox)));
-        TiledBox *tile = static_cast<TiledBox *>(arena_.alloc_bytes(pad / 64 * sizeof(TiledBox)));
-        PrepareReceptorLaunch p = prepare_launch(nullptr, 0, nullptr, 1);
-        p.num_anm = 0;
-        p.atoms_out = atoms;
-        p.sub_out = sub;
-        p.tile_out = tile;
-        hip_check(launch_prepare_receptor(p, stream_), "launch dfire_prepare_receptor");
-        hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        tiled_.rec.atoms = atoms;
-        tiled_.rec.sub_boxes = sub;
-        tiled_.rec.tile_boxes = tile;
-    }
 }
 
 double dfire_f32_error_bound(double ubound, int cells_per_unit) {
@@ -545,7 +500,7 @@ std::vector<uint32_t> build_packed_lut(int sc, double eps, uint32_t zero_bins) {
 // The default DFIRE kernel: f32 records in a frame centred on the receptor, the cell LUT of
 // kernels/dfire_packed.hpp (every cell that cannot decide the reference's f64 result is flagged),
 // and the receptor image as pair records.
-void Scorer::build_packed(const ld_scorer_desc &desc) {
+bool Scorer::build_packed(const ld_scorer_desc &desc) {
     double centre[3], half;
     frame_of_receptor(desc.receptor, centre, &half);
     // LUT cells per unit of 4 d2: 2 halves the share of pairs in flagged cells for 4 KiB more LDS
@@ -560,12 +515,12 @@ void Scorer::build_packed(const ld_scorer_desc &desc) {
         const double f = std::atof(e);
         if (f >= 1.0 && f <= 1000.0) eps *= f;
     }
-    if (!(eps * sc < 0.2)) return;  // a receptor thousands of angstroms across: keep the all-f64 tiled kernel
+    if (!(eps * sc < 0.2)) return false;  // a receptor thousands of angstroms across: the all-pairs kernel, all f64
 
     PackedLaunch &P = packed_;
-    P.lig = tiled_.lig;
-    P.use_anm = tiled_.use_anm;
-    P.anm_rec = tiled_.anm_rec;
+    P.lig = tiled_lig_;
+    P.use_anm = use_anm_ ? 1 : 0;
+    P.anm_rec = (int)anm_rec();
     P.cx = centre[0];
     P.cy = centre[1];
     P.cz = centre[2];
@@ -573,7 +528,7 @@ void Scorer::build_packed(const ld_scorer_desc &desc) {
     P.cells_per_unit = sc;
     P.ubound = (float)ubound;
     P.eps = std::nextafter((float)eps, INFINITY);
-    P.table = tiled_.table;
+    P.table = tiled_table_;
     P.bin_step = pair_.bin_step;
     P.iface_scaled = 4.0 * pair_.iface_d2;
 
@@ -600,9 +555,8 @@ void Scorer::build_packed(const ld_scorer_desc &desc) {
     P.lut = arena_.upload(build_packed_lut(sc, (double)P.eps, zero_bins));
     packed_lut_full_ = zero_bins ? arena_.upload(build_packed_lut(sc, (double)P.eps, 0)) : P.lut;  // counting launches count every pair
 
-    int split = tiled_.split;
-    P.split = split;
-    P.n_groups = (P.lig.n_tiles * split + kPackedWaves - 1) / kPackedWaves;
+    P.split = tiled_split_;
+    P.n_groups = (P.lig.n_tiles * P.split + kPackedWaves - 1) / kPackedWaves;
 
     P.rec.n_real = tiled_rec_soa_.n_real;
     P.rec.n_tiles = tiled_rec_soa_.n_tiles;
@@ -628,7 +582,7 @@ void Scorer::build_packed(const ld_scorer_desc &desc) {
     P.rec.x = tiled_rec_soa_.x;  // undeformed; the exact path applies the modes of a per-pose image itself
     P.rec.y = tiled_rec_soa_.y;
     P.rec.z = tiled_rec_soa_.z;
-    use_packed_ = true;
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -818,7 +772,7 @@ double dfire_bm_fix_scale(double vmax, size_t reach_count, int *extra_bits_out) 
     return std::ldexp(1.0, 44 - e - x);
 }
 
-void Scorer::build_bm(const ld_scorer_desc &desc) {
+bool Scorer::build_bm(const ld_scorer_desc &desc) {
 #ifdef LD_DIAG_BUILD
     // (diagnostic builds only, tools/build_variant.sh -- LIGHTDOCK_BM_DIAG_IGNORE_ANM=1: timing experiments, the block-major kernels
     // on an ANM complex as if it were rigid, wrong sums.  The shipped library does not read the variable.)
@@ -835,17 +789,17 @@ void Scorer::build_bm(const ld_scorer_desc &desc) {
     const bool anm = !diag_rigid && use_anm_ && (rec.num_anm > 0 || lig.num_anm > 0);
     if (anm) {
         const char *e = std::getenv("LIGHTDOCK_BM_ANM");
-        if (e && std::atoi(e) == 0) return;
-        if (rec.num_anm > kBmMaxModes || lig.num_anm > kBmMaxModes) return;
+        if (e && std::atoi(e) == 0) return false;
+        if (rec.num_anm > kBmMaxModes || lig.num_anm > kBmMaxModes) return false;
     }
-    if (rec.n_tiles > 1024 || lig.n_tiles > 1024) return;  // an item of the exact path names its atoms in 16 bits each
-    if (bm_cull_lds_bytes(rec.n_tiles) + 1024 > kBmLdsPerCu) return;  // the culling kernel keeps every receptor box in LDS: ~430 tiles at most
+    if (rec.n_tiles > 1024 || lig.n_tiles > 1024) return false;  // an item of the exact path names its atoms in 16 bits each
+    if (bm_cull_lds_bytes(rec.n_tiles) + 1024 > kBmLdsPerCu) return false;  // the culling kernel keeps every receptor box in LDS: ~430 tiles at most
     // Table values reach a pose's sum as 64-bit fixed point (dfire_bm.hpp): a table that could overflow it or that the scale
     // would resolve too coarsely (beyond kBmFixLimit), or one that holds a value the reference would carry as inf / NaN
     // (src/dfire.rs:338), stays with the pose-major kernels.
     double table_vmax = 0.0;
     for (size_t i = 0; i < LD_DFIRE_TABLE_LEN; i++) {
-        if (!(std::fabs(desc.potential[i]) <= kBmFixLimit)) return;
+        if (!(std::fabs(desc.potential[i]) <= kBmFixLimit)) return false;
         table_vmax = std::max(table_vmax, std::fabs(desc.potential[i]));
     }
     double centre[3], half;
@@ -861,7 +815,7 @@ void Scorer::build_bm(const ld_scorer_desc &desc) {
         const double f = std::atof(e);
         if (f >= 1.0 && f <= 1000.0) eps *= f;
     }
-    if (!(eps < 8.0)) return;  // a complex thousands of angstroms across: the pose-major kernels
+    if (!(eps < 8.0)) return false;  // a complex thousands of angstroms across: the pose-major kernels
 
     BmModel &M = bm_;
     M.rec_n_real = rec.n_real;
@@ -872,13 +826,13 @@ void Scorer::build_bm(const ld_scorer_desc &desc) {
     M.rec_tindex = rec.tindex;
     M.rec_slot = rec.slot;
     M.rec_flag_words = pair_.rec.flag_words;
-    M.lig = tiled_.lig;
+    M.lig = tiled_lig_;
     M.cx = centre[0];
     M.cy = centre[1];
     M.cz = centre[2];
     M.ubound = (float)ubound;
     M.box_pad = std::nextafter((float)(2.0 * dfire_bm_pose_error(ubound, extent, anm)), INFINITY);
-    M.table = tiled_.table;
+    M.table = tiled_table_;
     M.iface_scaled = 4.0 * pair_.iface_d2;
     {
         const DfireBinning b = build_dfire_binning();
@@ -1107,7 +1061,7 @@ void Scorer::build_bm(const ld_scorer_desc &desc) {
         const double flex_reach = anm ? 2.0 * std::sqrt(3.0) * (double)kBmWildUnits / kBmKappa : 0.0;   // (W bounds a coordinate: sqrt(3) W the atom)
         const size_t reach_count = dfire_bm_reach_count(desc.receptor.coordinates, desc.receptor.n_atoms, 15.0 + tile_radius + 0.01 + flex_reach);
         M.fix_scale = dfire_bm_fix_scale(table_vmax, reach_count, nullptr);
-        if (!(M.fix_scale > 0.0)) return;
+        if (!(M.fix_scale > 0.0)) return false;
         std::vector<long long> rows((size_t)kBmTypes * kBmTypes * kBmRowSlots, 0), ones(rows.size(), 0);
         for (uint32_t l = 0; l < (uint32_t)kBmTypes; l++)
             for (uint32_t r = 0; r < (uint32_t)kBmTypes; r++) {
@@ -1125,7 +1079,7 @@ void Scorer::build_bm(const ld_scorer_desc &desc) {
     // round 5 also 64 bytes of partial sums per entry, which now live in a per-wave scratch: the budgets kept their pass sizes)
     const size_t tile_pairs = (size_t)rec.n_tiles * lig.n_tiles;
     constexpr size_t kEntryBytes = 12;
-    if (tile_pairs * kBmPassQuantum * kEntryBytes > ((size_t)2560 << 20)) return;   // even the smallest pass (1024 poses) would not fit 2.5 GiB: the pose-major kernels
+    if (tile_pairs * kBmPassQuantum * kEntryBytes > ((size_t)2560 << 20)) return false;   // even the smallest pass (1024 poses) would not fit 2.5 GiB: the pose-major kernels
     size_t chunk = ((size_t)640 << 20) / (kEntryBytes * tile_pairs);   // a second such workspace exists while two passes are in flight
     chunk = std::min<size_t>(kBmMaxPassPoses, std::max<size_t>(kBmPassQuantum, chunk / kBmPassQuantum * kBmPassQuantum));
     if (const char *e = std::getenv("LIGHTDOCK_BM_CHUNK")) {   // tests, A/B: any pass size that the layout can hold --
@@ -1135,7 +1089,7 @@ void Scorer::build_bm(const ld_scorer_desc &desc) {
         const size_t by_index = ((size_t)1 << 32) / tile_pairs - 1, by_bytes = ((size_t)2560 << 20) / (kEntryBytes * tile_pairs);
         if (v >= 1) chunk = std::max<size_t>(1, std::min<size_t>({(size_t)v, kBmMaxPassPoses, by_index, by_bytes}));
     }
-    if (tile_pairs * chunk >= ((size_t)1 << 32)) return;   // (unreachable with the 640 MiB default: 12 bytes an entry)
+    if (tile_pairs * chunk >= ((size_t)1 << 32)) return false;   // (unreachable with the 640 MiB default: 12 bytes an entry)
     bm_chunk_ = chunk;
     {
         const char *e = std::getenv("LIGHTDOCK_BM_LANES");
@@ -1145,7 +1099,7 @@ void Scorer::build_bm(const ld_scorer_desc &desc) {
             hip_check(hipEventCreateWithFlags(&bm_join_, hipEventDisableTiming), "hipEventCreate");
         }
     }
-    use_bm_ = true;
+    return true;
 }
 
 // Poses per block-major pass: at most bm_chunk_ (the entry workspace).  Batches that need several passes alternate them between two
@@ -1280,24 +1234,6 @@ PackedPrepareLaunch Scorer::packed_prepare_launch(const double *poses, size_t st
     return p;
 }
 
-PrepareReceptorLaunch Scorer::prepare_launch(const double *poses, size_t stride, const uint8_t *active, size_t n) const {
-    PrepareReceptorLaunch p;
-    p.n_real = tiled_rec_soa_.n_real;
-    p.n_tiles = tiled_rec_soa_.n_tiles;
-    p.x = tiled_rec_soa_.x;
-    p.y = tiled_rec_soa_.y;
-    p.z = tiled_rec_soa_.z;
-    p.tindex = tiled_rec_soa_.tindex;
-    p.slot = tiled_rec_soa_.slot;
-    p.num_anm = tiled_rec_soa_.num_anm;
-    p.modes = tiled_rec_soa_.modes;
-    p.poses = poses;
-    p.stride = stride;
-    p.active = active;
-    p.n_poses = n;
-    return p;
-}
-
 Scorer::~Scorer() {
     for (auto &e : events_) {
         (void)hipEventDestroy(e.first);
@@ -1313,33 +1249,23 @@ Scorer::~Scorer() {
         (void)hipStreamSynchronize(own_stream_);
         (void)hipStreamDestroy(own_stream_);
     }
-    ws_partial_.release();
-    ws_flags_.release();
-    ws_counts_.release();
-    ws_tested_.release();
-    ws_rec_atoms_.release();
-    ws_rec_sub_.release();
-    ws_rec_tile_.release();
-    ws_rec_pairs_.release();
-    ws_exact_.release();
-    for (DeviceBuffer *b : {&ws_bm_rt_, &ws_bm_tp_count_, &ws_bm_ent_row_, &ws_bm_jobs_, &ws_bm_job_cost_, &ws_bm_job_order_, &ws_bm_ent_mask_, &ws_bm_queue_, &ws_bm_ent_partial_, &ws_bm_tile_sum_,
-                            &ws_bm_tile_tested_, &ws_bm_exact_fix_, &ws_bm_exact_pairs_, &ws_bm_amp_})
-        b->release();
-    ws_poses_.release();
-    ws_energies_.release();
+    // (the workspace buffers free themselves after this body, behind the synchronisations above)
 }
 
 uint64_t Scorer::workspace_generation() const {
-    return ws_partial_.generation + ws_flags_.generation + ws_counts_.generation + ws_tested_.generation + ws_exact_.generation +
-           ws_rec_atoms_.generation + ws_rec_sub_.generation + ws_rec_tile_.generation + ws_rec_pairs_.generation + ws_bm_rt_.generation +
-           ws_bm_tp_count_.generation + ws_bm_ent_row_.generation + ws_bm_jobs_.generation + ws_bm_job_cost_.generation + ws_bm_job_order_.generation + ws_bm_ent_mask_.generation + ws_bm_queue_.generation + ws_bm_ent_partial_.generation +
-           ws_bm_tile_sum_.generation + ws_bm_tile_tested_.generation +
-           ws_bm_exact_fix_.generation + ws_bm_exact_pairs_.generation + ws_bm_amp_.generation;
+    uint64_t g = 0;
+    // every buffer a launch of energy_batch_device can touch (ws_poses_ / ws_energies_ serve energy_batch_host only)
+    for (const DeviceBuffer *b : {&ws_partial_, &ws_flags_, &ws_counts_, &ws_tested_, &ws_exact_, &ws_rec_sub_, &ws_rec_tile_, &ws_rec_pairs_,
+                                  &ws_bm_debug_, &ws_bm_rt_, &ws_bm_tp_count_, &ws_bm_ent_row_, &ws_bm_jobs_, &ws_bm_job_cost_, &ws_bm_job_order_,
+                                  &ws_bm_ent_mask_, &ws_bm_queue_, &ws_bm_ent_partial_, &ws_bm_tile_sum_, &ws_bm_tile_tested_, &ws_bm_exact_fix_,
+                                  &ws_bm_exact_pairs_, &ws_bm_amp_})
+        g += b->generation;
+    return g;
 }
 
 void Scorer::reserve_workspace(size_t n_poses, bool counts) {
     const size_t words = (size_t)(pair_.rec.flag_words + pair_.lig.flag_words);
-    const size_t chunks = (size_t)std::max(pair_.n_chunks, use_packed_ ? packed_.n_groups * kPackedPartialsPerGroup : use_tiled_ ? tiled_.n_groups : 0);
+    const size_t chunks = (size_t)std::max(pair_.n_chunks, route_ == PairRoute::all_pairs ? 0 : packed_.n_groups * kPackedPartialsPerGroup);
     ws_partial_.reserve(n_poses * chunks * 2 * sizeof(double));
     ws_flags_.reserve(std::max<size_t>(n_poses * words * sizeof(uint32_t), 16));
     if (counts) {
@@ -1347,7 +1273,7 @@ void Scorer::reserve_workspace(size_t n_poses, bool counts) {
         ws_tested_.reserve(n_poses * chunks * sizeof(uint32_t));
         ws_exact_.reserve(n_poses * chunks * sizeof(uint32_t));
     }
-    if (use_bm_) {
+    if (route_ == PairRoute::block_major) {
         const size_t n_lt = (size_t)bm_.lig.n_tiles, n_rt = (size_t)bm_.rec_n_tiles, tile_pairs = n_lt * n_rt;
         const size_t cap = bm_pass_poses(n_poses), sets = bm_sets(n_poses);   // a second set only while two passes are in flight
         const size_t parts = tile_pairs * (cap / 64 + 1), waves = (size_t)n_cus_ * kBmWavesPerCu;
@@ -1382,12 +1308,11 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
     if (stride < pose_len()) throw Error(LD_ERR_INVALID, "energy_batch: stride shorter than a pose row");
     // the list is the compacted form of the mask: the pair kernels walk the list, the tail kernel the mask
     if (d_list && (!d_active || !d_count)) throw Error(LD_ERR_INVALID, "energy_batch: a pose list needs its device-side count and the matching active mask");
-    if (use_tiled_ && rec_anm_per_pose_ && !use_bm_) {   // (the block-major path keeps a pose's receptor BOXES only: 36 bytes an atom less)
+    if (route_ == PairRoute::packed && rec_anm_per_pose_) {   // (the block-major path keeps a pose's receptor BOXES only: 36 bytes an atom less)
         // every pose carries its own deformed receptor image: bound that workspace (8 GiB) by
         // slicing very large batches; poses are independent, so the results do not change
-        const size_t pad = (size_t)tiled_.rec.n_tiles * 64;
-        const size_t per_pose = (use_packed_ ? pad / 2 * sizeof(PackedRecPair) : pad * sizeof(TiledAtom)) +
-                                (pad / 8 + pad / 64) * sizeof(TiledBox);
+        const size_t pad = (size_t)packed_.rec.n_tiles * 64;
+        const size_t per_pose = pad / 2 * sizeof(PackedRecPair) + (pad / 8 + pad / 64) * sizeof(TiledBox);
         static const size_t cap = [] {  // LIGHTDOCK_RECEPTOR_IMAGE_MIB: test hook for the slicing
             const char *e = std::getenv("LIGHTDOCK_RECEPTOR_IMAGE_MIB");
             const long v = e ? std::atol(e) : 0;
@@ -1415,7 +1340,7 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
 
     const size_t words = (size_t)(p.rec.flag_words + p.lig.flag_words);
     // (the block-major path clears a pose's flag words in dfire_bm_pose: one launch less per step)
-    if (words > 0 && !use_bm_) hip_check(hipMemsetAsync(p.flags, 0, n * words * sizeof(uint32_t), stream_), "hipMemsetAsync(flags)");
+    if (words > 0 && route_ != PairRoute::block_major) hip_check(hipMemsetAsync(p.flags, 0, n * words * sizeof(uint32_t), stream_), "hipMemsetAsync(flags)");
     const bool timing = timing_ && !capturing_;
     if (timing) {
         if (events_used_ == events_.size()) {
@@ -1434,10 +1359,12 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
         }
         hip_check(hipEventRecord(events_[events_used_].first, stream_), "hipEventRecord");
     }
-    if (use_bm_) {
+    switch (route_) {
+    case PairRoute::block_major:
         p.n_chunks = 1;  // dfire_bm_gather leaves one partial per pose
         run_bm(n, d_poses, stride, d_active, d_pair_counts != nullptr, d_list, d_count);
-    } else if (use_packed_) {
+        break;
+    case PairRoute::packed: {
         PackedLaunch t = packed_;
         t.poses = d_poses;
         t.stride = stride;
@@ -1472,37 +1399,11 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
             t.rec.pose_stride_tile = pad / 64;
         }
         hip_check(launch_dfire_packed(t, stream_), "launch dfire_packed_pairs");
-    } else     if (use_tiled_) {
-        TiledLaunch t = tiled_;
-        t.poses = d_poses;
-        t.stride = stride;
-        t.active = d_active;
-        t.n_poses = n;
-        t.partial = p.partial;
-        t.flags = p.flags;
-        t.count_partial = p.count_partial;
-        t.tested_partial = p.count_partial ? static_cast<uint32_t *>(ws_tested_.ptr) : nullptr;
-        p.n_chunks = t.n_groups;  // the tail kernel folds this many partials
-        if (rec_anm_per_pose_) {  // one deformed receptor image per pose (src/dfire.rs:304-320)
-            const size_t pad = (size_t)t.rec.n_tiles * 64;
-            ws_rec_atoms_.reserve(n * pad * sizeof(TiledAtom));
-            ws_rec_sub_.reserve(n * (pad / 8) * sizeof(TiledBox));
-            ws_rec_tile_.reserve(n * (pad / 64) * sizeof(TiledBox));
-            PrepareReceptorLaunch pr = prepare_launch(d_poses, stride, d_active, n);
-            pr.atoms_out = static_cast<TiledAtom *>(ws_rec_atoms_.ptr);
-            pr.sub_out = static_cast<TiledBox *>(ws_rec_sub_.ptr);
-            pr.tile_out = static_cast<TiledBox *>(ws_rec_tile_.ptr);
-            hip_check(launch_prepare_receptor(pr, stream_), "launch dfire_prepare_receptor");
-            t.rec.atoms = pr.atoms_out;
-            t.rec.sub_boxes = pr.sub_out;
-            t.rec.tile_boxes = pr.tile_out;
-            t.rec.pose_stride_atoms = pad;
-            t.rec.pose_stride_sub = pad / 8;
-            t.rec.pose_stride_tile = pad / 64;
-        }
-        hip_check(launch_dfire_tiled(t, stream_), "launch dfire_tiled_pairs");
-    } else {
+        break;
+    }
+    case PairRoute::all_pairs:
         hip_check(launch_pair_kernel(p, stream_), "launch pose_energy_pairs");
+        break;
     }
     if (timing) {
         hip_check(hipEventRecord(events_[events_used_].second, stream_), "hipEventRecord");
@@ -1538,9 +1439,9 @@ void Scorer::energy_batch_host(size_t n, const double *poses, size_t stride, dou
 }
 
 void Scorer::last_block_counts(size_t n, uint32_t *out_host) {
-    if (!use_tiled_) throw Error(LD_ERR_UNSUPPORTED, "block counts exist for the tiled DFIRE kernel only");
+    if (route_ == PairRoute::all_pairs) throw Error(LD_ERR_UNSUPPORTED, "block counts exist for a box-culled, tiled DFIRE kernel only (block-major or packed), not for all pairs");
     if (!out_host) throw Error(LD_ERR_INVALID, "null output");
-    const size_t groups = (size_t)(use_bm_ ? 1 : use_packed_ ? packed_.n_groups * kPackedPartialsPerGroup : tiled_.n_groups);
+    const size_t groups = (size_t)(route_ == PairRoute::block_major ? 1 : packed_.n_groups * kPackedPartialsPerGroup);
     if (ws_tested_.bytes < n * groups * sizeof(uint32_t)) throw Error(LD_ERR_INVALID, "no counting launch of that size has run");
     std::vector<uint32_t> part(n * groups);
     hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
@@ -1572,10 +1473,26 @@ void Scorer::pair_kernel_time(double *total_ms, uint64_t *launches) {
 }
 
 void Scorer::kernel_info(ld_kernel_info *out) const {
-    out->pair_kernel_name = use_bm_ ? "dfire_bm_pairs" : use_packed_ ? "dfire_packed_pairs" : use_tiled_ ? "dfire_tiled_pairs" : pair_kernel_name(method_);
-    out->block_threads = use_bm_ ? (uint32_t)kBmWaves * 64 : use_packed_ ? (uint32_t)kPackedWaves * 64 : use_tiled_ ? (uint32_t)tiled_.waves * 64 : (uint32_t)kBlockThreads;
-    out->receptor_chunks = (uint32_t)(use_bm_ ? 1 : use_packed_ ? packed_.n_groups : use_tiled_ ? tiled_.n_groups : pair_.n_chunks);
-    out->lds_bytes = (uint32_t)(use_bm_ ? bm_pairs_lds_bytes() : use_packed_ ? packed_kernel_lds_bytes(packed_.cells_per_unit) : use_tiled_ ? tiled_kernel_lds_bytes(tiled_) : pair_kernel_lds_bytes(pair_));
+    switch (route_) {
+    case PairRoute::block_major:
+        out->pair_kernel_name = "dfire_bm_pairs";
+        out->block_threads = (uint32_t)kBmWaves * 64;
+        out->receptor_chunks = 1;
+        out->lds_bytes = (uint32_t)bm_pairs_lds_bytes();
+        break;
+    case PairRoute::packed:
+        out->pair_kernel_name = "dfire_packed_pairs";
+        out->block_threads = (uint32_t)kPackedWaves * 64;
+        out->receptor_chunks = (uint32_t)packed_.n_groups;
+        out->lds_bytes = (uint32_t)packed_kernel_lds_bytes(packed_.cells_per_unit);
+        break;
+    case PairRoute::all_pairs:
+        out->pair_kernel_name = pair_kernel_name(method_);
+        out->block_threads = (uint32_t)kBlockThreads;
+        out->receptor_chunks = (uint32_t)pair_.n_chunks;
+        out->lds_bytes = (uint32_t)pair_kernel_lds_bytes(pair_);
+        break;
+    }
     out->pair_tests_per_pose = (uint64_t)pair_.rec.n * (uint64_t)pair_.lig.n;
     // DFIRE 26 B/atom (3 f64 + u16 type), DNA 48 B/atom (6 f64), + 240 B/atom
     // per ANM-deformed molecule (10 modes x 24 B), + 56 B pose in + 8 B energy out.

@@ -41,11 +41,15 @@ class DeviceArena {
     std::vector<void *> blocks_;
 };
 
-// A grow-only device buffer.
+// A grow-only device buffer, freed with its owner.
 struct DeviceBuffer {
     void *ptr = nullptr;
     size_t bytes = 0;
     uint64_t generation = 0;  // bumped whenever the block is reallocated
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer &) = delete;
+    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+    ~DeviceBuffer() { release(); }
     void reserve(size_t want);
     void release();
 };
@@ -103,9 +107,9 @@ class Scorer {
     void energy_batch_host(size_t n, const double *poses, size_t stride, double *energies);
 
     void kernel_info(ld_kernel_info *out) const;
-    // diagnostics of the last counting launch: 8x8 atom-pair blocks evaluated per pose (tiled kernel)
+    // diagnostics of the last counting launch: 8x8 atom-pair blocks evaluated per pose (culled DFIRE kernels)
     void last_block_counts(size_t n, uint32_t *out_host);
-    uint32_t bm_quiet_subtiles() const { return use_bm_ ? bm_quiet_subtiles_ : 0u; }
+    uint32_t bm_quiet_subtiles() const { return route_ == PairRoute::block_major ? bm_quiet_subtiles_ : 0u; }
     void enable_timing(bool on);
     void pair_kernel_time(double *total_ms, uint64_t *launches);
 
@@ -114,9 +118,9 @@ class Scorer {
                          std::vector<uint32_t> &group_offsets, std::vector<uint32_t> &group_slots,
                          std::vector<uint32_t> &membrane_slots);
     void reserve_workspace(size_t n_poses, bool counts);
-    void build_tiled(const ld_scorer_desc &desc);
-    void build_packed(const ld_scorer_desc &desc);  // after build_tiled: shares its table, ligand and tile order
-    void build_bm(const ld_scorer_desc &desc);      // after build_packed: the block-major path (rigid molecules; the ANM form for molecules that flex)
+    void build_tile_order(const ld_scorer_desc &desc, bool latency);  // what the culled paths share: tile order, patch table, ligand view, split
+    bool build_packed(const ld_scorer_desc &desc);  // after build_tile_order; false: declined (the receptor is too long for the f32 frame)
+    bool build_bm(const ld_scorer_desc &desc);      // after build_packed: the block-major path (rigid molecules; the ANM form for molecules that flex)
     void run_bm(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, bool counts, const uint32_t *d_list,
                 const uint32_t *d_count);
     void frame_of_receptor(const ld_molecule &rec, double centre[3], double *half) const;
@@ -133,7 +137,6 @@ class Scorer {
         std::vector<double> hmodes;       // host copy of `modes`: [mode][xyz][padded atoms]
     };
     void upload_tiled_molecule(const ld_molecule &m, bool is_receptor, TiledSoA &out);
-    PrepareReceptorLaunch prepare_launch(const double *poses, size_t stride, const uint8_t *active, size_t n) const;
     PackedPrepareLaunch packed_prepare_launch(const double *poses, size_t stride, const uint8_t *active, size_t n) const;
 
     int device_ = 0;
@@ -145,15 +148,18 @@ class Scorer {
     DeviceArena arena_;
     PairLaunch pair_;     // receptor / ligand / table pointers filled once; batch fields per call
     TailTables tail_;
-    bool use_tiled_ = false;  // DFIRE: a bounding-box culled kernel instead of all-pairs
-    TiledLaunch tiled_;
-    bool use_packed_ = false;  // DFIRE default: culling + packed-f32 pair test with exact f64 path (kernels/dfire_packed.hpp)
+    // K1, fixed in the constructor: the block-major path (kernels/dfire_bm.hpp, the DFIRE default), the pose-major packed-f32
+    // kernel (kernels/dfire_packed.hpp), or the all-pairs kernel of pose_energy.hpp (DNA, and DFIRE where the culled paths decline)
+    enum class PairRoute { block_major, packed, all_pairs };
+    PairRoute route_ = PairRoute::all_pairs;
+    TiledLigand tiled_lig_;                 // the ligand in tile order, as the culled kernels read it
+    const double *tiled_table_ = nullptr;   // the potential in 2 x 2 x 4 patches (kernels/dfire_tiled.hpp)
+    int tiled_split_ = 1;                   // waves sharing one ligand tile in the pose-major kernel
     PackedLaunch packed_;
     const uint32_t *packed_lut_full_ = nullptr;  // the LUT without elided zero bins (counting launches)
     uint32_t packed_zero_bins_ = 0;
     uint32_t bm_quiet_subtiles_ = 0;   // receptor subtiles of the block-major path whose atoms' rows of the potential are zero (build_bm)
     DeviceBuffer ws_rec_pairs_, ws_exact_;
-    bool use_bm_ = false;      // DFIRE: the block-major path (kernels/dfire_bm.hpp) evaluates every batch
     BmModel bm_;
     TiledSoA tiled_lig_soa_;
     size_t bm_chunk_ = 0;      // poses per block-major pass (bounds the entry workspace)
@@ -165,10 +171,10 @@ class Scorer {
     int n_cus_ = 256;
     DeviceBuffer ws_bm_debug_, ws_bm_jobs_, ws_bm_job_cost_, ws_bm_job_order_, ws_bm_rt_, ws_bm_tp_count_, ws_bm_ent_row_, ws_bm_ent_mask_, ws_bm_queue_, ws_bm_ent_partial_, ws_bm_tile_sum_,
         ws_bm_tile_tested_, ws_bm_exact_fix_, ws_bm_exact_pairs_, ws_bm_amp_;
-    TiledSoA tiled_rec_soa_;          // receptor in tile order (input of dfire_prepare_receptor)
+    TiledSoA tiled_rec_soa_;          // receptor in tile order (input of dfire_packed_prepare)
     bool rec_anm_per_pose_ = false;   // receptor ANM: one receptor image per pose per launch
-    DeviceBuffer ws_rec_atoms_, ws_rec_sub_, ws_rec_tile_;
-    std::vector<uint32_t> type_perm_rec_, type_perm_lig_;  // DFIRE type -> number used by the tiled kernel's table layout
+    DeviceBuffer ws_rec_sub_, ws_rec_tile_;
+    std::vector<uint32_t> type_perm_rec_, type_perm_lig_;  // DFIRE type -> number used by the patch table's layout
     std::vector<int32_t> host_slot_rec_, host_slot_lig_;  // per original atom, as uploaded to the all-pairs path
     HostMolecule host_rec_, host_lig_;
     DeviceBuffer ws_partial_, ws_flags_, ws_counts_, ws_tested_, ws_poses_, ws_energies_;

@@ -67,18 +67,9 @@ hipError_t launch_finish_kernel(const FinishLaunch &f, hipStream_t) {
         if (!f.active || f.active[i]) f.energies[i] = 0.0;   // the output buffer really has n_poses doubles
     return hipSuccess;
 }
-size_t tiled_kernel_lds_bytes(const TiledLaunch &) { return 0; }
-hipError_t launch_dfire_tiled(const TiledLaunch &t, hipStream_t) {
-    if (t.n_poses && t.partial) t.partial[2 * (t.n_poses * (size_t)t.n_groups - 1) + 1] = 0.0;   // last slot of the workspace
-    return hipSuccess;
-}
-hipError_t launch_prepare_receptor(const PrepareReceptorLaunch &p, hipStream_t) {
-    if (p.n_poses && p.atoms_out) std::memset(p.atoms_out, 0, p.n_poses * (size_t)p.n_tiles * 64 * sizeof(TiledAtom));
-    return hipSuccess;
-}
 size_t packed_kernel_lds_bytes(int) { return 0; }
 hipError_t launch_dfire_packed(const PackedLaunch &t, hipStream_t) {
-    if (t.n_poses && t.partial) t.partial[2 * (t.n_poses * (size_t)t.n_groups - 1) + 1] = 0.0;
+    if (t.n_poses && t.partial) t.partial[2 * (t.n_poses * (size_t)t.n_groups - 1) + 1] = 0.0;   // last slot of the workspace
     return hipSuccess;
 }
 size_t bm_pairs_lds_bytes() { return 0; }

@@ -30,7 +30,7 @@ NORTH_STAR_TOL = 1e-4
 
 def rel_err(got, want):
     """Relative error (values below 1e-9 are measured against 1e-9).  For every path whose sums are f64: DNA / PYDOCK, the
-    pose-major DFIRE kernels (ANM complexes, LIGHTDOCK_DFIRE_KERNEL=packed | tiled | allpairs), K2's luciferins of those."""
+    pose-major DFIRE kernels (ANM complexes, LIGHTDOCK_DFIRE_KERNEL=packed | allpairs), K2's luciferins of those."""
     return np.max(np.abs(got - want) / np.maximum(np.abs(want), 1e-9))
 
 
@@ -53,8 +53,9 @@ BM_DFIRE = ("1ppe", "1k4c", "2uuy", "ab_icode")   # the DFIRE fixtures: the bloc
 
 
 def err_for(name, env=None):
-    """The error measure of a fixture's default K1 (or of the kernel `env` forces)."""
-    kernel = (env or {}).get("LIGHTDOCK_DFIRE_KERNEL", "bm")
+    """The error measure of a fixture's default K1 (or of the kernel `env` forces; LIGHTDOCK_TILED_LATENCY=1: the pose-major one)."""
+    env = env or {}
+    kernel = env.get("LIGHTDOCK_DFIRE_KERNEL", "packed" if env.get("LIGHTDOCK_TILED_LATENCY") else "bm")
     return bm_err if name in BM_DFIRE and kernel == "bm" else rel_err
 
 
@@ -425,9 +426,9 @@ def test_real_dcparams_goldens_on_gpu(pkg, orc, real_dcparams):
 
 @pytest.mark.parametrize("env", [
     {"LIGHTDOCK_DFIRE_KERNEL": "allpairs"},
-    {"LIGHTDOCK_DFIRE_KERNEL": "tiled"},
-    {"LIGHTDOCK_DFIRE_KERNEL": "tiled", "LIGHTDOCK_TILED_WAVES": "3"},
-    {"LIGHTDOCK_DFIRE_KERNEL": "tiled", "LIGHTDOCK_TILED_WAVES": "16"},
+    {"LIGHTDOCK_DFIRE_KERNEL": "tiled"},      # no such kernel any more: an unknown value, the default route
+    {"LIGHTDOCK_TILED_LATENCY": "1"},         # the single-swarm CLI's setting: the pose-major kernel, split 3 below 32 ligand tiles
+    {"LIGHTDOCK_TILED_LATENCY": "1", "LIGHTDOCK_DFIRE_KERNEL": "bm"},     # ... with the block-major path forced
     {"LIGHTDOCK_DFIRE_KERNEL": "packed"},                                  # the pose-major kernel (what ANM runs use)
     {"LIGHTDOCK_DFIRE_KERNEL": "packed", "LIGHTDOCK_PACKED_CELLS": "2"},    # ... with half-unit LUT cells
     {"LIGHTDOCK_DFIRE_KERNEL": "packed", "LIGHTDOCK_PACKED_EPS_SCALE": "8"},
@@ -440,10 +441,10 @@ def test_real_dcparams_goldens_on_gpu(pkg, orc, real_dcparams):
 ])
 @pytest.mark.parametrize("name", ["1ppe", "1k4c", "2uuy"])
 def test_dfire_kernel_variants_agree(pkg, orc, table, scorers, name, env):
-    """The all-pairs kernel, the box-culled f64 kernel (in several workgroup shapes), the pose-major packed-f32
-    kernel and the default block-major path (both: box culling + f32 pair test with exact f64 path, in several
-    settings) are routes to the same sum: all match the oracle, and the in-cutoff pair counts -- which neither
-    culling nor the f32 test may change by a single pair -- are identical."""
+    """The all-pairs kernel, the pose-major packed-f32 kernel and the default block-major path (both: box culling + f32 pair
+    test with exact f64 path, in several settings, and as the environment picks them) are routes to the same sum: all match
+    the oracle, and the in-cutoff pair counts -- which neither culling nor the f32 test may change by a single pair -- are
+    identical."""
     torch = pytest.importorskip("torch")
     default_hip, cpu = scorers(name)
     method, rec, lig, kw = case_kwargs(name, orc, table)
@@ -633,7 +634,7 @@ def test_tiny_molecules_and_cutoff_corners(pkg, orc, table, tmp_path):
     assert cpu.energy_row(poses[2]) == 4.7
     want = cpu.energy_rows(poses)
     assert want[0] == want[1]
-    for env in ({}, {"LIGHTDOCK_DFIRE_KERNEL": "allpairs"}, {"LIGHTDOCK_TILED_WAVES": "16", "LIGHTDOCK_TILED_SPLIT": "2"}):
+    for env in ({}, {"LIGHTDOCK_DFIRE_KERNEL": "allpairs"}, {"LIGHTDOCK_TILED_SPLIT": "2"}):
         old = {k: os.environ.get(k) for k in env}
         os.environ.update(env)
         try:
@@ -1207,6 +1208,38 @@ def test_receptor_larger_than_one_ballot(pkg, orc, table, tmp_path, n_rec, box):
     finally:
         os.environ.pop("LIGHTDOCK_DFIRE_KERNEL")
     assert bm_err(ap.energy_batch(poses), want) < REL_TOL
+
+
+def test_receptor_too_long_for_the_packed_frame(pkg, orc, table, tmp_path):
+    """A receptor more than ~8100 A long on one axis: no f32 frame of the packed kernels holds it with a small enough error
+    bound (scorer.cpp, build_packed), so the scorer takes the all-pairs kernel -- the oracle's energies and in-cutoff pair
+    counts.  Two residue clumps 8300 A apart, the ligand posed next to either of them or far from both."""
+    torch = pytest.importorskip("torch")
+    rng = np.random.default_rng(41)
+    rec, lig = str(tmp_path / "long_rec.pdb"), str(tmp_path / "long_lig.pdb")
+    clumps = [_random_molecule(rng, 150, 16.0, "A"), _random_molecule(rng, 150, 16.0, "A")]
+    _write_pdb(rec, [(a, r, c, seq + 100 * k, x + x0, y, z) for k, x0 in enumerate((-900.0, 7400.0)) for a, r, c, seq, x, y, z in clumps[k]])
+    _write_pdb(lig, _random_molecule(rng, 90, 10.0, "B"))
+    hip = pkg.Scorer.from_pdb("dfire", rec, lig, potential=table)
+    cpu = orc.Scorer("dfire", rec, lig, potential=table)
+    assert hip.kernel_info()["pair_kernel_name"] == "pose_energy_pairs<0"
+    q = rng.normal(size=(24, 4))
+    t = np.array([-900.0, 0.0, 0.0]) + rng.uniform(-10.0, 10.0, size=(24, 3))
+    t[16:22, 0] += 8300.0        # next to the other clump
+    t[22:, 0] = 3000.0           # between them: nothing in range
+    poses = np.ascontiguousarray(np.concatenate([t, q / np.linalg.norm(q, axis=1, keepdims=True)], axis=1))
+    want = [cpu.energy_ex_row(p) for p in poses]
+    want_counts = np.array([w[1][5] for w in want]).astype(np.int64)
+    assert np.all(want_counts[:22] > 0) and np.all(want_counts[22:] == 0)
+    dev = torch.device("cuda:0")
+    d_poses = torch.from_numpy(poses).to(dev)
+    d_out = torch.zeros(len(poses), dtype=torch.float64, device=dev)
+    d_cnt = torch.zeros(len(poses), dtype=torch.int32, device=dev)
+    hip.energy_batch_device(len(poses), d_poses.data_ptr(), 7, d_out.data_ptr(), None, d_cnt.data_ptr())
+    torch.cuda.synchronize()
+    assert np.array_equal(d_cnt.cpu().numpy().astype(np.int64), want_counts)
+    assert rel_err(d_out.cpu().numpy(), np.array([w[0] for w in want])) < REL_TOL
+    assert rel_err(hip.energy_batch(poses), np.array([w[0] for w in want])) < REL_TOL
 
 
 def test_which_kernel_a_flexing_complex_gets(pkg, orc, table, tmp_path):

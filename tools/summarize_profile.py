@@ -9,7 +9,7 @@ import sys
 
 out = sys.argv[1]
 KERNELS = ("dfire_bm_pairs<false", "dfire_bm_cull<false", "dfire_bm_gather", "dfire_bm_pose", "dfire_bm_plan", "dfire_bm_census", "dfire_bm_order",
-           "dfire_packed_pairs<false", "dfire_tiled_pairs<false", "pose_energy_pairs<1", "pose_energy_pairs<0", "gso_movement_phase",
+           "dfire_packed_pairs<false", "pose_energy_pairs<1", "pose_energy_pairs<0", "gso_movement_phase",
            "pose_energy_finish", "dfire_packed_prepare")
 
 
