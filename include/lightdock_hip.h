@@ -154,6 +154,14 @@ int ld_dfire_bm_lut(double ubound, double lig_extent, uint8_t *codes_out, double
  * value beyond 1024 or not finite, or a count beyond 2^23) -- such a scorer runs the pose-major kernels. */
 int ld_dfire_bm_fix_scale(const double *rec_xyz /* n_rec x 3 */, size_t n_rec, double reach, double table_vmax,
                           uint64_t *reach_count_out, int *extra_bits_out, double *scale_out);
+/* The workspace of the block-major DFIRE kernels for one batch shape (host-side, no GPU), for tests: the layout the scorer
+ * itself reserves and points its launches into (kernels/dfire_bm.hpp, bm_layout).  n_rt / n_lt: receptor / ligand tiles; cap:
+ * poses per pass; sets: passes in flight (1 or 2); waves: waves of dfire_bm_pairs; flags: 1 = ANM form, 2 = counting launch,
+ * 4 = LIGHTDOCK_BM_DEBUG.  For each of the 22 regions r: names_out[2 r] = its name, names_out[2 r + 1] = its
+ * buffer's name (static strings), rows_out[5 r ..] = {buffer index, the buffer's bytes (slack included), byte offset of set 0,
+ * byte stride from set to set, bytes of one set}.  A region the shape does not ask for has 0 bytes. */
+int ld_dfire_bm_workspace(size_t n_rt, size_t n_lt, size_t cap, size_t sets, size_t waves, int flags,
+                          const char **names_out /* 2 x 22 */, uint64_t *rows_out /* 5 x 22 */);
 /* The atom order the culled DFIRE kernels use (host-side, no GPU): order_out[slot] = original atom
  * index, UINT32_MAX for padding; length = ceil(n/64)*64.  Consecutive 8 slots ("subtile") and 64
  * slots ("tile") are spatially compact; padding only at the tail.  The energy is a plain sum over

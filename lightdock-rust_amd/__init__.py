@@ -259,6 +259,22 @@ def dfire_bm_fix_scale(rec_xyz, reach, table_vmax):
     return count.value, extra.value, scale.value
 
 
+BM_WS_REGIONS = 22
+
+
+def dfire_bm_workspace(n_rt, n_lt, cap, sets, waves, anm=False, counts=False, debug=False):
+    """The block-major kernels' workspace for one batch shape, see ld_dfire_bm_workspace in the header:
+    {region: dict(buffer=name, buffer_bytes=, base=, stride=, bytes=)}."""
+    names = (C.c_char_p * (2 * BM_WS_REGIONS))()
+    rows = np.zeros((BM_WS_REGIONS, 5), dtype=np.uint64)
+    flags = (1 if anm else 0) | (2 if counts else 0) | (4 if debug else 0)
+    lib = load_library()
+    lib.ld_dfire_bm_workspace.argtypes = [C.c_size_t] * 5 + [C.c_int, C.c_void_p, C.c_void_p]   # (bound here: a library variant of an older build loads without it)
+    _check(lib.ld_dfire_bm_workspace(n_rt, n_lt, cap, sets, waves, flags, C.cast(names, C.c_void_p), _ptr(rows)))
+    return {names[2 * r].decode(): dict(buffer=names[2 * r + 1].decode(), buffer_bytes=int(rows[r, 1]), base=int(rows[r, 2]),
+                                        stride=int(rows[r, 3]), bytes=int(rows[r, 4])) for r in range(BM_WS_REGIONS)}
+
+
 def spatial_tile_order(xyz):
     """Tile order of the DFIRE kernel: slot -> atom index (UINT32_MAX = padding)."""
     xyz = _f64(xyz).reshape(-1, 3)

@@ -197,6 +197,34 @@ int ld_dfire_bm_fix_scale(const double *rec_xyz, size_t n_rec, double reach, dou
         if (scale_out) *scale_out = scale;
     });
 }
+int ld_dfire_bm_workspace(size_t n_rt, size_t n_lt, size_t cap, size_t sets, size_t waves, int flags, const char **names_out,
+                          uint64_t *rows_out) {
+    static_assert(ld::kBmRegions == 22, "the region count the header states");
+    return guarded([&] {
+        if (!n_rt || !n_lt || !cap || sets < 1 || sets > 2) throw ld::Error(LD_ERR_INVALID, "tiles and a pass size, one or two sets");
+        ld::BmShape s;
+        s.n_rt = n_rt;
+        s.n_lt = n_lt;
+        s.cap = cap;
+        s.sets = sets;
+        s.waves = waves;
+        s.anm = (flags & 1) != 0;
+        s.counts = (flags & 2) != 0;
+        s.debug = (flags & 4) != 0;
+        const ld::BmLayout L = ld::bm_layout(s);
+        for (int r = 0; r < ld::kBmRegions; r++) {
+            const ld::BmRegion &g = L.region[r];
+            if (names_out) {
+                names_out[2 * r] = g.name;
+                names_out[2 * r + 1] = g.buffer_name;
+            }
+            if (rows_out) {
+                const uint64_t row[5] = {(uint64_t)g.buffer, L.buffer_bytes[g.buffer], g.base, g.stride, g.bytes};
+                std::memcpy(rows_out + 5 * r, row, sizeof row);
+            }
+        }
+    });
+}
 size_t ld_spatial_tile_order(const double *xyz, size_t n, uint32_t *order_out) {
     size_t len = 0;
     guarded([&] {

@@ -113,7 +113,7 @@ constexpr int kBmCostClasses = 80;           // jobs are drawn in classes of est
 // -- 14 bytes a hit, room for `hit tiles` poses that reach every receptor tile: a pose adds at most one hit per receptor tile, and
 // the list is flushed (one atomic per tile pair) when the next pose might not fit -- plus two words per receptor tile.  The list
 // shrinks for a receptor whose boxes leave less room; one of more than ~430 tiles (27 000 atoms) does not fit 160 KB with any
-// list: such a complex stays with the pose-major kernels (scorer.cpp, build_bm).
+// list: such a complex stays with the pose-major kernels (scorer.cpp, bm_accepts).
 #ifndef LD_BM_CULL_WAVES
 #define LD_BM_CULL_WAVES 4
 #endif
@@ -138,7 +138,7 @@ struct BmModel {
     // receptor (static image in the kappa = 8 frame; no receptor ANM on this path)
     int rec_n_real = 0, rec_n_tiles = 0;
     const PackedRecPair *rec_pairs = nullptr;   // [n_tiles*32]
-    const TiledBox *rec_sub = nullptr;          // [n_tiles*8]; pad0 = the subtile's reach for the culling kernel's box test, squared record units (scorer.cpp, build_bm)
+    const TiledBox *rec_sub = nullptr;          // [n_tiles*8]; pad0 = the subtile's reach for the culling kernel's box test, squared record units (scorer.cpp, bm_box_reaches)
     const TiledBox *rec_tile = nullptr;         // [n_tiles]; pad0 = the largest reach of its subtiles
     const uint32_t *rec_rowoff = nullptr;       // [n_tiles*64]: byte offset of the atom's type column in a table row block
     const float *rec_ops = nullptr;             // [n_tiles*8][kBmOpsFloats]: a receptor subtile as the pair kernel's batches take it -- the centre c of its box
@@ -230,6 +230,117 @@ struct BmLaunch {
     uint32_t *tested_partial = nullptr;    // out: [pose][1] or nullptr
     uint32_t *exact_partial = nullptr;     // out: [pose][1] or nullptr
 };
+
+// ---- The workspace of a block-major batch: THE description (host only).  Everything that reserves, points into or counts
+// the buffers goes through bm_layout(): scorer.cpp's BmWorkspace (reserve, generation), bm_point_launch() below (the pointers
+// of a BmLaunch), and the C ABI's ld_dfire_bm_workspace (tests/test_host_cpu.py restates the table).
+// A batch runs in passes of `cap` poses; `sets` = passes in flight (1 or 2), each with a workspace set of its own.  A region
+// is one array of a BmLaunch: set w of it occupies [base + w * stride, + bytes) of its buffer.  Regions of one buffer follow
+// each other set by set (every set's f32 maps, then every set's f64 rows); only the counters share a set's stride with
+// tp_count.  A region the shape does not ask for (ANM, counting, debug) has no bytes, and its buffer none either.
+struct BmShape {
+    size_t n_rt = 0, n_lt = 0;   // receptor / ligand tiles
+    size_t cap = 0;              // poses per pass
+    size_t sets = 1;
+    size_t waves = 0;            // waves of dfire_bm_pairs: CUs x kBmWavesPerCu
+    bool anm = false, counts = false, debug = false;
+};
+enum BmBuffer { kBmBufRt, kBmBufTpCount, kBmBufJobs, kBmBufJobCost, kBmBufJobOrder, kBmBufQueue, kBmBufEntRow, kBmBufEntMask, kBmBufEntPartial,
+                kBmBufTileSum, kBmBufExactFix, kBmBufAmp, kBmBufAnmSub, kBmBufAnmTile, kBmBufTileTested, kBmBufExactPairs, kBmBufDebug, kBmBuffers };
+enum BmRegionId { kBmRegRt, kBmRegRtExact, kBmRegTpCount, kBmRegJobCount, kBmRegJobNext, kBmRegJobs, kBmRegJobCost, kBmRegJobOrder, kBmRegJobRec,
+                  kBmRegQueue, kBmRegEntRow, kBmRegEntMask, kBmRegEntPartial, kBmRegTileSum, kBmRegExactFix, kBmRegAmp, kBmRegAmpExact, kBmRegAnmSub,
+                  kBmRegAnmTile, kBmRegTileTested, kBmRegExactPairs, kBmRegDebug, kBmRegions };
+struct BmRegion {
+    const char *name = "", *buffer_name = "";
+    int buffer = 0;
+    size_t base = 0, stride = 0, bytes = 0;
+};
+struct BmLayout {
+    size_t buffer_bytes[kBmBuffers] = {};   // trailing slack included
+    BmRegion region[kBmRegions];
+};
+inline BmLayout bm_layout(const BmShape &s) {
+    const size_t tile_pairs = s.n_rt * s.n_lt;
+    const size_t parts = tile_pairs * (s.cap / 64 + 1);   // at most entries / 64 + tile pairs (tile pair, part) pairs
+    BmLayout L;
+    // the next region of buffer b: `per_set` bytes for every set, behind what the buffer holds so far
+    auto put = [&](int r, const char *name, int b, const char *buffer_name, size_t per_set, size_t n_sets) {
+        L.region[r].name = name;
+        L.region[r].buffer_name = buffer_name;
+        L.region[r].buffer = b;
+        L.region[r].base = L.buffer_bytes[b];
+        L.region[r].stride = per_set;
+        L.region[r].bytes = per_set;
+        L.buffer_bytes[b] += n_sets * per_set;
+    };
+    put(kBmRegRt, "rt", kBmBufRt, "rt", s.cap * 12 * sizeof(float), s.sets);              // the f32 maps of every set ...
+    put(kBmRegRtExact, "rt_exact", kBmBufRt, "rt", s.cap * 8 * sizeof(double), s.sets);   // ... then the exact path's rows
+    {   // per set: the tile pairs' entry counts, the launch's counters (job_next = the second) and the culling kernel's item counters
+        const size_t counters = (kBmCounters + kBmCullQueueWords) * sizeof(uint32_t), set = tile_pairs * sizeof(uint32_t) + counters;
+        put(kBmRegTpCount, "tp_count", kBmBufTpCount, "tp_count", set, s.sets);
+        L.region[kBmRegTpCount].bytes = tile_pairs * sizeof(uint32_t);
+        L.region[kBmRegJobCount] = L.region[kBmRegJobNext] = L.region[kBmRegTpCount];
+        L.region[kBmRegJobCount].name = "job_count";
+        L.region[kBmRegJobCount].base = tile_pairs * sizeof(uint32_t);
+        L.region[kBmRegJobCount].bytes = counters;
+        L.region[kBmRegJobNext].name = "job_next";
+        L.region[kBmRegJobNext].base = (tile_pairs + 1) * sizeof(uint32_t);
+        L.region[kBmRegJobNext].bytes = sizeof(uint32_t);
+    }
+    put(kBmRegJobs, "jobs", kBmBufJobs, "jobs", parts * 2 * sizeof(uint32_t), s.sets);
+    put(kBmRegJobCost, "job_cost", kBmBufJobCost, "job_cost", parts * kBmJobRows * sizeof(uint32_t), s.sets);
+    put(kBmRegJobOrder, "job_order", kBmBufJobOrder, "job_order", parts * kBmJobRows * sizeof(uint32_t), s.sets);   // the order ...
+    put(kBmRegJobRec, "job_rec", kBmBufJobOrder, "job_order", parts * kBmJobRows * 4 * sizeof(uint32_t), s.sets);   // ... then the jobs' 16-byte records
+    L.buffer_bytes[kBmBufJobOrder] += 16;
+    put(kBmRegQueue, "queue", kBmBufQueue, "queue", s.waves * kBmQueueCap * sizeof(unsigned long long), s.sets);
+    // (+ one part: a job of dfire_bm_pairs loads its part's entries without looking at the part's end; what lies beyond is never used)
+    put(kBmRegEntRow, "ent_row", kBmBufEntRow, "ent_row", tile_pairs * s.cap * sizeof(uint32_t), s.sets);
+    L.buffer_bytes[kBmBufEntRow] += kBmPartEntries * sizeof(uint32_t);
+    put(kBmRegEntMask, "ent_mask", kBmBufEntMask, "ent_mask", tile_pairs * s.cap * sizeof(unsigned long long), s.sets);
+    L.buffer_bytes[kBmBufEntMask] += kBmPartEntries * sizeof(unsigned long long);
+    put(kBmRegEntPartial, "ent_partial", kBmBufEntPartial, "ent_partial", s.waves * kBmPartEntries * sizeof(long long), s.sets);   // per wave of dfire_bm_pairs: 8 KB, L2 resident
+    put(kBmRegTileSum, "tile_sum", kBmBufTileSum, "tile_sum", s.cap * s.n_lt * sizeof(long long), s.sets);
+    put(kBmRegExactFix, "exact_fix", kBmBufExactFix, "exact_fix", s.cap * sizeof(long long), s.sets);
+    // ANM: the poses' amplitudes by row (every set's f32 rows, then the f64 ones) and the flexed receptor's boxes by row
+    put(kBmRegAmp, "amp", kBmBufAmp, "amp", s.anm ? s.cap * kBmAmpFloats * sizeof(float) : 0, s.sets);
+    put(kBmRegAmpExact, "amp_exact", kBmBufAmp, "amp", s.anm ? s.cap * 2 * kBmMaxModes * sizeof(double) : 0, s.sets);
+    put(kBmRegAnmSub, "anm_sub", kBmBufAnmSub, "anm_sub", s.anm ? s.cap * s.n_rt * 8 * sizeof(TiledBox) : 0, s.sets);
+    put(kBmRegAnmTile, "anm_tile", kBmBufAnmTile, "anm_tile", s.anm ? s.cap * s.n_rt * sizeof(TiledBox) : 0, s.sets);
+    put(kBmRegTileTested, "tile_tested", kBmBufTileTested, "tile_tested", s.counts ? s.cap * s.n_lt * sizeof(uint32_t) : 0, s.sets);
+    put(kBmRegExactPairs, "exact_pairs", kBmBufExactPairs, "exact_pairs", s.counts ? s.cap * sizeof(uint32_t) : 0, s.sets);
+    put(kBmRegDebug, "debug", kBmBufDebug, "debug", s.debug ? s.waves * kBmDebugWords * sizeof(unsigned long long) : 0, 1);
+    L.region[kBmRegDebug].stride = 0;   // not per set
+    return L;
+}
+// The workspace pointers of set w in a BmLaunch; a region without bytes is nullptr.
+inline void bm_point_launch(BmLaunch &t, const BmLayout &L, void *const buffers[kBmBuffers], size_t w) {
+    auto at = [&](int r) -> void * {
+        const BmRegion &g = L.region[r];
+        return g.bytes ? static_cast<char *>(buffers[g.buffer]) + g.base + w * g.stride : nullptr;
+    };
+    t.rt = static_cast<float *>(at(kBmRegRt));
+    t.rt_exact = static_cast<double *>(at(kBmRegRtExact));
+    t.tp_count = static_cast<uint32_t *>(at(kBmRegTpCount));
+    t.job_count = static_cast<uint32_t *>(at(kBmRegJobCount));
+    t.job_next = static_cast<uint32_t *>(at(kBmRegJobNext));
+    t.jobs = static_cast<uint32_t *>(at(kBmRegJobs));
+    t.job_cost = static_cast<uint32_t *>(at(kBmRegJobCost));
+    t.job_order = static_cast<uint32_t *>(at(kBmRegJobOrder));
+    t.job_rec = static_cast<uint32_t *>(at(kBmRegJobRec));
+    t.queue = static_cast<unsigned long long *>(at(kBmRegQueue));
+    t.ent_row = static_cast<uint32_t *>(at(kBmRegEntRow));
+    t.ent_mask = static_cast<unsigned long long *>(at(kBmRegEntMask));
+    t.ent_partial = static_cast<long long *>(at(kBmRegEntPartial));
+    t.tile_sum = static_cast<long long *>(at(kBmRegTileSum));
+    t.exact_fix = static_cast<long long *>(at(kBmRegExactFix));
+    t.amp = static_cast<float *>(at(kBmRegAmp));
+    t.amp_exact = static_cast<double *>(at(kBmRegAmpExact));
+    t.anm_sub = static_cast<TiledBox *>(at(kBmRegAnmSub));
+    t.anm_tile = static_cast<TiledBox *>(at(kBmRegAnmTile));
+    t.tile_tested = static_cast<uint32_t *>(at(kBmRegTileTested));
+    t.exact_pairs = static_cast<uint32_t *>(at(kBmRegExactPairs));
+    t.debug = static_cast<unsigned long long *>(at(kBmRegDebug));
+}
 
 // Bound on |D''_f32 - 64 d2 - 1/2| (LUT cells) for a ligand atom posed by the f32 affine map and a receptor record,
 // both inside `ubound` (record units), pairs within 1100 units of 4 d2; `lig_extent` = largest |local coordinate| of

@@ -9,6 +9,15 @@
 
 #include "host/spatial_order.hpp"
 
+// The sanitizer build of the host side (`make asan`: device memory is host memory) poisons a workspace block's growth headroom,
+// so that an offset which leaves the bytes that were asked for is reported even while it stays inside the block.
+#if defined(__SANITIZE_ADDRESS__)
+#include <sanitizer/asan_interface.h>
+#else
+#define ASAN_POISON_MEMORY_REGION(addr, size) ((void)(addr), (void)(size))
+#define ASAN_UNPOISON_MEMORY_REGION(addr, size) ((void)(addr), (void)(size))
+#endif
+
 namespace ld {
 
 // ---------------------------------------------------------------------------------------
@@ -24,12 +33,16 @@ void *DeviceArena::alloc_bytes(size_t bytes) {
     return p;
 }
 void DeviceBuffer::reserve(size_t want) {
-    if (want <= bytes) return;
+    if (want <= bytes) {
+        ASAN_UNPOISON_MEMORY_REGION(ptr, want);
+        return;
+    }
     generation++;  // the old block is gone: whoever baked its address (a captured hipGraph) must notice
     release();
     size_t grow = want + want / 4 + 256;
     hip_check(hipMalloc(&ptr, grow), "hipMalloc(workspace)");
     bytes = grow;
+    ASAN_POISON_MEMORY_REGION(static_cast<char *>(ptr) + want, grow - want);
 }
 void DeviceBuffer::release() {
     if (ptr) (void)hipFree(ptr);
@@ -303,7 +316,7 @@ Scorer::Scorer(const ld_scorer_desc &desc) {
     if (method_ == LD_METHOD_DFIRE) {
         // LIGHTDOCK_DFIRE_KERNEL: "bm" (and any other value, the default): the block-major path (kernels/dfire_bm.hpp; its ANM
         // form for molecules that flex); "packed": the pose-major kernel for everything (what LIGHTDOCK_TILED_LATENCY=1, the
-        // single-swarm CLI, and the complexes build_bm declines use anyway); "allpairs": no culling (what the receptors
+        // single-swarm CLI, and the complexes BlockMajorPath::build declines use anyway); "allpairs": no culling (what the receptors
         // build_packed declines use too)
         const char *env = std::getenv("LIGHTDOCK_DFIRE_KERNEL");
         const std::string kernel = env ? env : "";
@@ -313,7 +326,20 @@ Scorer::Scorer(const ld_scorer_desc &desc) {
             build_tile_order(desc, latency);
             if (build_packed(desc)) {
                 route_ = PairRoute::packed;
-                if (kernel != "packed" && (kernel == "bm" || !latency) && build_bm(desc)) route_ = PairRoute::block_major;
+                if (kernel != "packed" && (kernel == "bm" || !latency)) {
+                    BmInputs in(desc, tiled_rec_soa_, tiled_lig_soa_, type_perm_rec_, type_perm_lig_);
+                    in.tiled_lig = tiled_lig_;
+                    in.tiled_table = tiled_table_;
+                    in.zero_bins = packed_zero_bins_;
+                    in.rec_flag_words = pair_.rec.flag_words;
+                    in.iface_d2 = pair_.iface_d2;
+                    in.use_anm = use_anm_;
+                    in.n_cus = n_cus_;
+                    in.prepare = packed_prepare_launch(nullptr, 0, nullptr, 1);
+                    in.stream = stream_;
+                    bm_ = BlockMajorPath::build(in);
+                    if (bm_) route_ = PairRoute::block_major;
+                }
             }
         }
     }
@@ -414,6 +440,21 @@ void Scorer::build_tile_order(const ld_scorer_desc &desc, bool latency) {
     }
     tiled_split_ = split;
     rec_anm_per_pose_ = use_anm_ && tiled_rec_soa_.num_anm > 0;
+}
+
+// The centre and the largest half extent of the receptor's bounding box: the f32 record frames.
+static void frame_of_receptor(const ld_molecule &rec, double centre[3], double *half) {
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    for (size_t i = 0; i < rec.n_atoms; i++)
+        for (int c = 0; c < 3; c++) {
+            lo[c] = std::min(lo[c], rec.coordinates[3 * i + c]);
+            hi[c] = std::max(hi[c], rec.coordinates[3 * i + c]);
+        }
+    *half = 0.0;
+    for (int c = 0; c < 3; c++) {
+        centre[c] = 0.5 * (lo[c] + hi[c]);
+        *half = std::max(*half, 0.5 * (hi[c] - lo[c]));
+    }
 }
 
 double dfire_f32_error_bound(double ubound, int cells_per_unit) {
@@ -670,20 +711,6 @@ std::vector<uint8_t> build_bm_lut(double eps_cells, uint32_t zero_bins) {
     return codes;
 }
 
-void Scorer::frame_of_receptor(const ld_molecule &rec, double centre[3], double *half) const {
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    for (size_t i = 0; i < rec.n_atoms; i++)
-        for (int c = 0; c < 3; c++) {
-            lo[c] = std::min(lo[c], rec.coordinates[3 * i + c]);
-            hi[c] = std::max(hi[c], rec.coordinates[3 * i + c]);
-        }
-    *half = 0.0;
-    for (int c = 0; c < 3; c++) {
-        centre[c] = 0.5 * (lo[c] + hi[c]);
-        *half = std::max(*half, 0.5 * (hi[c] - lo[c]));
-    }
-}
-
 // ---- the fixed-point scale of the block-major path, count-aware.  Table values enter the sums as rint(v * 2^(44 - e - x)),
 // 2^e >= the table's largest |value|.  What has to hold (dfire_bm.hpp): 32 pairs of a block stay below 2^50 (the markers sit at
 // bit 51) -- true for x >= 0 whatever the complex; and a (row, ligand tile) sum, which collects 64 ligand atoms x every receptor
@@ -772,7 +799,60 @@ double dfire_bm_fix_scale(double vmax, size_t reach_count, int *extra_bits_out) 
     return std::ldexp(1.0, 44 - e - x);
 }
 
-bool Scorer::build_bm(const ld_scorer_desc &desc) {
+// ---- (a) the predicate, and the host builders it needs: nothing here calls HIP ---------------------------------------
+
+// A sphere around every ligand tile (rotation invariant): centre of its box, radius to its farthest atom.
+// sphere: [tile][4] centre (local, angstrom) and radius (record units, rounded up); radius: angstrom.
+static void bm_tile_spheres(const TiledSoA &lig, std::vector<float> &sphere, std::vector<float> &radius) {
+    const uint32_t kPad = std::numeric_limits<uint32_t>::max();
+    sphere.assign((size_t)lig.n_tiles * 4, 0.f);
+    radius.clear();
+    for (int t = 0; t < lig.n_tiles; t++) {
+        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+        for (int i = t * 64; i < t * 64 + 64; i++) {
+            if (lig.htype[i] == kPad) continue;
+            const double c[3] = {lig.hx[i], lig.hy[i], lig.hz[i]};
+            for (int k = 0; k < 3; k++) {
+                lo[k] = std::min(lo[k], c[k]);
+                hi[k] = std::max(hi[k], c[k]);
+            }
+        }
+        float ctr[3];
+        for (int k = 0; k < 3; k++) ctr[k] = lo[k] <= hi[k] ? (float)(0.5 * (lo[k] + hi[k])) : 0.f;
+        double r = 0.0;
+        for (int i = t * 64; i < t * 64 + 64; i++) {
+            if (lig.htype[i] == kPad) continue;
+            const double dx = lig.hx[i] - ctr[0], dy = lig.hy[i] - ctr[1], dz = lig.hz[i] - ctr[2];
+            r = std::max(r, std::sqrt(dx * dx + dy * dy + dz * dz));
+        }
+        for (int k = 0; k < 3; k++) sphere[4 * t + k] = ctr[k];
+        sphere[4 * t + 3] = std::nextafter((float)(kBmKappa * r * 1.000001 + 1e-3), INFINITY);
+        radius.push_back((float)(r * 1.000001 + 1e-3));
+    }
+}
+
+// Poses per pass: the entry workspace is (tile pairs) x (poses of the pass) x 12 bytes (an entry's row and block mask; until
+// round 5 also 64 bytes of partial sums per entry, which now live in a per-wave scratch: the budgets kept their pass sizes).
+// 0: no pass size fits.
+static size_t bm_pass_size(size_t tile_pairs) {
+    constexpr size_t kEntryBytes = 12;
+    if (tile_pairs * kBmPassQuantum * kEntryBytes > ((size_t)2560 << 20)) return 0;   // even the smallest pass (1024 poses) would not fit 2.5 GiB: the pose-major kernels
+    size_t chunk = ((size_t)640 << 20) / (kEntryBytes * tile_pairs);   // a second such workspace exists while two passes are in flight
+    chunk = std::min<size_t>(kBmMaxPassPoses, std::max<size_t>(kBmPassQuantum, chunk / kBmPassQuantum * kBmPassQuantum));
+    if (const char *e = std::getenv("LIGHTDOCK_BM_CHUNK")) {   // tests, A/B: any pass size that the layout can hold --
+        // an entry's index (tile pair * cap + entry) travels in 32 bits (bm_block_item), and the override stays inside the 16 GiB
+        // the default's guard admits for the smallest pass
+        const long v = std::atol(e);
+        const size_t by_index = ((size_t)1 << 32) / tile_pairs - 1, by_bytes = ((size_t)2560 << 20) / (kEntryBytes * tile_pairs);
+        if (v >= 1) chunk = std::max<size_t>(1, std::min<size_t>({(size_t)v, kBmMaxPassPoses, by_index, by_bytes}));
+    }
+    if (tile_pairs * chunk >= ((size_t)1 << 32)) return 0;   // (unreachable with the 640 MiB default: 12 bytes an entry)
+    return chunk;
+}
+
+// Does the block-major path take this complex?  Every reason for declining, before anything is uploaded or launched; what the
+// decision derived on the way (frame, error bound, tile spheres, fixed-point scale, pass size) goes to `out`.
+static bool bm_accepts(const BmInputs &in, BmFrame *out) {
 #ifdef LD_DIAG_BUILD
     // (diagnostic builds only, tools/build_variant.sh -- LIGHTDOCK_BM_DIAG_IGNORE_ANM=1: timing experiments, the block-major kernels
     // on an ANM complex as if it were rigid, wrong sums.  The shipped library does not read the variable.)
@@ -781,12 +861,13 @@ bool Scorer::build_bm(const ld_scorer_desc &desc) {
 #else
     constexpr bool diag_rigid = false;
 #endif
-    const TiledSoA &rec = tiled_rec_soa_, &lig = tiled_lig_soa_;
+    const ld_scorer_desc &desc = in.desc;
+    const TiledSoA &rec = in.rec, &lig = in.lig;
     // Molecules that flex per pose (src/dfire.rs:288-320): the ANM form of the kernels, for up to kBmMaxModes modes a molecule (more:
     // the pose-major kernel -- a stated contract, tests/test_gpu_parity.py::test_which_kernel_a_flexing_complex_gets).  The
     // fixed-point scale's reach count allows for the deformation below (until round 6 a receptor of 8192 atoms or more was declined
     // instead).  LIGHTDOCK_BM_ANM=0: such complexes stay with the pose-major kernels (A/B, tests).
-    const bool anm = !diag_rigid && use_anm_ && (rec.num_anm > 0 || lig.num_anm > 0);
+    const bool anm = !diag_rigid && in.use_anm && (rec.num_anm > 0 || lig.num_anm > 0);
     if (anm) {
         const char *e = std::getenv("LIGHTDOCK_BM_ANM");
         if (e && std::atoi(e) == 0) return false;
@@ -802,8 +883,8 @@ bool Scorer::build_bm(const ld_scorer_desc &desc) {
         if (!(std::fabs(desc.potential[i]) <= kBmFixLimit)) return false;
         table_vmax = std::max(table_vmax, std::fabs(desc.potential[i]));
     }
-    double centre[3], half;
-    frame_of_receptor(desc.receptor, centre, &half);
+    double half;
+    frame_of_receptor(desc.receptor, out->centre, &half);
     // The frame holds the receptor's box + 16 A: a ligand atom outside it is beyond the cutoff of every receptor atom.
     // (flexing: a receptor atom of a pose that is not WILD moves less than kBmWildUnits)
     double ubound = 128.0;
@@ -816,8 +897,246 @@ bool Scorer::build_bm(const ld_scorer_desc &desc) {
         if (f >= 1.0 && f <= 1000.0) eps *= f;
     }
     if (!(eps < 8.0)) return false;  // a complex thousands of angstroms across: the pose-major kernels
+    out->anm = anm;
+    out->ubound = ubound;
+    out->extent = extent;
+    out->eps = eps;
+    // the fixed-point scale: 32 pairs of a block stay below 2^49, under the markers, and a (row, ligand tile) sum -- 64 ligand
+    // atoms x the receptor atoms one ligand tile can reach -- inside 63 bits (dfire_bm_fix_scale)
+    bm_tile_spheres(lig, out->tile_sphere, out->tile_radius);
+    double tile_radius = 0.0;   // angstrom: the largest ligand tile's bounding sphere
+    for (int t = 0; t < lig.n_tiles; t++) tile_radius = std::max(tile_radius, (double)out->tile_radius[t]);
+    // (flexing: in a pose that is not WILD no coordinate of an atom moves further than kBmWildUnits / kappa = 16 A, the atom no
+    // further than sqrt(3) x that = 27.7 A from its place -- the atoms of a ligand tile stay within its radius + 27.7 A of its
+    // centre, a receptor atom within the cutoff of one of them rests within another 27.7 A: the ball grows by 55.4 A; a wild
+    // pose's sums are the exact path's, pair by pair)
+    const double flex_reach = anm ? 2.0 * std::sqrt(3.0) * (double)kBmWildUnits / kBmKappa : 0.0;   // (W bounds a coordinate: sqrt(3) W the atom)
+    const size_t reach_count = dfire_bm_reach_count(desc.receptor.coordinates, desc.receptor.n_atoms, 15.0 + tile_radius + 0.01 + flex_reach);
+    out->fix_scale = dfire_bm_fix_scale(table_vmax, reach_count, nullptr);
+    if (!(out->fix_scale > 0.0)) return false;
+    out->chunk = bm_pass_size((size_t)rec.n_tiles * lig.n_tiles);
+    return out->chunk != 0;
+}
 
-    BmModel &M = bm_;
+// ---- (b) the other host builders: host vectors in, host vectors out ----------------------------------------------------
+
+// Every receptor subtile's packed operands (BmModel::rec_ops): E = (seed - |r - c|^2) - |l - c|^2 + 2 (r - c) . (l - c), dfire_bm.hip.
+// f32, operation by operation what bm_recheck computes on the device (IEEE: the same bits).
+static std::vector<float> bm_rec_ops(const std::vector<PackedRecPair> &hp, const std::vector<TiledBox> &hb) {
+    const float seed = (float)kBmCellZero + 0.5f;
+    std::vector<float> ops(hb.size() * (size_t)kBmOpsFloats, 0.f);
+    for (size_t sbt = 0; sbt < hb.size(); sbt++) {
+        const TiledBox &box = hb[sbt];
+        const float cbx = 0.5f * (box.lox + box.hix), cby = 0.5f * (box.loy + box.hiy), cbz = 0.5f * (box.loz + box.hiz);
+        float *o = &ops[sbt * kBmOpsFloats];
+        for (int q = 0; q < 4; q++) {
+            const PackedRecPair &r = hp[sbt * 4 + q];
+            const float xs[2] = {r.x0 - cbx, r.x1 - cbx}, ys[2] = {r.y0 - cby, r.y1 - cby}, zs[2] = {r.z0 - cbz, r.z1 - cbz};
+            for (int h = 0; h < 2; h++) {
+                o[2 * q + h] = std::fmaf(-xs[h], xs[h], std::fmaf(-ys[h], ys[h], std::fmaf(-zs[h], zs[h], seed)));
+                o[8 + 2 * q + h] = zs[h] * 2.f;
+                o[16 + 2 * q + h] = ys[h] * 2.f;
+                o[24 + 2 * q + h] = xs[h] * 2.f;
+            }
+        }
+        o[32] = cbx; o[33] = cby; o[34] = cbz;
+    }
+    return ops;
+}
+
+// A receptor subtile's REACH for the culling kernel's box tests, in the spare word of its box (and the largest of a tile's
+// eight in the tile's): (8 x 15 A)^2 for every subtile whose atoms can add to a sum.  A receptor type whose rows of the
+// potential are 0.0 against every ligand type of the complex -- all 20 bins and the read past the row at r = 15.0
+// (src/dfire.rs:336-338: bin 20 = the next type's bin 0) -- adds nothing at any distance: a subtile of such atoms only
+// (lightdock's membrane beads, if the DCparams at hand carries zero rows for them) is listed within the interface
+// distance alone (d <= 3.9, i.e. r <= 2.45 A, src/dfire.rs:339) when it or the ligand holds an atom with an
+// interface-flag slot, and never otherwise.  Exact: a block that is not listed holds no pair that changes the sum or a
+// flag.  Counting launches test against the full cutoff (they count pairs, not values).  VERDICT r05 item 8.
+// Returns the number of quiet subtiles.
+static uint32_t bm_box_reaches(const ld_scorer_desc &desc, const TiledSoA &rec, const TiledSoA &lig, std::vector<TiledBox> &hb, std::vector<TiledBox> &ht) {
+    std::vector<char> lig_has(169, 0), quiet_type(169, 1);
+    for (size_t i = 0; i < desc.ligand.n_atoms; i++) lig_has[desc.ligand.dfire_types[i]] = 1;
+    for (uint32_t r = 0; r < 169; r++)
+        for (uint32_t l = 0; l < 169 && quiet_type[r]; l++)
+            for (uint32_t b = 0; b <= 20 && quiet_type[r] && lig_has[l]; b++) {
+                const size_t at = (size_t)r * kDfireRowStride + (size_t)l * 20 + b;
+                if (at >= LD_DFIRE_TABLE_LEN || desc.potential[at] != 0.0) quiet_type[r] = 0;   // (past the table's end: not ours to reason about)
+            }
+    bool lig_tracked_any = false;
+    for (int32_t v : lig.hslot) lig_tracked_any = lig_tracked_any || v >= 0;
+    const float full_cut = kBmBoxCutUnits2, iface_cut = 400.0f * 1.00005f;   // (8 x 15 A)^2 and (8 x 2.5 A)^2 record units, padded like the full one
+    uint32_t quiet_subtiles = 0;
+    for (size_t t = 0; t < ht.size(); t++) {
+        float tile_cut = -1.0f;
+        for (size_t sb = 0; sb < 8; sb++) {
+            const size_t sbt = t * 8 + sb;
+            bool quiet = true, any = false, tracked = false;
+            for (size_t k = 0; k < 8; k++) {
+                const uint32_t ty = rec.htype[sbt * 8 + k];
+                if (ty == 0xffffffffu) continue;
+                any = true;
+                quiet = quiet && ty < 169 && quiet_type[ty];
+                tracked = tracked || rec.hslot[sbt * 8 + k] >= 0;
+            }
+            float cut = full_cut;
+            if (any && quiet) {
+                cut = (tracked || lig_tracked_any) ? iface_cut : -1.0f;
+                quiet_subtiles++;
+            }
+            hb[sbt].pad0 = cut;
+            hb[sbt].pad1 = 0.f;
+            tile_cut = std::max(tile_cut, cut);
+        }
+        ht[t].pad0 = tile_cut;
+        ht[t].pad1 = 0.f;
+    }
+    return quiet_subtiles;
+}
+
+// A molecule's modes as the kernels read them: kappa x, f32 (BmModel)
+struct BmModeTables {
+    std::vector<double> exact;                 // [atom][mode][x y z], the reference's numbers
+    std::vector<float> by_subtile, by_atom;    // BmModel::*_modes_f32, *_modes_atom
+    float norm_coord = 0.f, norm_atom = 0.f;   // BmModel::*_mode_norm, lig_mode_norm_vec
+};
+static BmModeTables bm_mode_tables(const TiledSoA &m) {
+    BmModeTables out;
+    const size_t pad = (size_t)m.n_tiles * 64;
+    out.exact.assign(pad * 3 * (size_t)kBmMaxModes, 0.0);
+    for (int k = 0; k < m.num_anm; k++)
+        for (size_t i = 0; i < pad; i++)
+            for (int c = 0; c < 3; c++) out.exact[(i * kBmMaxModes + (size_t)k) * 3 + c] = m.hmodes[((size_t)k * 3 + c) * pad + i];
+    out.by_subtile.assign(pad / 8 * (size_t)kBmModeFloats, 0.f);
+    out.by_atom.assign(pad * 32, 0.f);
+    // per atom: the 2-norm of the ten components of a coordinate, and of all thirty -- of the f32 values the kernels multiply with
+    std::vector<double> n2((size_t)pad * 3, 0.0);
+    for (int k = 0; k < m.num_anm; k++)
+        for (size_t i = 0; i < pad; i++)
+            for (int c = 0; c < 3; c++) {
+                const double v = m.hmodes[((size_t)k * 3 + c) * pad + i];
+                const float f = (float)(kBmKappa * v);
+                out.by_subtile[(i / 8) * (size_t)kBmModeFloats + ((((i % 8) / 2) * 3 + c) * (size_t)kBmMaxModes + k) * 2 + (i & 1)] = f;
+                out.by_atom[i * 32 + 3 * (size_t)k + c] = f;
+                n2[i * 3 + c] += (double)f * (double)f;
+            }
+    double coord = 0.0, atom = 0.0;
+    for (size_t i = 0; i < pad; i++) {
+        for (int c = 0; c < 3; c++) coord = std::max(coord, n2[i * 3 + c]);
+        atom = std::max(atom, n2[i * 3] + n2[i * 3 + 1] + n2[i * 3 + 2]);
+    }
+    // (not finite: every pose with a non-zero amplitude is wild; NaN stays NaN and fails the kernel's comparison)
+    out.norm_coord = std::nextafter((float)(std::sqrt(coord) * 1.000001), INFINITY);
+    out.norm_atom = std::nextafter((float)(std::sqrt(atom) * 1.000001), INFINITY);
+    return out;
+}
+
+// subtiles that hold an atom with an interface-flag slot (restraint atoms, membrane beads)
+static std::vector<uint8_t> bm_tracked_subtiles(const TiledSoA &m) {
+    std::vector<uint8_t> t(m.hslot.size() / 8, 0);
+    for (size_t i = 0; i < m.hslot.size(); i++)
+        if (m.hslot[i] >= 0) t[i / 8] = 1;
+    return t;
+}
+
+// per atom: where its type's rows (ligand: type_bytes = a type's block) / column (receptor: a row) sit in the row table;
+// padding atoms take the all-zero type
+static std::vector<uint32_t> bm_type_offsets(const TiledSoA &m, uint32_t type_bytes) {
+    const uint32_t kPad = std::numeric_limits<uint32_t>::max();
+    std::vector<uint32_t> off(m.htype.size());
+    for (size_t i = 0; i < off.size(); i++) off[i] = (m.htype[i] == kPad ? (uint32_t)kBmTypes - 1 : m.htype[i]) * type_bytes;
+    return off;
+}
+
+// BmModel::lig_local: x, y, z (angstrom, f32), 1.0 = real atom
+static std::vector<float> bm_lig_local(const TiledSoA &lig) {
+    const uint32_t kPad = std::numeric_limits<uint32_t>::max();
+    std::vector<float> local(lig.htype.size() * 4, 0.f);
+    for (size_t i = 0; i < lig.htype.size(); i++) {
+        if (lig.htype[i] == kPad) continue;
+        local[4 * i] = (float)lig.hx[i];
+        local[4 * i + 1] = (float)lig.hy[i];
+        local[4 * i + 2] = (float)lig.hz[i];
+        local[4 * i + 3] = 1.f;
+    }
+    return local;
+}
+
+// what the exact path reads of an atom, together: x, y, z and {table term, interface-flag slot} in the fourth double's bytes
+static std::vector<double> bm_exact_rows(const TiledSoA &m, const std::vector<uint32_t> &perm, bool is_receptor) {
+    const uint32_t kPad = std::numeric_limits<uint32_t>::max();
+    std::vector<double> rows(m.htype.size() * 4, 0.0);
+    for (size_t i = 0; i < m.htype.size(); i++) {
+        rows[4 * i] = m.hx[i];
+        rows[4 * i + 1] = m.hy[i];
+        rows[4 * i + 2] = m.hz[i];
+        const uint32_t term = m.htype[i] == kPad ? 0u : is_receptor ? tiled_rec_term(perm[m.htype[i]]) : tiled_lig_term(perm[m.htype[i]]);
+        const uint32_t words[2] = {term, (uint32_t)m.hslot[i]};
+        std::memcpy(&rows[4 * i + 3], words, 8);
+    }
+    return rows;
+}
+
+// rows[l][r][b] = potential[r * 3380 + l * 20 + b] in fixed point, b = 0..19; slot 20 = 0, slot 21: the kernel's marker;
+// ones: the same with 1 in every bin's slot
+static void bm_fixed_rows(const double *potential, double fix_scale, std::vector<long long> &rows, std::vector<long long> &ones) {
+    rows.assign((size_t)kBmTypes * kBmTypes * kBmRowSlots, 0);
+    ones.assign(rows.size(), 0);
+    for (uint32_t l = 0; l < (uint32_t)kBmTypes; l++)
+        for (uint32_t r = 0; r < (uint32_t)kBmTypes; r++) {
+            long long *row = &rows[((size_t)l * kBmTypes + r) * kBmRowSlots], *one = &ones[((size_t)l * kBmTypes + r) * kBmRowSlots];
+            if (l >= 169 || r >= 169) continue;   // the all-zero type of padding atoms
+            for (uint32_t b = 0; b <= 19; b++) {
+                row[b] = std::llrint(potential[(size_t)r * kDfireRowStride + l * 20 + b] * fix_scale);
+                one[b] = 1;
+            }
+        }
+}
+
+// ---- (c) the object: the one device round trip, then every upload --------------------------------------------------------
+
+std::unique_ptr<BlockMajorPath> BlockMajorPath::build(const BmInputs &in) {
+    BmFrame frame;
+    if (!bm_accepts(in, &frame)) return nullptr;
+    return std::unique_ptr<BlockMajorPath>(new BlockMajorPath(in, frame));
+}
+
+BlockMajorPath::BlockMajorPath(const BmInputs &in, const BmFrame &frame) {
+    const TiledSoA &rec = in.rec, &lig = in.lig;
+    const size_t pad = (size_t)rec.n_tiles * 64;
+    n_cus_ = in.n_cus;
+    chunk_ = frame.chunk;
+
+    // THE DEVICE ROUND TRIP: the receptor image in this frame (kappa = 8) by the kernel that builds the packed kernel's, read back
+    // for the operands and reaches that are formed from it on the host; the boxes return with their reach words.
+    PackedRecPair *pairs = static_cast<PackedRecPair *>(arena_.alloc_bytes(pad / 2 * sizeof(PackedRecPair)));
+    TiledBox *sub = static_cast<TiledBox *>(arena_.alloc_bytes(pad / 8 * sizeof(TiledBox)));
+    TiledBox *tile = static_cast<TiledBox *>(arena_.alloc_bytes(pad / 64 * sizeof(TiledBox)));
+    std::vector<PackedRecPair> hp(pad / 2);
+    std::vector<TiledBox> hb(pad / 8), ht(pad / 64);
+    {
+        PackedPrepareLaunch p = in.prepare;
+        p.num_anm = 0;
+        p.cx = frame.centre[0];
+        p.cy = frame.centre[1];
+        p.cz = frame.centre[2];
+        p.kappa = kBmKappa;
+        p.ubound = (float)frame.ubound;
+        p.pairs_out = pairs;
+        p.sub_out = sub;
+        p.tile_out = tile;
+        hip_check(launch_packed_prepare(p, in.stream), "launch dfire_packed_prepare");
+        hip_check(hipStreamSynchronize(in.stream), "hipStreamSynchronize");
+        hip_check(hipMemcpy(hp.data(), pairs, hp.size() * sizeof(PackedRecPair), hipMemcpyDeviceToHost), "D2H receptor records");
+        hip_check(hipMemcpy(hb.data(), sub, hb.size() * sizeof(TiledBox), hipMemcpyDeviceToHost), "D2H receptor boxes");
+        hip_check(hipMemcpy(ht.data(), tile, ht.size() * sizeof(TiledBox), hipMemcpyDeviceToHost), "D2H receptor tile boxes");
+    }
+    const std::vector<float> ops = bm_rec_ops(hp, hb);
+    quiet_subtiles_ = bm_box_reaches(in.desc, rec, lig, hb, ht);
+    hip_check(hipMemcpy(sub, hb.data(), hb.size() * sizeof(TiledBox), hipMemcpyHostToDevice), "H2D receptor boxes");
+    hip_check(hipMemcpy(tile, ht.data(), ht.size() * sizeof(TiledBox), hipMemcpyHostToDevice), "H2D receptor tile boxes");
+
+    // the model: what the scorer shares, then this path's own tables
+    BmModel &M = model_;
     M.rec_n_real = rec.n_real;
     M.rec_n_tiles = rec.n_tiles;
     M.rec_x = rec.x;
@@ -825,369 +1144,151 @@ bool Scorer::build_bm(const ld_scorer_desc &desc) {
     M.rec_z = rec.z;
     M.rec_tindex = rec.tindex;
     M.rec_slot = rec.slot;
-    M.rec_flag_words = pair_.rec.flag_words;
-    M.lig = tiled_lig_;
-    M.cx = centre[0];
-    M.cy = centre[1];
-    M.cz = centre[2];
-    M.ubound = (float)ubound;
-    M.box_pad = std::nextafter((float)(2.0 * dfire_bm_pose_error(ubound, extent, anm)), INFINITY);
-    M.table = tiled_table_;
-    M.iface_scaled = 4.0 * pair_.iface_d2;
+    M.rec_flag_words = in.rec_flag_words;
+    M.lig = in.tiled_lig;
+    M.cx = frame.centre[0];
+    M.cy = frame.centre[1];
+    M.cz = frame.centre[2];
+    M.ubound = (float)frame.ubound;
+    M.box_pad = std::nextafter((float)(2.0 * dfire_bm_pose_error(frame.ubound, frame.extent, frame.anm)), INFINITY);
+    M.table = in.tiled_table;
+    M.iface_scaled = 4.0 * in.iface_d2;
+    M.fix_scale = frame.fix_scale;
+    M.rec_pairs = pairs;
+    M.rec_sub = sub;
+    M.rec_tile = tile;
+    M.rec_ops = arena_.upload(ops);
     {
         const DfireBinning b = build_dfire_binning();
         std::vector<double> step4(b.step);
         for (double &v : step4) v *= 4.0;
         M.bin_step = arena_.upload(step4);
     }
-    M.lut = arena_.upload(build_bm_lut(eps, packed_zero_bins_));
-    M.lut_full = packed_zero_bins_ ? arena_.upload(build_bm_lut(eps, 0)) : M.lut;  // counting launches count every pair
-    {   // subtiles that hold an atom with an interface-flag slot (restraint atoms, membrane beads)
-        auto tracked = [](const TiledSoA &m) {
-            std::vector<uint8_t> t(m.hslot.size() / 8, 0);
-            for (size_t i = 0; i < m.hslot.size(); i++)
-                if (m.hslot[i] >= 0) t[i / 8] = 1;
-            return t;
-        };
-        M.rec_sub_tracked = arena_.upload(tracked(rec));
-        M.lig_sub_tracked = arena_.upload(tracked(lig));
-    }
-    {   // receptor image in this frame, by the kernel that builds the packed kernel's
-        const size_t pad = (size_t)rec.n_tiles * 64;
-        PackedRecPair *pairs = static_cast<PackedRecPair *>(arena_.alloc_bytes(pad / 2 * sizeof(PackedRecPair)));
-        TiledBox *sub = static_cast<TiledBox *>(arena_.alloc_bytes(pad / 8 * sizeof(TiledBox)));
-        TiledBox *tile = static_cast<TiledBox *>(arena_.alloc_bytes(pad / 64 * sizeof(TiledBox)));
-        PackedPrepareLaunch p = packed_prepare_launch(nullptr, 0, nullptr, 1);
-        p.num_anm = 0;
-        p.cx = centre[0];
-        p.cy = centre[1];
-        p.cz = centre[2];
-        p.kappa = kBmKappa;
-        p.ubound = (float)ubound;
-        p.pairs_out = pairs;
-        p.sub_out = sub;
-        p.tile_out = tile;
-        hip_check(launch_packed_prepare(p, stream_), "launch dfire_packed_prepare");
-        hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        M.rec_pairs = pairs;
-        M.rec_sub = sub;
-        M.rec_tile = tile;
-        {   // every receptor subtile's packed operands (BmModel::rec_ops): E = (seed - |r - c|^2) - |l - c|^2 + 2 (r - c) . (l - c), dfire_bm.hip.
-            // f32, operation by operation what bm_recheck computes on the device (IEEE: the same bits).
-            std::vector<PackedRecPair> hp(pad / 2);
-            std::vector<TiledBox> hb(pad / 8);
-            hip_check(hipMemcpy(hp.data(), pairs, hp.size() * sizeof(PackedRecPair), hipMemcpyDeviceToHost), "D2H receptor records");
-            hip_check(hipMemcpy(hb.data(), sub, hb.size() * sizeof(TiledBox), hipMemcpyDeviceToHost), "D2H receptor boxes");
-            const float seed = (float)kBmCellZero + 0.5f;
-            std::vector<float> ops((pad / 8) * (size_t)kBmOpsFloats, 0.f);
-            for (size_t sbt = 0; sbt < pad / 8; sbt++) {
-                const TiledBox &box = hb[sbt];
-                const float cbx = 0.5f * (box.lox + box.hix), cby = 0.5f * (box.loy + box.hiy), cbz = 0.5f * (box.loz + box.hiz);
-                float *o = &ops[sbt * kBmOpsFloats];
-                for (int q = 0; q < 4; q++) {
-                    const PackedRecPair &r = hp[sbt * 4 + q];
-                    const float xs[2] = {r.x0 - cbx, r.x1 - cbx}, ys[2] = {r.y0 - cby, r.y1 - cby}, zs[2] = {r.z0 - cbz, r.z1 - cbz};
-                    for (int h = 0; h < 2; h++) {
-                        o[2 * q + h] = std::fmaf(-xs[h], xs[h], std::fmaf(-ys[h], ys[h], std::fmaf(-zs[h], zs[h], seed)));
-                        o[8 + 2 * q + h] = zs[h] * 2.f;
-                        o[16 + 2 * q + h] = ys[h] * 2.f;
-                        o[24 + 2 * q + h] = xs[h] * 2.f;
-                    }
-                }
-                o[32] = cbx; o[33] = cby; o[34] = cbz;
-            }
-            M.rec_ops = arena_.upload(ops);
-            // A receptor subtile's REACH for the culling kernel's box tests, in the spare word of its box (and the largest of a tile's
-            // eight in the tile's): (8 x 15 A)^2 for every subtile whose atoms can add to a sum.  A receptor type whose rows of the
-            // potential are 0.0 against every ligand type of the complex -- all 20 bins and the read past the row at r = 15.0
-            // (src/dfire.rs:336-338: bin 20 = the next type's bin 0) -- adds nothing at any distance: a subtile of such atoms only
-            // (lightdock's membrane beads, if the DCparams at hand carries zero rows for them) is listed within the interface
-            // distance alone (d <= 3.9, i.e. r <= 2.45 A, src/dfire.rs:339) when it or the ligand holds an atom with an
-            // interface-flag slot, and never otherwise.  Exact: a block that is not listed holds no pair that changes the sum or a
-            // flag.  Counting launches test against the full cutoff (they count pairs, not values).  VERDICT r05 item 8.
-            std::vector<char> lig_has(169, 0), quiet_type(169, 1);
-            for (size_t i = 0; i < desc.ligand.n_atoms; i++) lig_has[desc.ligand.dfire_types[i]] = 1;
-            for (uint32_t r = 0; r < 169; r++)
-                for (uint32_t l = 0; l < 169 && quiet_type[r]; l++)
-                    for (uint32_t b = 0; b <= 20 && quiet_type[r] && lig_has[l]; b++) {
-                        const size_t at = (size_t)r * kDfireRowStride + (size_t)l * 20 + b;
-                        if (at >= LD_DFIRE_TABLE_LEN || desc.potential[at] != 0.0) quiet_type[r] = 0;   // (past the table's end: not ours to reason about)
-                    }
-            bool lig_tracked_any = false;
-            for (int32_t v : lig.hslot) lig_tracked_any = lig_tracked_any || v >= 0;
-            const float full_cut = kBmBoxCutUnits2, iface_cut = 400.0f * 1.00005f;   // (8 x 15 A)^2 and (8 x 2.5 A)^2 record units, padded like the full one
-            std::vector<TiledBox> ht(pad / 64);
-            hip_check(hipMemcpy(ht.data(), tile, ht.size() * sizeof(TiledBox), hipMemcpyDeviceToHost), "D2H receptor tile boxes");
-            bm_quiet_subtiles_ = 0;
-            for (size_t t = 0; t < pad / 64; t++) {
-                float tile_cut = -1.0f;
-                for (size_t sb = 0; sb < 8; sb++) {
-                    const size_t sbt = t * 8 + sb;
-                    bool quiet = true, any = false, tracked = false;
-                    for (size_t k = 0; k < 8; k++) {
-                        const uint32_t ty = rec.htype[sbt * 8 + k];
-                        if (ty == 0xffffffffu) continue;
-                        any = true;
-                        quiet = quiet && ty < 169 && quiet_type[ty];
-                        tracked = tracked || rec.hslot[sbt * 8 + k] >= 0;
-                    }
-                    float cut = full_cut;
-                    if (any && quiet) {
-                        cut = (tracked || lig_tracked_any) ? iface_cut : -1.0f;
-                        bm_quiet_subtiles_++;
-                    }
-                    hb[sbt].pad0 = cut;
-                    hb[sbt].pad1 = 0.f;
-                    tile_cut = std::max(tile_cut, cut);
-                }
-                ht[t].pad0 = tile_cut;
-                ht[t].pad1 = 0.f;
-            }
-            hip_check(hipMemcpy(sub, hb.data(), hb.size() * sizeof(TiledBox), hipMemcpyHostToDevice), "H2D receptor boxes");
-            hip_check(hipMemcpy(tile, ht.data(), ht.size() * sizeof(TiledBox), hipMemcpyHostToDevice), "H2D receptor tile boxes");
-        }
-    }
-    if (anm) {   // the modes as the kernels read them: kappa x, f32 (BmModel)
+    M.lut = arena_.upload(build_bm_lut(frame.eps, in.zero_bins));
+    M.lut_full = in.zero_bins ? arena_.upload(build_bm_lut(frame.eps, 0)) : M.lut;  // counting launches count every pair
+    M.rec_sub_tracked = arena_.upload(bm_tracked_subtiles(rec));
+    M.lig_sub_tracked = arena_.upload(bm_tracked_subtiles(lig));
+    if (frame.anm) {
         M.anm_rec = rec.num_anm;
         M.anm_lig = lig.num_anm;
-        auto tables = [&](const TiledSoA &m, std::vector<float> &by_subtile, std::vector<float> *by_atom, float *norm_coord, float *norm_atom, const double **exact) {
-            const size_t pad = (size_t)m.n_tiles * 64;
-            std::vector<double> per_atom(pad * 3 * (size_t)kBmMaxModes, 0.0);   // [atom][mode][x y z], the reference's numbers
-            for (int k = 0; k < m.num_anm; k++)
-                for (size_t i = 0; i < pad; i++)
-                    for (int c = 0; c < 3; c++) per_atom[(i * kBmMaxModes + (size_t)k) * 3 + c] = m.hmodes[((size_t)k * 3 + c) * pad + i];
-            *exact = arena_.upload(per_atom);
-            by_subtile.assign(pad / 8 * (size_t)kBmModeFloats, 0.f);
-            if (by_atom) by_atom->assign(pad * 32, 0.f);
-            // per atom: the 2-norm of the ten components of a coordinate, and of all thirty -- of the f32 values the kernels multiply with
-            std::vector<double> n2((size_t)pad * 3, 0.0);
-            for (int k = 0; k < m.num_anm; k++)
-                for (size_t i = 0; i < pad; i++)
-                    for (int c = 0; c < 3; c++) {
-                        const double v = m.hmodes[((size_t)k * 3 + c) * pad + i];
-                        const float f = (float)(kBmKappa * v);
-                        by_subtile[(i / 8) * (size_t)kBmModeFloats + ((((i % 8) / 2) * 3 + c) * (size_t)kBmMaxModes + k) * 2 + (i & 1)] = f;
-                        if (by_atom) (*by_atom)[i * 32 + 3 * (size_t)k + c] = f;
-                        n2[i * 3 + c] += (double)f * (double)f;
-                    }
-            double coord = 0.0, atom = 0.0;
-            for (size_t i = 0; i < pad; i++) {
-                for (int c = 0; c < 3; c++) coord = std::max(coord, n2[i * 3 + c]);
-                atom = std::max(atom, n2[i * 3] + n2[i * 3 + 1] + n2[i * 3 + 2]);
-            }
-            // (not finite: every pose with a non-zero amplitude is wild; NaN stays NaN and fails the kernel's comparison)
-            *norm_coord = std::nextafter((float)(std::sqrt(coord) * 1.000001), INFINITY);
-            if (norm_atom) *norm_atom = std::nextafter((float)(std::sqrt(atom) * 1.000001), INFINITY);
-        };
-        std::vector<float> rsub, lsub, latom, ratom;
-        tables(rec, rsub, &ratom, &M.rec_mode_norm, nullptr, &M.rec_modes_exact);
-        tables(lig, lsub, &latom, &M.lig_mode_norm, &M.lig_mode_norm_vec, &M.lig_modes_exact);
-        M.rec_modes_f32 = arena_.upload(rsub);
-        M.lig_modes_f32 = arena_.upload(lsub);
-        M.lig_modes_atom = arena_.upload(latom);
-        M.rec_modes_atom = arena_.upload(ratom);
+        const BmModeTables r = bm_mode_tables(rec), l = bm_mode_tables(lig);
+        M.rec_modes_exact = arena_.upload(r.exact);
+        M.lig_modes_exact = arena_.upload(l.exact);
+        M.rec_mode_norm = r.norm_coord;
+        M.lig_mode_norm = l.norm_coord;
+        M.lig_mode_norm_vec = l.norm_atom;
+        M.rec_modes_f32 = arena_.upload(r.by_subtile);
+        M.lig_modes_f32 = arena_.upload(l.by_subtile);
+        M.lig_modes_atom = arena_.upload(l.by_atom);
+        M.rec_modes_atom = arena_.upload(r.by_atom);
         // dfire_bm_rec_boxes' atoms: the static record's rounding, the ten terms and their fma roundings (partial sums inside the frame); x 2
-        M.rec_box_pad = std::nextafter((float)(2.0 * (std::ldexp(ubound, -24) + bm_flex_error(ubound * 0.999))), INFINITY);
+        M.rec_box_pad = std::nextafter((float)(2.0 * (std::ldexp(frame.ubound, -24) + bm_flex_error(frame.ubound * 0.999))), INFINITY);
     }
-    const uint32_t kPad = std::numeric_limits<uint32_t>::max();
-    {   // per atom: where its type's rows / column sit in the row table; padding atoms take the all-zero type
-        std::vector<uint32_t> rowoff(rec.htype.size()), rowbase(lig.htype.size());
-        for (size_t i = 0; i < rowoff.size(); i++) rowoff[i] = (rec.htype[i] == kPad ? (uint32_t)kBmTypes - 1 : rec.htype[i]) * (uint32_t)kBmRowBytes;
-        for (size_t i = 0; i < rowbase.size(); i++)
-            rowbase[i] = (lig.htype[i] == kPad ? (uint32_t)kBmTypes - 1 : lig.htype[i]) * (uint32_t)(kBmTypes * kBmRowBytes);
-        M.rec_rowoff = arena_.upload(rowoff);
-        M.lig_rowbase = arena_.upload(rowbase);
-        std::vector<float> local(lig.htype.size() * 4, 0.f);
-        for (size_t i = 0; i < lig.htype.size(); i++) {
-            if (lig.htype[i] == kPad) continue;
-            local[4 * i] = (float)lig.hx[i];
-            local[4 * i + 1] = (float)lig.hy[i];
-            local[4 * i + 2] = (float)lig.hz[i];
-            local[4 * i + 3] = 1.f;
-        }
-        M.lig_local = arena_.upload(local);
-        // what the exact path reads of an atom, together: x, y, z and {table term, interface-flag slot} in the fourth double's bytes
-        auto exact_rows = [&](const TiledSoA &m, bool is_receptor) {
-            const std::vector<uint32_t> &perm = is_receptor ? type_perm_rec_ : type_perm_lig_;
-            std::vector<double> rows(m.htype.size() * 4, 0.0);
-            for (size_t i = 0; i < m.htype.size(); i++) {
-                rows[4 * i] = m.hx[i];
-                rows[4 * i + 1] = m.hy[i];
-                rows[4 * i + 2] = m.hz[i];
-                const uint32_t term = m.htype[i] == kPad ? 0u : is_receptor ? tiled_rec_term(perm[m.htype[i]]) : tiled_lig_term(perm[m.htype[i]]);
-                const uint32_t words[2] = {term, (uint32_t)m.hslot[i]};
-                std::memcpy(&rows[4 * i + 3], words, 8);
-            }
-            return rows;
-        };
-        M.lig_exact = arena_.upload(exact_rows(lig, false));
-        M.rec_exact = arena_.upload(exact_rows(rec, true));
-        // a sphere around every ligand tile (rotation invariant): centre of its box, radius to its farthest atom
-        std::vector<float> sphere((size_t)lig.n_tiles * 4, 0.f);
-        bm_tile_radius_.clear();
-        for (int t = 0; t < lig.n_tiles; t++) {
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-            for (int i = t * 64; i < t * 64 + 64; i++) {
-                if (lig.htype[i] == kPad) continue;
-                const double c[3] = {lig.hx[i], lig.hy[i], lig.hz[i]};
-                for (int k = 0; k < 3; k++) {
-                    lo[k] = std::min(lo[k], c[k]);
-                    hi[k] = std::max(hi[k], c[k]);
-                }
-            }
-            float ctr[3];
-            for (int k = 0; k < 3; k++) ctr[k] = lo[k] <= hi[k] ? (float)(0.5 * (lo[k] + hi[k])) : 0.f;
-            double r = 0.0;
-            for (int i = t * 64; i < t * 64 + 64; i++) {
-                if (lig.htype[i] == kPad) continue;
-                const double dx = lig.hx[i] - ctr[0], dy = lig.hy[i] - ctr[1], dz = lig.hz[i] - ctr[2];
-                r = std::max(r, std::sqrt(dx * dx + dy * dy + dz * dz));
-            }
-            for (int k = 0; k < 3; k++) sphere[4 * t + k] = ctr[k];
-            sphere[4 * t + 3] = std::nextafter((float)(kBmKappa * r * 1.000001 + 1e-3), INFINITY);
-            bm_tile_radius_.push_back((float)(r * 1.000001 + 1e-3));
-        }
-        M.lig_tile_sphere = arena_.upload(sphere);
-    }
-    {   // rows[l][r][b] = potential[r * 3380 + l * 20 + b] in fixed point, b = 0..19; slot 20 = 0, slot 21: the kernel's marker
-        // the scale: 32 pairs of a block stay below 2^49, under the markers, and a (row, ligand tile) sum -- 64 ligand atoms x
-        // the receptor atoms one ligand tile can reach -- inside 63 bits (dfire_bm_fix_scale)
-        double tile_radius = 0.0;   // angstrom: the largest ligand tile's bounding sphere
-        for (int t = 0; t < lig.n_tiles; t++) tile_radius = std::max(tile_radius, (double)bm_tile_radius_[t]);
-        // (flexing: in a pose that is not WILD no coordinate of an atom moves further than kBmWildUnits / kappa = 16 A, the atom no
-        // further than sqrt(3) x that = 27.7 A from its place -- the atoms of a ligand tile stay within its radius + 27.7 A of its
-        // centre, a receptor atom within the cutoff of one of them rests within another 27.7 A: the ball grows by 55.4 A; a wild
-        // pose's sums are the exact path's, pair by pair)
-        const double flex_reach = anm ? 2.0 * std::sqrt(3.0) * (double)kBmWildUnits / kBmKappa : 0.0;   // (W bounds a coordinate: sqrt(3) W the atom)
-        const size_t reach_count = dfire_bm_reach_count(desc.receptor.coordinates, desc.receptor.n_atoms, 15.0 + tile_radius + 0.01 + flex_reach);
-        M.fix_scale = dfire_bm_fix_scale(table_vmax, reach_count, nullptr);
-        if (!(M.fix_scale > 0.0)) return false;
-        std::vector<long long> rows((size_t)kBmTypes * kBmTypes * kBmRowSlots, 0), ones(rows.size(), 0);
-        for (uint32_t l = 0; l < (uint32_t)kBmTypes; l++)
-            for (uint32_t r = 0; r < (uint32_t)kBmTypes; r++) {
-                long long *row = &rows[((size_t)l * kBmTypes + r) * kBmRowSlots], *one = &ones[((size_t)l * kBmTypes + r) * kBmRowSlots];
-                if (l >= 169 || r >= 169) continue;   // the all-zero type of padding atoms
-                for (uint32_t b = 0; b <= 19; b++) {
-                    row[b] = std::llrint(desc.potential[(size_t)r * kDfireRowStride + l * 20 + b] * M.fix_scale);
-                    one[b] = 1;
-                }
-            }
+    M.rec_rowoff = arena_.upload(bm_type_offsets(rec, (uint32_t)kBmRowBytes));
+    M.lig_rowbase = arena_.upload(bm_type_offsets(lig, (uint32_t)(kBmTypes * kBmRowBytes)));
+    M.lig_local = arena_.upload(bm_lig_local(lig));
+    M.lig_exact = arena_.upload(bm_exact_rows(lig, in.type_perm_lig, false));
+    M.rec_exact = arena_.upload(bm_exact_rows(rec, in.type_perm_rec, true));
+    M.lig_tile_sphere = arena_.upload(frame.tile_sphere);
+    {
+        std::vector<long long> rows, ones;
+        bm_fixed_rows(in.desc.potential, frame.fix_scale, rows, ones);
         M.rows = arena_.upload(rows);
         M.rows_ones = arena_.upload(ones);
     }
-    // poses per pass: the entry workspace is (tile pairs) x (poses of the pass) x 12 bytes (an entry's row and block mask; until
-    // round 5 also 64 bytes of partial sums per entry, which now live in a per-wave scratch: the budgets kept their pass sizes)
-    const size_t tile_pairs = (size_t)rec.n_tiles * lig.n_tiles;
-    constexpr size_t kEntryBytes = 12;
-    if (tile_pairs * kBmPassQuantum * kEntryBytes > ((size_t)2560 << 20)) return false;   // even the smallest pass (1024 poses) would not fit 2.5 GiB: the pose-major kernels
-    size_t chunk = ((size_t)640 << 20) / (kEntryBytes * tile_pairs);   // a second such workspace exists while two passes are in flight
-    chunk = std::min<size_t>(kBmMaxPassPoses, std::max<size_t>(kBmPassQuantum, chunk / kBmPassQuantum * kBmPassQuantum));
-    if (const char *e = std::getenv("LIGHTDOCK_BM_CHUNK")) {   // tests, A/B: any pass size that the layout can hold --
-        // an entry's index (tile pair * cap + entry) travels in 32 bits (bm_block_item), and the override stays inside the 16 GiB
-        // the default's guard admits for the smallest pass
-        const long v = std::atol(e);
-        const size_t by_index = ((size_t)1 << 32) / tile_pairs - 1, by_bytes = ((size_t)2560 << 20) / (kEntryBytes * tile_pairs);
-        if (v >= 1) chunk = std::max<size_t>(1, std::min<size_t>({(size_t)v, kBmMaxPassPoses, by_index, by_bytes}));
+    const char *e = std::getenv("LIGHTDOCK_BM_LANES");
+    if (!(e && std::atoi(e) == 1)) {
+        hip_check(hipStreamCreateWithFlags(&aux_stream_, hipStreamNonBlocking), "hipStreamCreate");
+        hip_check(hipEventCreateWithFlags(&fork_, hipEventDisableTiming), "hipEventCreate");
+        hip_check(hipEventCreateWithFlags(&join_, hipEventDisableTiming), "hipEventCreate");
     }
-    if (tile_pairs * chunk >= ((size_t)1 << 32)) return false;   // (unreachable with the 640 MiB default: 12 bytes an entry)
-    bm_chunk_ = chunk;
-    {
-        const char *e = std::getenv("LIGHTDOCK_BM_LANES");
-        if (!(e && std::atoi(e) == 1)) {
-            hip_check(hipStreamCreateWithFlags(&bm_aux_stream_, hipStreamNonBlocking), "hipStreamCreate");
-            hip_check(hipEventCreateWithFlags(&bm_fork_, hipEventDisableTiming), "hipEventCreate");
-            hip_check(hipEventCreateWithFlags(&bm_join_, hipEventDisableTiming), "hipEventCreate");
-        }
-    }
-    return true;
 }
 
-// Poses per block-major pass: at most bm_chunk_ (the entry workspace).  Batches that need several passes alternate them between two
+BlockMajorPath::~BlockMajorPath() {
+    if (aux_stream_) {
+        (void)hipStreamSynchronize(aux_stream_);
+        (void)hipStreamDestroy(aux_stream_);
+    }
+    if (fork_) (void)hipEventDestroy(fork_);
+    if (join_) (void)hipEventDestroy(join_);
+    // (the workspace and the model's uploads free themselves after this body, behind the synchronisation above and the scorer's own)
+}
+
+// Poses per block-major pass: at most chunk_ (the entry workspace).  Batches that need several passes alternate them between two
 // streams: the culling and gathering kernels of one pass wait on memory while the pair kernel of the other computes.
-size_t Scorer::bm_pass_poses(size_t n) const {
+size_t BlockMajorPath::pass_poses(size_t n) const {
     // (Halving a batch that fits one pass so that two passes overlap was measured and lost: 8192 poses of 1k4c as 2 x 4096 on
     // two streams 3.08 M evaluations/s against 3.43 M in one pass -- each pass pays its own tail of long jobs.)
-    return std::min(n, bm_chunk_);
+    return std::min(n, chunk_);
 }
 
 // Workspace sets of a block-major batch: one per pass in flight (two when the batch needs several passes and the second
 // stream exists).  Everything but the per-pose outputs (flags, partial sums) is indexed by the row of the pass.
-size_t Scorer::bm_sets(size_t n) const { return n > bm_pass_poses(n) && bm_aux_stream_ != nullptr ? 2 : 1; }
+size_t BlockMajorPath::sets(size_t n) const { return n > pass_poses(n) && aux_stream_ != nullptr ? 2 : 1; }
 
-void Scorer::run_bm(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, bool counts, const uint32_t *d_list,
-                    const uint32_t *d_count) {
-    const size_t n_lt = (size_t)bm_.lig.n_tiles, tile_pairs = n_lt * bm_.rec_n_tiles;
-    const size_t cap = bm_pass_poses(n);
-    const size_t parts = tile_pairs * (cap / 64 + 1);   // at most entries / 64 + tile pairs (tile pair, part) pairs
-    const size_t waves = (size_t)n_cus_ * kBmWavesPerCu;
+BmShape BlockMajorPath::shape(size_t n, bool counts, bool debug) const {
+    BmShape s;
+    s.n_rt = (size_t)model_.rec_n_tiles;
+    s.n_lt = (size_t)model_.lig.n_tiles;
+    s.cap = pass_poses(n);
+    s.sets = sets(n);   // a second set only while two passes are in flight
+    s.waves = (size_t)n_cus_ * kBmWavesPerCu;
+    s.anm = model_.anm_rec + model_.anm_lig > 0;
+    s.counts = counts;
+    s.debug = debug;
+    return s;
+}
+
+void BlockMajorPath::run(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, const uint32_t *d_list, const uint32_t *d_count,
+                         const Outputs &out, hipStream_t stream) {
+    const bool counts = out.count_partial != nullptr;
+    const char *dbg = std::getenv("LIGHTDOCK_BM_DEBUG");
+    const BmShape s = shape(n, counts, dbg != nullptr);
+    const BmLayout layout = bm_layout(s);
+    if (dbg) ws_.reserve(layout);   // (the debug words are the one region reserve() leaves out)
     BmLaunch t;
-    t.m = bm_;
+    t.m = model_;
     t.poses = d_poses;
     t.stride = stride;
     t.active = d_list ? nullptr : d_active;  // the list holds exactly the active rows
     t.pose_list = d_list;
     t.pose_count = d_list ? d_count : nullptr;
-    t.cap = cap;
+    t.cap = s.cap;
     t.pairs_groups = n_cus_;
-    t.flags = static_cast<uint32_t *>(ws_flags_.ptr);
-    t.partial = static_cast<double *>(ws_partial_.ptr);
-    if (counts) {
-        t.count_partial = static_cast<uint32_t *>(ws_counts_.ptr);
-        t.tested_partial = static_cast<uint32_t *>(ws_tested_.ptr);
-        t.exact_partial = static_cast<uint32_t *>(ws_exact_.ptr);
-    }
-    const bool anm = bm_.anm_rec + bm_.anm_lig > 0;
-    if (anm) t.part_cap = (uint32_t)kBmAnmPartEntries;
+    t.flags = out.flags;
+    t.partial = out.partial;
+    t.count_partial = out.count_partial;
+    t.tested_partial = out.tested_partial;
+    t.exact_partial = out.exact_partial;
+    if (s.anm) t.part_cap = (uint32_t)kBmAnmPartEntries;
     if (const char *e = std::getenv("LIGHTDOCK_BM_PART_CAP")) {   // A/B: jobs of fewer entries than the LDS has room for (a multiple of 64)
         const long v = std::atol(e);
-        if (v >= 64 && v % 64 == 0 && (uint32_t)v <= (anm ? (uint32_t)kBmAnmPartEntries : (uint32_t)kBmPartEntries)) t.part_cap = (uint32_t)v;
+        if (v >= 64 && v % 64 == 0 && (uint32_t)v <= (s.anm ? (uint32_t)kBmAnmPartEntries : (uint32_t)kBmPartEntries)) t.part_cap = (uint32_t)v;
     }
-    const char *dbg = std::getenv("LIGHTDOCK_BM_DEBUG");
-    if (dbg) {
-        ws_bm_debug_.reserve(waves * kBmDebugWords * sizeof(unsigned long long));
-        t.debug = static_cast<unsigned long long *>(ws_bm_debug_.ptr);
-        // (zeroed: a wave that draws no job, and the culling kernel's sampled records, leave words unwritten)
-        hip_check(hipMemsetAsync(t.debug, 0, waves * kBmDebugWords * sizeof(unsigned long long), stream_), "hipMemsetAsync debug");
+    if (dbg) {   // (zeroed: a wave that draws no job, and the culling kernel's sampled records, leave words unwritten)
+        ws_.point(t, layout, 0);
+        hip_check(hipMemsetAsync(t.debug, 0, layout.region[kBmRegDebug].bytes, stream), "hipMemsetAsync debug");
     }
-    // Passes of at most `cap` poses (poses are independent), alternating between this handle's stream and a second
+    // Passes of at most `cap` poses (poses are independent), alternating between the caller's stream and a second
     // one: fork behind what the stream holds so far, join before what follows.
-    const bool two_lanes = bm_sets(n) == 2;
+    const bool two_lanes = s.sets == 2;
     if (two_lanes) {
-        hip_check(hipEventRecord(bm_fork_, stream_), "hipEventRecord");
-        hip_check(hipStreamWaitEvent(bm_aux_stream_, bm_fork_, 0), "hipStreamWaitEvent");
+        hip_check(hipEventRecord(fork_, stream), "hipEventRecord");
+        hip_check(hipStreamWaitEvent(aux_stream_, fork_, 0), "hipStreamWaitEvent");
     }
     int lane = 0;
-    for (size_t off = 0; off < n; off += cap, lane ^= 1) {
-        hipStream_t st = lane && two_lanes ? bm_aux_stream_ : stream_;
-        const size_t w = two_lanes ? (size_t)lane : 0;   // workspace set
+    for (size_t off = 0; off < n; off += s.cap, lane ^= 1) {
+        hipStream_t st = lane && two_lanes ? aux_stream_ : stream;
         t.first = off;
-        t.n_poses = std::min(cap, n - off);
-        t.rt = static_cast<float *>(ws_bm_rt_.ptr) + w * cap * 12;
-        t.rt_exact = reinterpret_cast<double *>(static_cast<float *>(ws_bm_rt_.ptr) + bm_sets(n) * cap * 12) + w * cap * 8;
-        t.tp_count = static_cast<uint32_t *>(ws_bm_tp_count_.ptr) + w * (tile_pairs + kBmCounters + kBmCullQueueWords);
-        t.job_count = t.tp_count + tile_pairs;
-        t.job_next = t.tp_count + tile_pairs + 1;
-        t.jobs = static_cast<uint32_t *>(ws_bm_jobs_.ptr) + w * parts * 2;
-        t.job_cost = static_cast<uint32_t *>(ws_bm_job_cost_.ptr) + w * parts * kBmJobRows;
-        t.job_order = static_cast<uint32_t *>(ws_bm_job_order_.ptr) + w * parts * kBmJobRows;
-        t.job_rec = static_cast<uint32_t *>(ws_bm_job_order_.ptr) + bm_sets(n) * parts * kBmJobRows + w * parts * kBmJobRows * 4;
-        t.queue = static_cast<unsigned long long *>(ws_bm_queue_.ptr) + w * waves * kBmQueueCap;
-        t.ent_row = static_cast<uint32_t *>(ws_bm_ent_row_.ptr) + w * tile_pairs * cap;
-        t.ent_mask = static_cast<unsigned long long *>(ws_bm_ent_mask_.ptr) + w * tile_pairs * cap;
-        t.ent_partial = static_cast<long long *>(ws_bm_ent_partial_.ptr) + w * waves * kBmPartEntries;
-        t.tile_sum = static_cast<long long *>(ws_bm_tile_sum_.ptr) + w * cap * n_lt;
-        t.exact_fix = static_cast<long long *>(ws_bm_exact_fix_.ptr) + w * cap;
-        t.amp = anm ? static_cast<float *>(ws_bm_amp_.ptr) + w * cap * kBmAmpFloats : nullptr;
-        // the flexed receptor's boxes of the pass's rows: subtile boxes of every set, then the tile boxes
-        t.anm_sub = anm ? static_cast<TiledBox *>(ws_rec_sub_.ptr) + w * cap * (size_t)bm_.rec_n_tiles * 8 : nullptr;
-        t.anm_tile = anm ? static_cast<TiledBox *>(ws_rec_tile_.ptr) + w * cap * (size_t)bm_.rec_n_tiles : nullptr;
-        t.amp_exact = anm ? reinterpret_cast<double *>(static_cast<float *>(ws_bm_amp_.ptr) + bm_sets(n) * cap * kBmAmpFloats) + w * cap * 2 * kBmMaxModes : nullptr;
+        t.n_poses = std::min(s.cap, n - off);
+        ws_.point(t, layout, two_lanes ? (size_t)lane : 0);
+        uint32_t *const tile_tested = t.tile_tested, *const exact_pairs = t.exact_pairs;
         // With pair counts wanted the sequence runs twice: first as a counting launch (the same kernels over rows of ones and the
         // full LUT: the sums are the in-cutoff pair counts), then for the energies.
         for (int mode = counts ? 1 : 0; mode >= 0; mode--) {
             t.count_mode = mode;
-            t.tile_tested = mode ? static_cast<uint32_t *>(ws_bm_tile_tested_.ptr) + w * cap * n_lt : nullptr;
-            t.exact_pairs = mode ? static_cast<uint32_t *>(ws_bm_exact_pairs_.ptr) + w * cap : nullptr;
+            t.tile_tested = mode ? tile_tested : nullptr;
+            t.exact_pairs = mode ? exact_pairs : nullptr;
             // (dfire_bm_pose zeroes the sequence's counters: tp_count and the words behind it)
             hip_check(launch_bm_pose(t, st), "launch dfire_bm_pose");
             hip_check(launch_bm_cull(t, st), "launch dfire_bm_cull");
@@ -1196,12 +1297,12 @@ void Scorer::run_bm(size_t n, const double *d_poses, size_t stride, const uint8_
         }
     }
     if (two_lanes) {
-        hip_check(hipEventRecord(bm_join_, bm_aux_stream_), "hipEventRecord");
-        hip_check(hipStreamWaitEvent(stream_, bm_join_, 0), "hipStreamWaitEvent");
+        hip_check(hipEventRecord(join_, aux_stream_), "hipEventRecord");
+        hip_check(hipStreamWaitEvent(stream, join_, 0), "hipStreamWaitEvent");
     }
     if (dbg) {   // diagnostics: wave lifetimes of the last pass, one text line per wave
-        hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        std::vector<unsigned long long> h(waves * kBmDebugWords);
+        hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+        std::vector<unsigned long long> h(s.waves * kBmDebugWords);
         hip_check(hipMemcpy(h.data(), t.debug, h.size() * 8, hipMemcpyDeviceToHost), "D2H debug");
         if (FILE *f = std::fopen(dbg, "w")) {
             for (size_t i = 0; i < h.size(); i += kBmDebugWords)
@@ -1239,28 +1340,19 @@ Scorer::~Scorer() {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);
     }
-    if (bm_aux_stream_) {
-        (void)hipStreamSynchronize(bm_aux_stream_);
-        (void)hipStreamDestroy(bm_aux_stream_);
-        (void)hipEventDestroy(bm_fork_);
-        (void)hipEventDestroy(bm_join_);
-    }
     if (own_stream_) {
         (void)hipStreamSynchronize(own_stream_);
         (void)hipStreamDestroy(own_stream_);
     }
-    // (the workspace buffers free themselves after this body, behind the synchronisations above)
+    // (the workspace buffers and the block-major path free themselves after this body, behind the synchronisation above)
 }
 
 uint64_t Scorer::workspace_generation() const {
     uint64_t g = 0;
     // every buffer a launch of energy_batch_device can touch (ws_poses_ / ws_energies_ serve energy_batch_host only)
-    for (const DeviceBuffer *b : {&ws_partial_, &ws_flags_, &ws_counts_, &ws_tested_, &ws_exact_, &ws_rec_sub_, &ws_rec_tile_, &ws_rec_pairs_,
-                                  &ws_bm_debug_, &ws_bm_rt_, &ws_bm_tp_count_, &ws_bm_ent_row_, &ws_bm_jobs_, &ws_bm_job_cost_, &ws_bm_job_order_,
-                                  &ws_bm_ent_mask_, &ws_bm_queue_, &ws_bm_ent_partial_, &ws_bm_tile_sum_, &ws_bm_tile_tested_, &ws_bm_exact_fix_,
-                                  &ws_bm_exact_pairs_, &ws_bm_amp_})
+    for (const DeviceBuffer *b : {&ws_partial_, &ws_flags_, &ws_counts_, &ws_tested_, &ws_exact_, &ws_rec_sub_, &ws_rec_tile_, &ws_rec_pairs_})
         g += b->generation;
-    return g;
+    return g + (bm_ ? bm_->generation() : 0);
 }
 
 void Scorer::reserve_workspace(size_t n_poses, bool counts) {
@@ -1273,32 +1365,7 @@ void Scorer::reserve_workspace(size_t n_poses, bool counts) {
         ws_tested_.reserve(n_poses * chunks * sizeof(uint32_t));
         ws_exact_.reserve(n_poses * chunks * sizeof(uint32_t));
     }
-    if (route_ == PairRoute::block_major) {
-        const size_t n_lt = (size_t)bm_.lig.n_tiles, n_rt = (size_t)bm_.rec_n_tiles, tile_pairs = n_lt * n_rt;
-        const size_t cap = bm_pass_poses(n_poses), sets = bm_sets(n_poses);   // a second set only while two passes are in flight
-        const size_t parts = tile_pairs * (cap / 64 + 1), waves = (size_t)n_cus_ * kBmWavesPerCu;
-        ws_bm_rt_.reserve(sets * cap * (12 * sizeof(float) + 8 * sizeof(double)));   // the f32 maps of every set, then the exact path's rows
-        ws_bm_tp_count_.reserve(sets * (tile_pairs + kBmCounters + kBmCullQueueWords) * sizeof(uint32_t));   // + the launch's counters
-        ws_bm_jobs_.reserve(sets * parts * 2 * sizeof(uint32_t));
-        ws_bm_job_cost_.reserve(sets * parts * kBmJobRows * sizeof(uint32_t));
-        ws_bm_job_order_.reserve(sets * parts * kBmJobRows * (1 + 4) * sizeof(uint32_t) + 16);   // the order, then the jobs' 16-byte records
-        ws_bm_queue_.reserve(sets * waves * kBmQueueCap * sizeof(unsigned long long));
-        // (+ one part: a job of dfire_bm_pairs loads its part's 1024 entries without looking at the part's end; what lies beyond is never used)
-        ws_bm_ent_row_.reserve((sets * tile_pairs * cap + kBmPartEntries) * sizeof(uint32_t));
-        ws_bm_ent_mask_.reserve((sets * tile_pairs * cap + kBmPartEntries) * sizeof(unsigned long long));
-        ws_bm_ent_partial_.reserve(sets * waves * kBmPartEntries * sizeof(long long));   // per wave of dfire_bm_pairs: the partial sums of its current job (8 KB, L2 resident)
-        ws_bm_tile_sum_.reserve(sets * cap * n_lt * sizeof(long long));
-        ws_bm_exact_fix_.reserve(sets * cap * sizeof(long long));
-        if (bm_.anm_rec + bm_.anm_lig > 0) {   // the poses' amplitudes by row, and the receptor's boxes by pose
-            ws_bm_amp_.reserve(sets * cap * (kBmAmpFloats * sizeof(float) + 2 * kBmMaxModes * sizeof(double)));   // every set's f32 rows, then the f64 ones
-            ws_rec_sub_.reserve(sets * cap * n_rt * 8 * sizeof(TiledBox));
-            ws_rec_tile_.reserve(sets * cap * n_rt * sizeof(TiledBox));
-        }
-        if (counts) {
-            ws_bm_tile_tested_.reserve(sets * cap * n_lt * sizeof(uint32_t));
-            ws_bm_exact_pairs_.reserve(sets * cap * sizeof(uint32_t));
-        }
-    }
+    if (bm_) bm_->reserve(n_poses, counts);
 }
 
 void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active,
@@ -1360,10 +1427,19 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
         hip_check(hipEventRecord(events_[events_used_].first, stream_), "hipEventRecord");
     }
     switch (route_) {
-    case PairRoute::block_major:
+    case PairRoute::block_major: {
         p.n_chunks = 1;  // dfire_bm_gather leaves one partial per pose
-        run_bm(n, d_poses, stride, d_active, d_pair_counts != nullptr, d_list, d_count);
+        BlockMajorPath::Outputs out;
+        out.flags = p.flags;
+        out.partial = p.partial;
+        if (d_pair_counts) {
+            out.count_partial = p.count_partial;
+            out.tested_partial = static_cast<uint32_t *>(ws_tested_.ptr);
+            out.exact_partial = static_cast<uint32_t *>(ws_exact_.ptr);
+        }
+        bm_->run(n, d_poses, stride, d_active, d_list, d_count, out, stream_);
         break;
+    }
     case PairRoute::packed: {
         PackedLaunch t = packed_;
         t.poses = d_poses;

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -73,6 +74,106 @@ size_t dfire_bm_reach_count(const double *xyz, size_t n, double reach);   // upp
 double dfire_bm_fix_scale(double vmax, size_t reach_count, int *extra_bits_out);   // the block-major path's fixed-point units per unit of the potential; 0.0: none fits
 std::vector<uint8_t> build_bm_lut(double eps_cells, uint32_t zero_bins = 0);  // kBmLutBytes codes of the block-major kernel (kernels/dfire_bm.hpp)
 
+struct TiledSoA {  // a molecule in tile order, SoA, padded to whole tiles
+    int n_real = 0, n_tiles = 0;
+    const double *x = nullptr, *y = nullptr, *z = nullptr;
+    const uint32_t *tindex = nullptr;
+    const int32_t *slot = nullptr;
+    int num_anm = 0;
+    const double *modes = nullptr;
+    std::vector<double> hx, hy, hz;   // host copies, tile order (padding included)
+    std::vector<uint32_t> htype;      // DFIRE type per slot of the tile order, 0xffffffff = padding
+    std::vector<int32_t> hslot;       // interface-flag slot or -1
+    std::vector<double> hmodes;       // host copy of `modes`: [mode][xyz][padded atoms]
+};
+
+// ---------------------------------------------------------------------------------------
+// The block-major DFIRE route (kernels/dfire_bm.hpp) as one object
+// ---------------------------------------------------------------------------------------
+// The device buffers of kernels/dfire_bm.hpp's bm_layout(), grow-only.
+struct BmWorkspace {
+    DeviceBuffer buffer[kBmBuffers];
+    void reserve(const BmLayout &layout) {
+        for (int b = 0; b < kBmBuffers; b++) buffer[b].reserve(layout.buffer_bytes[b]);
+    }
+    uint64_t generation() const {
+        uint64_t g = 0;
+        for (const DeviceBuffer &b : buffer) g += b.generation;
+        return g;
+    }
+    void point(BmLaunch &t, const BmLayout &layout, size_t set) const {
+        void *ptrs[kBmBuffers];
+        for (int b = 0; b < kBmBuffers; b++) ptrs[b] = buffer[b].ptr;
+        bm_point_launch(t, layout, ptrs, set);
+    }
+};
+
+// What the block-major path takes from the scorer that builds it: the complex, both molecules in tile order (already
+// uploaded), the tables the culled routes share, and the stream of the one launch its construction needs.
+struct BmInputs {
+    const ld_scorer_desc &desc;
+    const TiledSoA &rec, &lig;
+    const std::vector<uint32_t> &type_perm_rec, &type_perm_lig;
+    BmInputs(const ld_scorer_desc &d, const TiledSoA &r, const TiledSoA &l, const std::vector<uint32_t> &pr, const std::vector<uint32_t> &pl)
+        : desc(d), rec(r), lig(l), type_perm_rec(pr), type_perm_lig(pl) {}
+    TiledLigand tiled_lig;
+    const double *tiled_table = nullptr;
+    uint32_t zero_bins = 0;      // bins in which this complex's potential is zero throughout (build_packed)
+    int rec_flag_words = 0;
+    double iface_d2 = 0.0;
+    bool use_anm = false;
+    int n_cus = 256;
+    PackedPrepareLaunch prepare;   // dfire_packed_prepare's receptor arguments (frame and outputs: the path's own)
+    hipStream_t stream = nullptr;
+};
+
+// What bm_accepts() derives of a complex the path takes (host arithmetic only).
+struct BmFrame {
+    bool anm = false;
+    double centre[3] = {0, 0, 0}, ubound = 0.0, extent = 0.0, eps = 0.0;   // the record frame; the LUT's error bound (cells)
+    std::vector<float> tile_sphere, tile_radius;   // the ligand tiles' bounding spheres: [tile][4] as the culling kernel reads them; radii in angstrom (the reach of the fixed-point scale)
+    double fix_scale = 0.0;
+    size_t chunk = 0;                              // poses per pass
+};
+
+class BlockMajorPath {
+   public:
+    // nullptr: declined -- the complex stays with the pose-major kernels, and nothing was uploaded or launched for this path
+    static std::unique_ptr<BlockMajorPath> build(const BmInputs &in);
+    ~BlockMajorPath();
+    BlockMajorPath(const BlockMajorPath &) = delete;
+    BlockMajorPath &operator=(const BlockMajorPath &) = delete;
+
+    // the workspace of a batch of n poses (no allocation in a following run() of that size)
+    void reserve(size_t n, bool counts) { ws_.reserve(bm_layout(shape(n, counts, false))); }
+    // One batch: passes of at most pass_poses(n) poses, each dfire_bm_pose .. dfire_bm_gather, on `stream` (and, two passes in
+    // flight, the path's second stream, joined before returning).  Leaves one partial per pose in `partial`.
+    struct Outputs {   // the per-pose buffers every route shares (the scorer's)
+        uint32_t *flags = nullptr;
+        double *partial = nullptr;
+        uint32_t *count_partial = nullptr, *tested_partial = nullptr, *exact_partial = nullptr;   // counting launches only
+    };
+    void run(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, const uint32_t *d_list, const uint32_t *d_count,
+             const Outputs &out, hipStream_t stream);
+    uint64_t generation() const { return ws_.generation(); }
+    uint32_t quiet_subtiles() const { return quiet_subtiles_; }
+
+   private:
+    BlockMajorPath(const BmInputs &in, const BmFrame &frame);
+    size_t pass_poses(size_t n) const;   // poses per pass of a batch of n
+    size_t sets(size_t n) const;         // workspace sets a batch of n poses needs (2 while two passes are in flight)
+    BmShape shape(size_t n, bool counts, bool debug) const;
+
+    DeviceArena arena_;                   // the model's uploads
+    BmModel model_;
+    size_t chunk_ = 0;                    // poses per pass (bounds the entry workspace)
+    uint32_t quiet_subtiles_ = 0;         // receptor subtiles whose atoms' rows of the potential are zero
+    int n_cus_ = 256;
+    hipStream_t aux_stream_ = nullptr;    // the second of two passes in flight runs here
+    hipEvent_t fork_ = nullptr, join_ = nullptr;
+    BmWorkspace ws_;
+};
+
 class Scorer {
    public:
     explicit Scorer(const ld_scorer_desc &desc);
@@ -109,7 +210,7 @@ class Scorer {
     void kernel_info(ld_kernel_info *out) const;
     // diagnostics of the last counting launch: 8x8 atom-pair blocks evaluated per pose (culled DFIRE kernels)
     void last_block_counts(size_t n, uint32_t *out_host);
-    uint32_t bm_quiet_subtiles() const { return route_ == PairRoute::block_major ? bm_quiet_subtiles_ : 0u; }
+    uint32_t bm_quiet_subtiles() const { return bm_ ? bm_->quiet_subtiles() : 0u; }
     void enable_timing(bool on);
     void pair_kernel_time(double *total_ms, uint64_t *launches);
 
@@ -120,22 +221,6 @@ class Scorer {
     void reserve_workspace(size_t n_poses, bool counts);
     void build_tile_order(const ld_scorer_desc &desc, bool latency);  // what the culled paths share: tile order, patch table, ligand view, split
     bool build_packed(const ld_scorer_desc &desc);  // after build_tile_order; false: declined (the receptor is too long for the f32 frame)
-    bool build_bm(const ld_scorer_desc &desc);      // after build_packed: the block-major path (rigid molecules; the ANM form for molecules that flex)
-    void run_bm(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, bool counts, const uint32_t *d_list,
-                const uint32_t *d_count);
-    void frame_of_receptor(const ld_molecule &rec, double centre[3], double *half) const;
-    struct TiledSoA {  // a molecule in tile order, SoA, padded to whole tiles
-        int n_real = 0, n_tiles = 0;
-        const double *x = nullptr, *y = nullptr, *z = nullptr;
-        const uint32_t *tindex = nullptr;
-        const int32_t *slot = nullptr;
-        int num_anm = 0;
-        const double *modes = nullptr;
-        std::vector<double> hx, hy, hz;   // host copies, tile order (padding included)
-        std::vector<uint32_t> htype;      // DFIRE type per slot of the tile order, 0xffffffff = padding
-        std::vector<int32_t> hslot;       // interface-flag slot or -1
-        std::vector<double> hmodes;       // host copy of `modes`: [mode][xyz][padded atoms]
-    };
     void upload_tiled_molecule(const ld_molecule &m, bool is_receptor, TiledSoA &out);
     PackedPrepareLaunch packed_prepare_launch(const double *poses, size_t stride, const uint8_t *active, size_t n) const;
 
@@ -158,19 +243,10 @@ class Scorer {
     PackedLaunch packed_;
     const uint32_t *packed_lut_full_ = nullptr;  // the LUT without elided zero bins (counting launches)
     uint32_t packed_zero_bins_ = 0;
-    uint32_t bm_quiet_subtiles_ = 0;   // receptor subtiles of the block-major path whose atoms' rows of the potential are zero (build_bm)
     DeviceBuffer ws_rec_pairs_, ws_exact_;
-    BmModel bm_;
+    std::unique_ptr<BlockMajorPath> bm_;    // set: route_ == block_major (after build_packed; rigid molecules, and the ANM form for molecules that flex)
     TiledSoA tiled_lig_soa_;
-    size_t bm_chunk_ = 0;      // poses per block-major pass (bounds the entry workspace)
-    std::vector<float> bm_tile_radius_;   // angstrom: the ligand tiles' bounding spheres (the reach of the count-aware fixed-point scale)
-    size_t bm_pass_poses(size_t n) const;
-    size_t bm_sets(size_t n) const;            // workspace sets a batch of n poses needs (2 while two passes are in flight)
-    hipStream_t bm_aux_stream_ = nullptr;   // the second of two passes in flight runs here
-    hipEvent_t bm_fork_ = nullptr, bm_join_ = nullptr;
     int n_cus_ = 256;
-    DeviceBuffer ws_bm_debug_, ws_bm_jobs_, ws_bm_job_cost_, ws_bm_job_order_, ws_bm_rt_, ws_bm_tp_count_, ws_bm_ent_row_, ws_bm_ent_mask_, ws_bm_queue_, ws_bm_ent_partial_, ws_bm_tile_sum_,
-        ws_bm_tile_tested_, ws_bm_exact_fix_, ws_bm_exact_pairs_, ws_bm_amp_;
     TiledSoA tiled_rec_soa_;          // receptor in tile order (input of dfire_packed_prepare)
     bool rec_anm_per_pose_ = false;   // receptor ANM: one receptor image per pose per launch
     DeviceBuffer ws_rec_sub_, ws_rec_tile_;

@@ -27,7 +27,9 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_t *p, int) {
     std::strcpy(p->gcnArchName, "gfx950:sramecc+:xnack-");
     return hipSuccess;
 }
-hipError_t hipMalloc(void **p, size_t n) { *p = std::malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+static size_t device_allocations = 0;
+size_t ld_stub_device_allocations(void) { return device_allocations; }   // host_check: what a scorer's construction allocated
+hipError_t hipMalloc(void **p, size_t n) { device_allocations++; *p = std::malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void *p) { std::free(p); return hipSuccess; }
 hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { std::memcpy(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t) { std::memcpy(d, s, n); return hipSuccess; }
@@ -73,33 +75,72 @@ hipError_t launch_dfire_packed(const PackedLaunch &t, hipStream_t) {
     return hipSuccess;
 }
 size_t bm_pairs_lds_bytes() { return 0; }
+// The block-major launches write the first and the last element of EVERY workspace region of the launch's set, indexed from the
+// BmLaunch fields the way the kernels index them (kernels/dfire_bm.hpp: the comments of BmLaunch) -- not through bm_layout(), so
+// that ASan checks the layout's offsets and sizes independently.  Rows of the pass run to t.cap, the room a set has.
+template <typename T>
+static void touch(T *base, size_t count) {
+    if (!count) return;
+    base[0] = T();
+    base[count - 1] = T();
+}
 hipError_t launch_bm_pose(const BmLaunch &t, hipStream_t) {
-    if (t.n_poses && t.rt) t.rt[12 * t.n_poses - 1] = 0.f;   // last slot of the pass's affine maps (the workspace of a pass goes by row)
-    if (t.n_poses && t.rt_exact) t.rt_exact[8 * t.n_poses - 1] = 0.0;
+    if (!t.n_poses) return hipSuccess;
+    const size_t tile_pairs = (size_t)t.m.lig.n_tiles * t.m.rec_n_tiles;
+    const size_t flag_words = (size_t)(t.m.rec_flag_words + t.m.lig.flag_words);
+    touch(t.rt, 12 * t.cap);
+    touch(t.rt_exact, 8 * t.cap);
+    touch(t.tp_count, tile_pairs + kBmCounters + kBmCullQueueWords);   // the sequence's counters lie behind the tile pairs' counts
+    touch(t.tile_sum, t.cap * (size_t)t.m.lig.n_tiles);
+    touch(t.exact_fix, t.cap);
+    if (flag_words) touch(t.flags + t.first * flag_words, t.n_poses * flag_words);
+    if (t.m.anm_rec + t.m.anm_lig > 0) {
+        touch(t.amp, t.cap * kBmAmpFloats);
+        touch(t.amp_exact, t.cap * 2 * kBmMaxModes);
+        touch(t.anm_sub, t.cap * (size_t)t.m.rec_n_tiles * 8);   // dfire_bm_rec_boxes
+        touch(t.anm_tile, t.cap * (size_t)t.m.rec_n_tiles);
+    }
+    if (t.count_mode) {
+        touch(t.tile_tested, t.cap * (size_t)t.m.lig.n_tiles);
+        touch(t.exact_pairs, t.cap);
+    }
     return hipSuccess;
 }
 hipError_t launch_bm_cull(const BmLaunch &t, hipStream_t) {
+    if (!t.n_poses) return hipSuccess;
     const size_t tile_pairs = (size_t)t.m.lig.n_tiles * t.m.rec_n_tiles;
-    if (t.n_poses) {
-        t.ent_row[tile_pairs * t.cap - 1] = 0;
-        t.ent_mask[tile_pairs * t.cap - 1] = 0;
-        t.tile_sum[t.n_poses * (size_t)t.m.lig.n_tiles - 1] = 0;
-        t.exact_fix[t.n_poses - 1] = 0;
-    }
+    touch(t.ent_row, tile_pairs * t.cap);
+    touch(t.ent_mask, tile_pairs * t.cap);
+    touch(t.job_count, (size_t)kBmCounters + kBmCullQueueWords);   // the culling kernel's item counters: job_count + kBmCounters + queue
+    if (t.job_next != t.job_count + 1) return hipErrorInvalidValue;
     return hipSuccess;
 }
 hipError_t launch_bm_pairs(const BmLaunch &t, hipStream_t) {
+    if (!t.n_poses) return hipSuccess;
     const size_t tile_pairs = (size_t)t.m.lig.n_tiles * t.m.rec_n_tiles;
-    if (t.n_poses) {
-        t.ent_partial[tile_pairs * kBmJobRows * t.cap - 1] = 0;
-        t.queue[(size_t)t.pairs_groups * kBmWavesPerCu * kBmQueueCap - 1] = 0ull;
-        t.job_order[tile_pairs * (t.cap / 64 + 1) * kBmJobRows - 1] = 0u;
-    }
+    const size_t parts = tile_pairs * (t.cap / 64 + 1), waves = (size_t)t.pairs_groups * kBmWavesPerCu;
+    touch(t.jobs, parts * 2);                     // dfire_bm_plan
+    touch(t.job_cost, parts * kBmJobRows);        // dfire_bm_census
+    touch(t.job_rec, parts * kBmJobRows * 4);
+    touch(t.job_order, parts * kBmJobRows);       // dfire_bm_order
+    touch(t.job_next, 1);
+    touch(t.ent_partial, waves * kBmPartEntries);   // [wave][kBmPartEntries]
+    touch(t.queue, waves * kBmQueueCap);
+    // a job loads its part's entries without looking at the part's end: a read of up to one part behind the last tile pair's list
+    volatile uint32_t row = t.ent_row[tile_pairs * t.cap + kBmPartEntries - 1];
+    volatile unsigned long long mask = t.ent_mask[tile_pairs * t.cap + kBmPartEntries - 1];
+    (void)row;
+    (void)mask;
+    if (t.debug) touch(t.debug, waves * kBmDebugWords);
     return hipSuccess;
 }
 hipError_t launch_bm_gather(const BmLaunch &t, hipStream_t) {
-    if (t.n_poses && !t.count_mode) t.partial[2 * (t.first + t.n_poses) - 1] = 0.0;
-    if (t.n_poses && t.count_mode) t.count_partial[t.first + t.n_poses - 1] = 0u;
+    if (t.n_poses && !t.count_mode) touch(t.partial + 2 * t.first, 2 * t.n_poses);
+    if (t.n_poses && t.count_mode) {
+        touch(t.count_partial + t.first, t.n_poses);
+        touch(t.tested_partial + t.first, t.n_poses);
+        touch(t.exact_partial + t.first, t.n_poses);
+    }
     return hipSuccess;
 }
 hipError_t launch_packed_prepare(const PackedPrepareLaunch &p, hipStream_t) {

@@ -22,6 +22,23 @@ static int failures = 0;
         }                                                                        \
     } while (0)
 
+extern "C" size_t ld_stub_device_allocations(void);   // tests/asan/hip_stub.cpp
+
+// A DFIRE scorer through every form of a block-major batch: plain, counting (the sequence runs twice), the single-pose call.
+// Device memory is host memory in this build, so the device-pointer call takes host vectors.
+static void bm_batches(ld_scorer *s, size_t n, const char *want_kernel) {
+    const size_t len = ld_scorer_pose_len(s);
+    std::vector<double> poses(len * n, 0.0), e(n);
+    for (size_t i = 0; i < n; i++) poses[len * i + 3] = 1.0;
+    std::vector<uint32_t> counts(n), blocks(n);
+    ld_kernel_info info;
+    CHECK(ld_scorer_kernel_info(s, &info) == LD_OK && std::strcmp(info.pair_kernel_name, want_kernel) == 0);
+    CHECK(ld_scorer_energy_batch(s, n, poses.data(), len, e.data()) == LD_OK);
+    CHECK(ld_scorer_energy_batch_device(s, n, poses.data(), len, nullptr, e.data(), counts.data()) == LD_OK);
+    CHECK(ld_scorer_last_block_counts(s, n, blocks.data()) == LD_OK);
+    CHECK(ld_scorer_energy_batch(s, 1, poses.data(), len, e.data()) == LD_OK);   // a smaller batch after a larger one
+}
+
 static int cli(std::vector<std::string> args) {
     std::vector<char *> argv;
     for (auto &a : args) argv.push_back(&a[0]);
@@ -112,6 +129,7 @@ int main(int argc, char **argv) {
         CHECK(ld_scorer_energy(s, t0, q0, nullptr, nullptr, &one) == LD_OK);
         ld_kernel_info info;
         CHECK(ld_scorer_kernel_info(s, &info) == LD_OK);
+        bm_batches(s, 300, "dfire_bm_pairs");
         std::vector<double> swarms(7 * 2 * 50, 0.0);
         for (int i = 0; i < 100; i++) swarms[7 * i + 3] = 1.0;
         ld_gso *g = ld_gso_create(s, 2, 50, swarms.data(), nullptr);
@@ -137,6 +155,65 @@ int main(int argc, char **argv) {
         }
         CHECK(ld_gso_create(s, 0, 50, swarms.data(), nullptr) == nullptr);
         ld_scorer_destroy(s);
+    }
+    // ---- the block-major path's object (scorer.hpp, BlockMajorPath): construction, reserve, run, destruction ----------------
+    auto dfire = [&](const double *rec_nm, const double *lig_nm, size_t num_anm, const double *potential) {
+        return ld_scorer_create_from_pdb(LD_METHOD_DFIRE, rec1.c_str(), lig1.c_str(), active, 1, nullptr, 0, rec_nm, rec_nm ? 1615 * 3 * num_anm : 0,
+                                         num_anm, nullptr, 0, nullptr, 0, lig_nm, lig_nm ? 221 * 3 * num_anm : 0, num_anm, rec_nm ? 1 : 0, potential);
+    };
+    // a batch larger than a forced small pass: two workspace sets on two streams, then (LIGHTDOCK_BM_LANES=1) one set, pass after pass;
+    // 300 poses = 18 passes of 16 and one of 12
+    setenv("LIGHTDOCK_BM_CHUNK", "16", 1);
+    for (int lanes = 2; lanes >= 1; lanes--) {
+        if (lanes == 1) setenv("LIGHTDOCK_BM_LANES", "1", 1);
+        ld_scorer *c = dfire(nullptr, nullptr, 0, table.data());
+        CHECK(c != nullptr);
+        if (!c) continue;
+        bm_batches(c, 300, "dfire_bm_pairs");
+        if (lanes == 2) {   // the per-wave debug words (read per call)
+            const std::string dbg = scratch + "/bm_debug.txt";
+            setenv("LIGHTDOCK_BM_DEBUG", dbg.c_str(), 1);
+            bm_batches(c, 40, "dfire_bm_pairs");
+            unsetenv("LIGHTDOCK_BM_DEBUG");
+            CHECK(access(dbg.c_str(), R_OK) == 0);
+        }
+        ld_scorer_destroy(c);
+    }
+    unsetenv("LIGHTDOCK_BM_LANES");
+    {   // molecules that flex: the ANM form (amplitudes by row, the flexed receptor's boxes), passes of 16 and the default pass
+        std::vector<double> rec_nm(1615 * 3 * 10), lig_nm(221 * 3 * 10);
+        for (size_t i = 0; i < rec_nm.size(); i++) rec_nm[i] = 0.01 * (double)((i * 2654435761u) % 200) - 1.0;
+        for (size_t i = 0; i < lig_nm.size(); i++) lig_nm[i] = 0.01 * (double)((i * 40503u) % 200) - 1.0;
+        for (int pass = 0; pass < 2; pass++) {
+            if (pass == 1) unsetenv("LIGHTDOCK_BM_CHUNK");
+            ld_scorer *a = dfire(rec_nm.data(), lig_nm.data(), 10, table.data());
+            CHECK(a != nullptr);
+            if (!a) continue;
+            CHECK(ld_scorer_pose_len(a) == 27);
+            bm_batches(a, 70, "dfire_bm_pairs");
+            ld_scorer_destroy(a);
+        }
+    }
+    {   // a complex the path declines (a table value beyond the fixed-point sums' limit): the pose-major kernel, and nothing
+        // allocated for the block-major path -- construction allocates what a scorer that never asks for the path does
+        std::vector<double> big(table);
+        big[12345] = 2000.0;
+        size_t before = ld_stub_device_allocations();
+        ld_scorer *d = dfire(nullptr, nullptr, 0, big.data());
+        const size_t declined = ld_stub_device_allocations() - before;
+        CHECK(d != nullptr);
+        if (d) {
+            uint32_t quiet = 1;
+            CHECK(ld_scorer_bm_quiet_subtiles(d, &quiet) == LD_OK && quiet == 0);
+            bm_batches(d, 70, "dfire_packed_pairs");
+            ld_scorer_destroy(d);
+        }
+        setenv("LIGHTDOCK_DFIRE_KERNEL", "packed", 1);
+        before = ld_stub_device_allocations();
+        d = dfire(nullptr, nullptr, 0, big.data());
+        CHECK(d != nullptr && ld_stub_device_allocations() - before == declined);
+        if (d) ld_scorer_destroy(d);
+        unsetenv("LIGHTDOCK_DFIRE_KERNEL");
     }
     CHECK(ld_scorer_create_from_pdb(7, rec1.c_str(), lig1.c_str(), nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, nullptr, 0,
                                     nullptr, 0, 0, 0, table.data()) == nullptr);

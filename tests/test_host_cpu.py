@@ -635,3 +635,114 @@ def test_shipped_library_has_no_diagnostic_switch(pkg):
     assert b"_DIAG_" not in blob
     for name in diag_only:
         assert name.encode() not in blob, name + " is in the shipped library"
+
+
+# ---- the block-major workspace: one description (kernels/dfire_bm.hpp, bm_layout) -------------------------------------------
+# The constants of kernels/dfire_bm.hpp, restated: a change there has to be made here too, on purpose.
+BM_COUNTERS, BM_CULL_QUEUE_WORDS, BM_JOB_ROWS, BM_PART_ENTRIES, BM_AMP_FLOATS, BM_MAX_MODES, BM_DEBUG_WORDS = 8, 256, 8, 1792, 24, 10, 14
+BM_QUEUE_CAP = (8 * BM_PART_ENTRIES + 4096 + 512) + 8 * BM_PART_ENTRIES + 64
+
+
+def bm_workspace_table(n_rt, n_lt, cap, sets, waves, anm, counts, debug):
+    """The layout of the block-major workspace as the project's documents state it, in bytes:
+    ({buffer: bytes}, {region: (buffer, offset of set w as a function, bytes of a set)})."""
+    tp = n_rt * n_lt
+    parts = tp * (cap // 64 + 1)
+    tp_set = (tp + BM_COUNTERS + BM_CULL_QUEUE_WORDS) * 4
+    buffers = {
+        "rt": sets * cap * (12 * 4 + 8 * 8),
+        "tp_count": sets * tp_set,
+        "jobs": sets * parts * 2 * 4,
+        "job_cost": sets * parts * BM_JOB_ROWS * 4,
+        "job_order": sets * parts * BM_JOB_ROWS * 5 * 4 + 16,
+        "queue": sets * waves * BM_QUEUE_CAP * 8,
+        "ent_row": (sets * tp * cap + BM_PART_ENTRIES) * 4,
+        "ent_mask": (sets * tp * cap + BM_PART_ENTRIES) * 8,
+        "ent_partial": sets * waves * BM_PART_ENTRIES * 8,
+        "tile_sum": sets * cap * n_lt * 8,
+        "exact_fix": sets * cap * 8,
+        "amp": sets * cap * (BM_AMP_FLOATS * 4 + 2 * BM_MAX_MODES * 8) if anm else 0,
+        "anm_sub": sets * cap * n_rt * 8 * 32 if anm else 0,
+        "anm_tile": sets * cap * n_rt * 32 if anm else 0,
+        "tile_tested": sets * cap * n_lt * 4 if counts else 0,
+        "exact_pairs": sets * cap * 4 if counts else 0,
+        "debug": waves * BM_DEBUG_WORDS * 8 if debug else 0,
+    }
+    regions = {
+        "rt": ("rt", lambda w: w * cap * 12 * 4, cap * 12 * 4),
+        "rt_exact": ("rt", lambda w: sets * cap * 48 + w * cap * 8 * 8, cap * 8 * 8),
+        "tp_count": ("tp_count", lambda w: w * tp_set, tp * 4),
+        "job_count": ("tp_count", lambda w: w * tp_set + tp * 4, (BM_COUNTERS + BM_CULL_QUEUE_WORDS) * 4),
+        "job_next": ("tp_count", lambda w: w * tp_set + (tp + 1) * 4, 4),
+        "jobs": ("jobs", lambda w: w * parts * 2 * 4, parts * 2 * 4),
+        "job_cost": ("job_cost", lambda w: w * parts * BM_JOB_ROWS * 4, parts * BM_JOB_ROWS * 4),
+        "job_order": ("job_order", lambda w: w * parts * BM_JOB_ROWS * 4, parts * BM_JOB_ROWS * 4),
+        "job_rec": ("job_order", lambda w: (sets * parts * BM_JOB_ROWS + w * parts * BM_JOB_ROWS * 4) * 4, parts * BM_JOB_ROWS * 16),
+        "queue": ("queue", lambda w: w * waves * BM_QUEUE_CAP * 8, waves * BM_QUEUE_CAP * 8),
+        "ent_row": ("ent_row", lambda w: w * tp * cap * 4, tp * cap * 4),
+        "ent_mask": ("ent_mask", lambda w: w * tp * cap * 8, tp * cap * 8),
+        "ent_partial": ("ent_partial", lambda w: w * waves * BM_PART_ENTRIES * 8, waves * BM_PART_ENTRIES * 8),
+        "tile_sum": ("tile_sum", lambda w: w * cap * n_lt * 8, cap * n_lt * 8),
+        "exact_fix": ("exact_fix", lambda w: w * cap * 8, cap * 8),
+        "amp": ("amp", lambda w: w * cap * BM_AMP_FLOATS * 4, cap * BM_AMP_FLOATS * 4 if anm else 0),
+        "amp_exact": ("amp", lambda w: sets * cap * BM_AMP_FLOATS * 4 + w * cap * 2 * BM_MAX_MODES * 8, cap * 2 * BM_MAX_MODES * 8 if anm else 0),
+        "anm_sub": ("anm_sub", lambda w: w * cap * n_rt * 8 * 32, cap * n_rt * 8 * 32 if anm else 0),
+        "anm_tile": ("anm_tile", lambda w: w * cap * n_rt * 32, cap * n_rt * 32 if anm else 0),
+        "tile_tested": ("tile_tested", lambda w: w * cap * n_lt * 4, cap * n_lt * 4 if counts else 0),
+        "exact_pairs": ("exact_pairs", lambda w: w * cap * 4, cap * 4 if counts else 0),
+        "debug": ("debug", lambda w: 0, waves * BM_DEBUG_WORDS * 8 if debug else 0),
+    }
+    return buffers, regions
+
+
+BM_SHAPES = {   # n_rt, n_lt, cap, sets, anm, counts, debug
+    "1k4c": (54, 52, 8192, 1, False, False, False),                 # 2 808 tile pairs, the default workload's batch in one pass
+    "1ppe": (26, 4, 8192, 1, False, False, False),
+    "1ppe-chunk16-two-sets": (26, 4, 16, 2, False, False, False),   # LIGHTDOCK_BM_CHUNK=16 of the GPU matrix
+    "1ppe-chunk16-counting": (26, 4, 16, 2, False, True, True),
+    "anm": (28, 7, 8192, 1, True, False, False),
+    "anm-counting-two-sets": (28, 7, 1024, 2, True, True, False),
+    "cap-not-a-multiple-of-64": (26, 4, 300, 1, False, True, False),
+    "cap-odd-two-sets": (54, 52, 37, 2, True, True, True),
+}
+
+
+@pytest.mark.parametrize("name", sorted(BM_SHAPES))
+def test_block_major_workspace_layout(pkg, name):
+    """The one description of the block-major workspace (bm_layout, the function the scorer reserves and points its launches
+    with) against the table of the documents, restated here; and what any layout must satisfy: the regions of a buffer do not
+    overlap, each ends inside its buffer, 64-bit regions are 8-byte aligned and the ones the kernels read with 16-byte loads
+    16-byte aligned."""
+    n_rt, n_lt, cap, sets, anm, counts, debug = BM_SHAPES[name]
+    waves = 256 * 8
+    got = pkg.dfire_bm_workspace(n_rt, n_lt, cap, sets, waves, anm=anm, counts=counts, debug=debug)
+    buffers, regions = bm_workspace_table(n_rt, n_lt, cap, sets, waves, anm, counts, debug)
+    assert sorted(got) == sorted(regions)
+    spans = {}
+    for region, (buffer, offset, size) in regions.items():
+        g = got[region]
+        assert g["buffer"] == buffer and g["buffer_bytes"] == buffers[buffer], (region, g, buffers[buffer])
+        assert g["bytes"] == size, (region, g, size)
+        per_set = 1 if region == "debug" else sets
+        if not size:   # a region the shape does not ask for: no bytes, nowhere
+            assert buffers[buffer] == 0
+            continue
+        for w in range(per_set):
+            at = g["base"] + w * g["stride"]
+            assert at == offset(w), (region, w, at, offset(w))
+            assert at + size <= buffers[buffer], (region, w)
+            spans.setdefault(buffer, []).append((at, at + size, region, w))
+        align = {"rt_exact": 16, "job_rec": 16, "amp_exact": 16, "queue": 8, "ent_mask": 8, "ent_partial": 8, "tile_sum": 8,
+                 "exact_fix": 8, "debug": 8, "anm_sub": 16, "anm_tile": 16}.get(region, 4)
+        assert all((g["base"] + w * g["stride"]) % align == 0 for w in range(per_set)), (region, align)
+    # every byte of a buffer belongs to at most one region; job_next is, by definition, the second of job_count's counters
+    for buffer, items in spans.items():
+        items = sorted(i for i in items if i[2] != "job_next")
+        for a, b in zip(items, items[1:]):
+            assert a[1] <= b[0], (buffer, a, b)
+    for w in range(sets):
+        assert got["job_next"]["base"] + w * got["job_next"]["stride"] == got["job_count"]["base"] + w * got["job_count"]["stride"] + 4
+    # the slack behind the entries: one part
+    for buffer, word in (("ent_row", 4), ("ent_mask", 8)):
+        last = max(e for _, e, _, _ in spans[buffer])
+        assert buffers[buffer] - last == BM_PART_ENTRIES * word
