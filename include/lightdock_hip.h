@@ -309,9 +309,39 @@ int ld_complex_cluster(ld_complex *c, size_t n_swarms, size_t n_glowworms, const
                        int32_t *cluster_of /* n_swarms x n_glowworms */,
                        int32_t *representatives /* n_swarms x n_glowworms */,
                        uint32_t *n_clusters /* n_swarms */);
-int ld_complex_last_kernel_ms(const ld_complex *c, double *ms_out); /* kernels of the last cluster call (HIP events) */
+int ld_complex_last_kernel_ms(const ld_complex *c, double *ms_out); /* kernels of the last cluster or contacts call (HIP events) */
 /* lgd_top.py: receptor then ligand ATOM/HETATM lines as line[:30] + "%8.3f%8.3f%8.3f" + line[54:] */
 int ld_complex_write_pdb(ld_complex *c, const double *pose, const char *path);
+
+/* Interface contacts: for every pose, which receptor and which ligand residues touch.  The primitive
+ * under LightDock's lgd_filter_restraints.py and lgd_filter_membrane.py, which re-read the PDB file of
+ * a model and compare a distance matrix with a cutoff; those tools are not part of the reference
+ * tree, so the rule below is this library's own definition, modelled on them.
+ *   Residues: a residue is a maximal run of consecutive ATOM/HETATM records (file order) with the same
+ *     residue name (columns 18-20), chain (22), sequence number (23-26) and insertion code (27).  Its
+ *     id is AtomRecord::residue_id() (src/dfire.rs:139-142), "<chain>.<resname>.<serial><icode>",
+ *     e.g. A.SER.467, H.ASP.52A.  Indices count runs in file order, receptor and ligand separately.
+ *   Posing: as above (f64, reference operation order); every coordinate is then the integer number
+ *     of thousandths that "%8.3f" prints, so the contacts of a pose are those of the file
+ *     ld_complex_write_pdb writes for it.
+ *   Contact: C = llrint(cutoff * 1000), 1 <= C <= 30000.  Receptor atom a and ligand atom b touch iff
+ *     dx^2 + dy^2 + dz^2 <= C^2 in exact integer arithmetic on the thousandths.  A residue is in
+ *     contact iff any of its atoms touches any atom of the other molecule.  All atoms count
+ *     (hydrogens, hetero atoms, membrane beads).  No floating-point comparison decides anything.
+ * Bit k of word w of a pose's row is residue 32 w + k; bits beyond the last residue are 0.
+ * LD_ERR_INVALID, nothing written: non-finite poses, a zero quaternion, stride < pose_len, a cutoff
+ * that is NaN or whose C is outside 1 .. 30000, a side other than 0 / 1, a buffer too short for an
+ * id, a posed coordinate beyond +-1.0e6 A (so that the difference of two coordinates fits an int32).
+ * Replaces the distance-matrix pass of lgd_filter_restraints.py / lgd_filter_membrane.py over per-model
+ * PDB files.  Device workspace: one slot of atoms x 16 B (plus 24 B a residue and a group of 8 ligand
+ * residues when those boxes exceed 40 KiB) per workgroup in flight, at most 1024 slots and 256 MiB (or one slot). */
+size_t ld_complex_num_residues(const ld_complex *c, int side); /* 0 receptor, 1 ligand */
+int ld_complex_residue_id(const ld_complex *c, int side, size_t index, char *buf, size_t buf_len);
+int ld_complex_residue_of_atom(const ld_complex *c, int side, uint32_t *out /* n_atoms of that side */);
+/* Either output may be NULL; n == 0 is LD_OK.  ld_complex_last_kernel_ms then reports this call's kernels. */
+int ld_complex_contacts(ld_complex *c, size_t n, const double *poses, size_t stride, double cutoff,
+                        uint32_t *rec_bits /* n x ceil(n_rec_res / 32) */,
+                        uint32_t *lig_bits /* n x ceil(n_lig_res / 32) */);
 
 /* ------------------------------------------------------------------------------------
  * The reference command line (src/bin/lightdock-rust.rs:77-333) as a function:

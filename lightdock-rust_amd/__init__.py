@@ -149,6 +149,11 @@ def load_library():
     lib.ld_complex_cluster.argtypes = [vp, sz, sz, vp, sz, vp, C.c_double, vp, vp, vp]
     lib.ld_complex_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     lib.ld_complex_write_pdb.argtypes = [vp, vp, C.c_char_p]
+    lib.ld_complex_num_residues.restype = sz
+    lib.ld_complex_num_residues.argtypes = [vp, C.c_int]
+    lib.ld_complex_residue_id.argtypes = [vp, C.c_int, sz, C.c_char_p, sz]
+    lib.ld_complex_residue_of_atom.argtypes = [vp, C.c_int, vp]
+    lib.ld_complex_contacts.argtypes = [vp, sz, vp, sz, C.c_double, vp, vp]
     _lib = lib
     return lib
 
@@ -534,7 +539,8 @@ class GSO:
 
 
 class Complex:
-    """LightDock's analysis of a run (ld_complex_*): posed coordinates, BSAS clustering of whole swarms, top-model PDBs."""
+    """LightDock's analysis of a run (ld_complex_*): posed coordinates, BSAS clustering of whole swarms, top-model PDBs,
+    per-pose interface contacts."""
 
     def __init__(self, receptor_pdb, ligand_pdb, rec_nmodes=None, rec_num_anm=0, lig_nmodes=None, lig_num_anm=0):
         self.lib = load_library()
@@ -579,6 +585,44 @@ class Complex:
         ms = C.c_double()
         _check(self.lib.ld_complex_last_kernel_ms(self._h, C.byref(ms)))
         return ms.value
+
+    def num_residues(self, side):
+        """0: receptor, 1: ligand."""
+        return self.lib.ld_complex_num_residues(self._h, side)
+
+    def residues(self, side):
+        """Residue ids ("A.SER.467", "H.ASP.52A") of one side, in file order: the columns of contacts()."""
+        buf = C.create_string_buffer(64)
+        ids = []
+        for i in range(self.num_residues(side)):
+            _check(self.lib.ld_complex_residue_id(self._h, side, i, buf, len(buf)))
+            ids.append(buf.value.decode())
+        if not ids:   # a side other than 0 / 1
+            _check(self.lib.ld_complex_residue_id(self._h, side, 0, buf, len(buf)))
+        return ids
+
+    def residue_of_atom(self, side):
+        out = np.empty(self.num_atoms(side) if side in (0, 1) else 0, dtype=np.uint32)
+        _check(self.lib.ld_complex_residue_of_atom(self._h, side, _ptr(out)))
+        return out
+
+    def contacts(self, poses, cutoff=5.0, packed=False):
+        """(n, >= pose_len) poses -> {"rec": bool (n, receptor residues), "lig": bool (n, ligand residues)}: the residues
+        with an atom within `cutoff` of the other molecule, on the coordinates "%8.3f" prints (ld_complex_contacts).
+        packed=True: the call's uint32 words instead (bit k of word w is residue 32 w + k)."""
+        poses = _f64(poses)
+        if poses.ndim != 2:
+            raise ValueError("poses must be (n, pose_len)")
+        n, out = poses.shape[0], {}
+        words = {k: np.zeros((n, (self.num_residues(side) + 31) // 32), dtype=np.uint32) for side, k in enumerate(("rec", "lig"))}
+        _check(self.lib.ld_complex_contacts(self._h, n, _ptr(poses), poses.shape[1], C.c_double(cutoff), _ptr(words["rec"]),
+                                            _ptr(words["lig"])))
+        if packed:
+            return words
+        for side, k in enumerate(("rec", "lig")):
+            bits = np.unpackbits(words[k].view(np.uint8), axis=1, bitorder="little")   # little-endian words: bit 32 w + k
+            out[k] = bits[:, :self.num_residues(side)].astype(bool)
+        return out
 
     def write_pdb(self, pose, path):
         pose = _f64(pose).ravel()

@@ -3,7 +3,9 @@
 //   complex_pose_thousandths:  poses x CA / P atoms -> posed coordinates as the integer thousandths "%8.3f" prints
 //                              (lgd_cluster_bsas.py clusters the PDB files it wrote, so it sees exactly those);
 //   complex_bsas:              one workgroup per swarm: sort (scoring desc, glowworm asc) in LDS, then the greedy BSAS
-//                              pass one representative at a time.
+//                              pass one representative at a time;
+//   complex_contacts:          one workgroup a pose: which receptor and which ligand residues touch (ld_complex_contacts;
+//                              what lgd_filter_restraints.py and lgd_filter_membrane.py ask of a model's PDB file).
 // Posing: receptor R_a + sum_m rec_ext[m] rec_mode[m][a]; ligand rotate(q, L_a + sum_m lig_ext[m] lig_mode[m][a]) + t,
 // i.e. the ligand's modes in the ligand frame -- NOT the energy's convention (src/dfire.rs:282-302).  f64, qt.rs order,
 // -ffp-contract=off.  Workspace: the thousandths of a chunk of swarms, at most kClusterWorkspaceBytes (or one swarm's
@@ -11,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -236,13 +239,231 @@ unsigned grid_for(size_t total) {
     return (unsigned)std::max<size_t>(1, std::min<size_t>(blocks, 8192));
 }
 
+// --- contacts: which receptor and which ligand residues of a pose touch (lightdock_hip.h, "Interface contacts") -------
+// One kernel, one workgroup a pose at a time (a launch has at most kContactSlots workgroups, each with a workspace slot it
+// reuses for pose blockIdx, blockIdx + gridDim, ...), all on the integer thousandths:
+//   1. every atom is posed once and kept as int4 (x, y, z, 0) in the slot (global memory, read back through L2); the same
+//      pass folds it into the int32 min / max box of its residue with atomicMin / atomicMax;
+//   2. the boxes of every group of kResGroup consecutive LIGAND residues from those of its residues.  Boxes are in LDS
+//      when they fit kMaxBoxLdsBytes, else in the slot (one generic pointer serves both);
+//   3. the receptor residues, dealt to the waves round robin, are culled against the whole ligand's box (a lane each); a
+//      surviving receptor residue against the ligand groups (a lane each), against the residues of a surviving group,
+//      and a surviving residue pair is walked 8 x 8 atoms at a time, stopping at the first contact.  (Groups of
+//      consecutive RECEPTOR residues cull nothing on 1k4c: its membrane beads follow each other in the file, not in space.)
+//   4. bits are ORed in LDS and every output word is stored once.
+// Every coordinate is within +-kCoordBound (the call fails otherwise), so the difference of any two fits an int32.
+
+constexpr int kContactThreads = 512;
+constexpr int kContactSlots = 1024;            // 256 CUs x 4 resident workgroups
+constexpr int kResGroup = 8;
+constexpr int kCoordBound = 1000000000;        // thousandths: +-1.0e6 A
+constexpr uint32_t kAxisClamp = 32767;         // > 30000 >= C
+constexpr size_t kMaxContactWords = 16384;     // bit words of both sides, kept in LDS (64 KiB: 524 288 residues)
+constexpr size_t kMaxBoxLdsBytes = 40 << 10;   // 24 B a box: up to 1706 residues + ligand groups (1k4c: 1327) keep four workgroups a CU
+
+struct ContactsDevice {
+    int n_atoms = 0, n_rec_res = 0, n_lig_res = 0, n_lig_grp = 0;  // groups: kResGroup consecutive ligand residues
+    int boxes_in_lds = 0;
+    const uint32_t *res_start = nullptr;  // n_rec_res + n_lig_res + 1 complex atom indices, receptor residues first
+    const uint32_t *res_of_atom = nullptr;  // n_atoms residue indices, the ligand's after the receptor's
+    __host__ __device__ int n_boxes() const { return n_rec_res + n_lig_res + n_lig_grp; }
+    size_t box_bytes() const { return (size_t)n_boxes() * 6 * sizeof(int); }
+};
+
+// min(|d|, 32767) of a coordinate difference.  32767 > 30000 >= C: a clamped axis alone already exceeds the cutoff,
+// so clamping never changes dx^2 + dy^2 + dz^2 <= C^2, and the sum of three squares stays below 3 * 2^30 < 2^32:
+// 24-bit multiplies and one 32-bit compare, no 64-bit arithmetic.
+__device__ __forceinline__ uint32_t clamped_abs(int d) { return min((uint32_t)abs(d), kAxisClamp); }
+
+__device__ __forceinline__ uint32_t square_sum(uint32_t x, uint32_t y, uint32_t z) {
+    return __umul24(x, x) + __umul24(y, y) + __umul24(z, z);
+}
+
+__device__ __forceinline__ bool in_contact(const int4 &a, const int4 &b, uint32_t C2) {
+    return square_sum(clamped_abs(a.x - b.x), clamped_abs(a.y - b.y), clamped_abs(a.z - b.z)) <= C2;
+}
+
+// Box b of a pose is box[k * n_boxes + b], k = min x, y, z, max x, y, z: consecutive lanes read consecutive words.
+// b: residues (receptor, then ligand), receptor groups, ligand groups.
+struct Box {
+    int lo[3], hi[3];
+};
+
+__device__ __forceinline__ Box load_box(const int *box, int n_boxes, int b) {
+    Box v;
+    for (int k = 0; k < 3; k++) {
+        v.lo[k] = box[k * n_boxes + b];
+        v.hi[k] = box[(3 + k) * n_boxes + b];
+    }
+    return v;
+}
+
+__device__ __forceinline__ void store_box(int *box, int n_boxes, int b, const Box &v) {
+    for (int k = 0; k < 3; k++) {
+        box[k * n_boxes + b] = v.lo[k];
+        box[(3 + k) * n_boxes + b] = v.hi[k];
+    }
+}
+
+// The gap between two intervals on one axis (0 when they overlap), clamped like a difference.
+__device__ __forceinline__ uint32_t clamped_gap(int lo_a, int hi_a, int lo_b, int hi_b) {
+    return min((uint32_t)max(max(lo_a - hi_b, lo_b - hi_a), 0), kAxisClamp);
+}
+
+// Exact: every atom pair of the two boxes is at least the gap apart on each axis, so a box distance above C (which an
+// axis gap above C implies) leaves no pair within C.  Nothing is padded.
+__device__ __forceinline__ bool boxes_within(const Box &a, const Box &b, uint32_t C2) {
+    return square_sum(clamped_gap(a.lo[0], a.hi[0], b.lo[0], b.hi[0]), clamped_gap(a.lo[1], a.hi[1], b.lo[1], b.hi[1]),
+                      clamped_gap(a.lo[2], a.hi[2], b.lo[2], b.hi[2])) <= C2;
+}
+
+// 8 waves a SIMD: four workgroups a CU hide the latency of the dependent loads
+__global__ void __launch_bounds__(kContactThreads, 8) complex_contacts(ComplexDevice m, ContactsDevice d, const double *poses,
+                                                                    size_t stride, size_t n, uint32_t C2, int4 *atoms_ws,
+                                                                    int *boxes_ws, uint32_t *rec_bits, uint32_t *lig_bits,
+                                                                    int *overflow) {
+    extern __shared__ uint32_t s_bits[];  // receptor words, ligand words, then the boxes if they fit
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int rw = (d.n_rec_res + 31) >> 5, lw = (d.n_lig_res + 31) >> 5;
+    const int n_res = d.n_rec_res + d.n_lig_res, n_boxes = n_res + d.n_lig_grp;
+    int4 *A = atoms_ws + (size_t)blockIdx.x * d.n_atoms;
+    int *box = d.boxes_in_lds ? reinterpret_cast<int *>(s_bits + rw + lw) : boxes_ws + (size_t)blockIdx.x * 6 * n_boxes;
+    const uint32_t *lig_start = d.res_start + d.n_rec_res;
+    const int lig_grp = n_res;  // first group box
+    const int lig_res = d.n_rec_res;
+
+    for (size_t pose = blockIdx.x; pose < n; pose += gridDim.x) {
+        const double *row = poses + pose * stride;
+        for (int i = tid; i < rw + lw; i += kContactThreads) s_bits[i] = 0;
+        for (int r = tid; r < n_res; r += kContactThreads)
+            store_box(box, n_boxes, r, Box{{INT_MAX, INT_MAX, INT_MAX}, {INT_MIN, INT_MIN, INT_MIN}});
+        __syncthreads();
+        // every atom is posed once; its residue's box falls out of the same pass (min / max are order-free)
+#pragma unroll 1
+        for (int a = tid; a < d.n_atoms; a += kContactThreads) {
+            const P3 p = pose_atom(m, row, (uint32_t)a);
+            const double c[3] = {thousandths(p.x), thousandths(p.y), thousandths(p.z)};
+            const int r = (int)d.res_of_atom[a];
+            int v[3];
+            for (int k = 0; k < 3; k++) {
+                if (!(fabs(c[k]) <= (double)kCoordBound)) *overflow = 1;
+                v[k] = (int)fmax(-(double)kCoordBound, fmin((double)kCoordBound, c[k]));  // clamped: nothing later can wrap
+                atomicMin(&box[k * n_boxes + r], v[k]);
+                atomicMax(&box[(3 + k) * n_boxes + r], v[k]);
+            }
+            A[a] = make_int4(v[0], v[1], v[2], 0);
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int g = tid; g < d.n_lig_grp; g += kContactThreads) {
+            const int r0 = lig_res + g * kResGroup, r1 = min(r0 + kResGroup, n_res);
+            Box b = load_box(box, n_boxes, r0);
+#pragma unroll 1
+            for (int r = r0 + 1; r < r1; r++) {
+                const Box o = load_box(box, n_boxes, r);
+                for (int k = 0; k < 3; k++) b.lo[k] = min(b.lo[k], o.lo[k]), b.hi[k] = max(b.hi[k], o.hi[k]);
+            }
+            store_box(box, n_boxes, lig_grp + g, b);
+        }
+        __syncthreads();
+
+        // all control flow below is uniform over the wave: the masks come from ballots
+        // the whole ligand's box, every wave for itself: lanes over the groups, then a butterfly
+        Box whole{{INT_MAX, INT_MAX, INT_MAX}, {INT_MIN, INT_MIN, INT_MIN}};
+        for (int g = lane; g < d.n_lig_grp; g += 64) {
+            const Box o = load_box(box, n_boxes, lig_grp + g);
+            for (int k = 0; k < 3; k++) whole.lo[k] = min(whole.lo[k], o.lo[k]), whole.hi[k] = max(whole.hi[k], o.hi[k]);
+        }
+        for (int step = 1; step < 64; step <<= 1)
+            for (int k = 0; k < 3; k++) {
+                whole.lo[k] = min(whole.lo[k], __shfl_xor(whole.lo[k], step));
+                whole.hi[k] = max(whole.hi[k], __shfl_xor(whole.hi[k], step));
+            }
+        // receptor residues are dealt to the waves round robin (neighbours in the file are neighbours in space, and
+        // so are the residues of the interface): residue (64 i + lane) * waves + wave
+        constexpr int kWaves = kContactThreads / 64;
+        for (int base = 0; base * kWaves < d.n_rec_res; base += 64) {
+            const int mine = (base + lane) * kWaves + wave;
+            const Box mb = load_box(box, n_boxes, min(mine, d.n_rec_res - 1));
+            unsigned long long residues = __builtin_amdgcn_ballot_w64(mine < d.n_rec_res && boxes_within(mb, whole, C2));
+            while (residues) {
+                const int rr = (base + __ffsll(residues) - 1) * kWaves + wave;
+                residues &= residues - 1;
+                const Box rb = load_box(box, n_boxes, rr);
+                const uint32_t rbit = 1u << (rr & 31);
+                const int a0 = (int)d.res_start[rr], a1 = (int)d.res_start[rr + 1];
+                for (int lg0 = 0; lg0 < d.n_lig_grp; lg0 += 64) {
+                    const int lg = lg0 + lane;
+                    unsigned long long groups =
+                        __builtin_amdgcn_ballot_w64(lg < d.n_lig_grp && boxes_within(rb, load_box(box, n_boxes, lig_grp + lg), C2));
+                    while (groups) {
+                        const int lgi = lg0 + __ffsll(groups) - 1;
+                        groups &= groups - 1;
+                        const int l = lgi * kResGroup + lane;  // the first kResGroup lanes: a ligand residue each
+                        unsigned long long pairs = __builtin_amdgcn_ballot_w64(
+                            lane < kResGroup && l < d.n_lig_res && boxes_within(rb, load_box(box, n_boxes, lig_res + l), C2));
+                        while (pairs) {
+                            const int ll = lgi * kResGroup + __ffsll(pairs) - 1;
+                            pairs &= pairs - 1;
+                            const uint32_t lbit = 1u << (ll & 31);
+                            // the result is an OR: a pair whose two bits are set has nothing to add (a stale read of
+                            // another wave's bit only costs the walk)
+                            const uint32_t have_r = __builtin_amdgcn_readfirstlane(s_bits[rr >> 5]);
+                            const uint32_t have_l = __builtin_amdgcn_readfirstlane(s_bits[rw + (ll >> 5)]);
+                            if ((have_r & rbit) && (have_l & lbit)) continue;
+                            const int b0 = (int)lig_start[ll], b1 = (int)lig_start[ll + 1];
+                            bool hit = false;
+                            for (int ta = a0; ta < a1 && !hit; ta += 8)
+                                for (int tb = b0; tb < b1 && !hit; tb += 8) {
+                                    const int a = ta + (lane >> 3), b = tb + (lane & 7);
+                                    hit = __builtin_amdgcn_ballot_w64(a < a1 && b < b1 && in_contact(A[a], A[b], C2)) != 0;
+                                }
+                            if (hit && lane == 0) {
+                                if (!(have_r & rbit)) atomicOr(&s_bits[rr >> 5], rbit);
+                                if (!(have_l & lbit)) atomicOr(&s_bits[rw + (ll >> 5)], lbit);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < rw; i += kContactThreads) rec_bits[pose * rw + i] = s_bits[i];
+        for (int i = tid; i < lw; i += kContactThreads) lig_bits[pose * lw + i] = s_bits[rw + i];
+        __syncthreads();  // the slot and the words are reused by the next pose
+    }
+}
+
 // --- host side -------------------------------------------------------------------------------------------------
 
 struct PdbFile {
     std::vector<std::string> lines;  // ATOM / HETATM records as read (other records are dropped)
     std::vector<double> xyz;
     std::vector<uint32_t> backbone;  // atoms named CA or P
+    // residues: maximal runs of consecutive records with the same columns 18-20, 22, 23-26 and 27
+    std::vector<uint32_t> res_start;     // first atom of each residue, then the atom count
+    std::vector<uint32_t> res_of_atom;
+    std::vector<std::string> res_id;     // "<chain>.<resname>.<serial><icode>", AtomRecord::residue_id() (src/dfire.rs:139-142)
 };
+
+std::string trimmed(const std::string &s) {
+    const size_t b = s.find_first_not_of(' ');
+    return b == std::string::npos ? std::string() : s.substr(b, s.find_last_not_of(' ') - b + 1);
+}
+
+void cut_residues(PdbFile &f) {
+    for (size_t a = 0; a < f.lines.size(); a++) {
+        const std::string &line = f.lines[a];
+        // resname; chain, serial, icode
+        if (a == 0 || line.compare(17, 3, f.lines[a - 1], 17, 3) != 0 || line.compare(21, 6, f.lines[a - 1], 21, 6) != 0) {
+            f.res_start.push_back((uint32_t)a);
+            f.res_id.push_back(trimmed(line.substr(21, 1)) + "." + trimmed(line.substr(17, 3)) + "." +
+                               std::to_string(std::strtol(line.substr(22, 4).c_str(), nullptr, 10)) + trimmed(line.substr(26, 1)));
+        }
+        f.res_of_atom.push_back((uint32_t)f.res_id.size() - 1);
+    }
+    f.res_start.push_back((uint32_t)f.lines.size());
+}
 
 PdbFile read_pdb_file_order(const char *path) {
     if (!path) throw Error(LD_ERR_INVALID, "PDB path missing");
@@ -268,6 +489,7 @@ PdbFile read_pdb_file_order(const char *path) {
         f.lines.push_back(line);
     }
     if (f.lines.empty()) throw Error(LD_ERR_INVALID, std::string(path) + ": no ATOM/HETATM records");
+    cut_residues(f);
     return f;
 }
 
@@ -293,6 +515,7 @@ struct ld_complex {
     ld::DeviceArena arena;
     ld::ComplexDevice dev;
     const uint32_t *d_backbone = nullptr;
+    ld::ContactsDevice contacts;
     ld::DeviceBuffer d_poses, d_scores, d_out, d_ws, d_ids;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -402,6 +625,18 @@ ld_complex *ld_complex_create(const char *receptor_pdb, const char *ligand_pdb, 
         h->backbone = h->rec.backbone;
         for (uint32_t a : h->lig.backbone) h->backbone.push_back(a + (uint32_t)d.n_rec);
         h->d_backbone = h->arena.upload(h->backbone);
+        std::vector<uint32_t> res_start(h->rec.res_start.begin(), h->rec.res_start.end() - 1);
+        for (uint32_t a : h->lig.res_start) res_start.push_back(a + (uint32_t)d.n_rec);
+        ld::ContactsDevice &k = h->contacts;
+        k.n_atoms = d.n_rec + d.n_lig;
+        k.n_rec_res = (int)h->rec.res_id.size();
+        k.n_lig_res = (int)h->lig.res_id.size();
+        k.n_lig_grp = (k.n_lig_res + ld::kResGroup - 1) / ld::kResGroup;
+        k.res_start = h->arena.upload(res_start);
+        std::vector<uint32_t> res_of_atom = h->rec.res_of_atom;
+        for (uint32_t r : h->lig.res_of_atom) res_of_atom.push_back(r + (uint32_t)k.n_rec_res);
+        k.res_of_atom = h->arena.upload(res_of_atom);
+        k.boxes_in_lds = k.box_bytes() <= ld::kMaxBoxLdsBytes;
         c = h.release();
     });
     return rc == LD_OK ? c : nullptr;
@@ -486,6 +721,75 @@ int ld_complex_last_kernel_ms(const ld_complex *c, double *ms_out) {
     return guarded_complex([&] {
         if (!c || !ms_out) throw ld::Error(LD_ERR_INVALID, "null argument");
         *ms_out = c->last_kernel_ms;
+    });
+}
+
+size_t ld_complex_num_residues(const ld_complex *c, int side) {
+    if (!c) return 0;
+    return side == 0 ? c->rec.res_id.size() : side == 1 ? c->lig.res_id.size() : 0;
+}
+
+int ld_complex_residue_id(const ld_complex *c, int side, size_t index, char *buf, size_t buf_len) {
+    return guarded_complex([&] {
+        if (!c || !buf) throw ld::Error(LD_ERR_INVALID, "null argument");
+        if (side != 0 && side != 1) throw ld::Error(LD_ERR_INVALID, "side must be 0 (receptor) or 1 (ligand)");
+        const std::vector<std::string> &ids = side == 0 ? c->rec.res_id : c->lig.res_id;
+        if (index >= ids.size()) throw ld::Error(LD_ERR_INVALID, "residue index out of range");
+        if (ids[index].size() + 1 > buf_len) throw ld::Error(LD_ERR_INVALID, "buffer too short for the residue id");
+        std::memcpy(buf, ids[index].c_str(), ids[index].size() + 1);
+    });
+}
+
+int ld_complex_residue_of_atom(const ld_complex *c, int side, uint32_t *out) {
+    return guarded_complex([&] {
+        if (!c || !out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        if (side != 0 && side != 1) throw ld::Error(LD_ERR_INVALID, "side must be 0 (receptor) or 1 (ligand)");
+        const std::vector<uint32_t> &of = side == 0 ? c->rec.res_of_atom : c->lig.res_of_atom;
+        std::copy(of.begin(), of.end(), out);
+    });
+}
+
+int ld_complex_contacts(ld_complex *c, size_t n, const double *poses, size_t stride, double cutoff, uint32_t *rec_bits,
+                        uint32_t *lig_bits) {
+    return guarded_complex([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        const double scaled = cutoff * 1000.0;
+        if (!(scaled > 0.0 && scaled < 30001.0)) throw ld::Error(LD_ERR_INVALID, "cutoff must be 0.001 .. 30 A");
+        const long long C = std::llrint(scaled);
+        if (C < 1 || C > 30000) throw ld::Error(LD_ERR_INVALID, "cutoff must be 0.001 .. 30 A");
+        if (n == 0) return;
+        ld::check_poses(n, poses, stride, c->pose_len());
+        const ld::ContactsDevice &k = c->contacts;
+        const size_t rw = ((size_t)k.n_rec_res + 31) / 32, lw = ((size_t)k.n_lig_res + 31) / 32;
+        if (rw + lw > ld::kMaxContactWords) throw ld::Error(LD_ERR_INVALID, "more than 524288 residues");
+        // a workspace slot a workgroup in flight: the atoms, and the boxes when LDS does not hold them
+        const size_t per_slot = (size_t)k.n_atoms * sizeof(int4) + (k.boxes_in_lds ? 0 : k.box_bytes());
+        const size_t slots = std::min(n, std::min<size_t>(ld::kContactSlots, std::max<size_t>(1, ld::kClusterWorkspaceBytes / per_slot)));
+        const size_t lds = (rw + lw) * sizeof(uint32_t) + (k.boxes_in_lds ? k.box_bytes() : 0);
+        hipStream_t st = c->stream;
+        c->upload_poses(n, poses, stride);
+        c->d_ids.reserve(n * (rw + lw) * sizeof(uint32_t) + sizeof(int));
+        uint32_t *d_rec = static_cast<uint32_t *>(c->d_ids.ptr);
+        uint32_t *d_lig = d_rec + n * rw;
+        int *d_overflow = reinterpret_cast<int *>(d_lig + n * lw);
+        ld::hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), st), "hipMemset");
+        c->d_ws.reserve(slots * per_slot);
+        int4 *d_atoms = static_cast<int4 *>(c->d_ws.ptr);
+        ld::hip_check(hipEventRecord(c->ev0, st), "hipEventRecord");
+        hipLaunchKernelGGL(ld::complex_contacts, dim3((unsigned)slots), dim3(ld::kContactThreads), lds, st, c->dev, k,
+                           static_cast<const double *>(c->d_poses.ptr), stride, n, (uint32_t)(C * C), d_atoms,
+                           reinterpret_cast<int *>(d_atoms + slots * k.n_atoms), d_rec, d_lig, d_overflow);
+        ld::hip_check(hipGetLastError(), "complex_contacts launch");
+        ld::hip_check(hipEventRecord(c->ev1, st), "hipEventRecord");
+        int overflow = 0;
+        ld::hip_check(hipMemcpyAsync(&overflow, d_overflow, sizeof(int), hipMemcpyDeviceToHost, st), "hipMemcpy D2H");
+        ld::hip_check(hipStreamSynchronize(st), "complex_contacts");
+        if (overflow) throw ld::Error(LD_ERR_INVALID, "a posed coordinate is beyond +-1.0e6 A");
+        float ms = 0.0f;
+        ld::hip_check(hipEventElapsedTime(&ms, c->ev0, c->ev1), "hipEventElapsedTime");
+        c->last_kernel_ms = ms;
+        if (rec_bits) ld::hip_check(hipMemcpy(rec_bits, d_rec, n * rw * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
+        if (lig_bits) ld::hip_check(hipMemcpy(lig_bits, d_lig, n * lw * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
     });
 }
 
