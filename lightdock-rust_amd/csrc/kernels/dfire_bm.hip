@@ -43,7 +43,7 @@ constexpr float kBmBoxCut = kBmBoxCutUnits2;  // (8 * 15 A)^2 in record units, p
 // {-hi, lo} the two differences of an axis' gap -- lo_r - hi_l and lo_l - hi_r, the values axis_gap forms -- are ONE packed add.
 struct alignas(16) BmCullBox {
     v2f x, y, z;
-    float cut, unused;   // the subtile's reach, squared (kBmBoxCut unless its atoms' rows of the potential are zero: scorer.cpp, build_bm)
+    float cut, unused;   // the subtile's reach, squared (kBmBoxCut unless its atoms' rows of the potential are zero: scorer.cpp, bm_box_reaches)
 };
 static_assert(sizeof(BmCullBox) == sizeof(TiledBox), "same room in LDS");
 __device__ __forceinline__ float bm_cull_gap2(v2f lx, v2f ly, v2f lz, const BmCullBox &r) {   // = box_gap2, bit for bit

@@ -317,37 +317,25 @@ Scorer::Scorer(const ld_scorer_desc &desc) {
         // LIGHTDOCK_DFIRE_KERNEL: "bm" (and any other value, the default): the block-major path (kernels/dfire_bm.hpp; its ANM
         // form for molecules that flex); "packed": the pose-major kernel for everything (what LIGHTDOCK_TILED_LATENCY=1, the
         // single-swarm CLI, and the complexes BlockMajorPath::build declines use anyway); "allpairs": no culling (what the receptors
-        // build_packed declines use too)
+        // packed_accepts declines use too, whatever the block-major path would say)
         const char *env = std::getenv("LIGHTDOCK_DFIRE_KERNEL");
         const std::string kernel = env ? env : "";
         const char *latency_env = std::getenv("LIGHTDOCK_TILED_LATENCY");
         const bool latency = latency_env && std::atoi(latency_env) > 0;
-        if (kernel != "allpairs") {
-            build_tile_order(desc, latency);
-            if (build_packed(desc)) {
-                route_ = PairRoute::packed;
-                if (kernel != "packed" && (kernel == "bm" || !latency)) {
-                    BmInputs in(desc, tiled_rec_soa_, tiled_lig_soa_, type_perm_rec_, type_perm_lig_);
-                    in.tiled_lig = tiled_lig_;
-                    in.tiled_table = tiled_table_;
-                    in.zero_bins = packed_zero_bins_;
-                    in.rec_flag_words = pair_.rec.flag_words;
-                    in.iface_d2 = pair_.iface_d2;
-                    in.use_anm = use_anm_;
-                    in.n_cus = n_cus_;
-                    in.prepare = packed_prepare_launch(nullptr, 0, nullptr, 1);
-                    in.stream = stream_;
-                    bm_ = BlockMajorPath::build(in);
-                    if (bm_) route_ = PairRoute::block_major;
-                }
-            }
+        PackedFrame frame;
+        if (kernel != "allpairs") build_tiles(desc);
+        if (kernel != "allpairs" && packed_accepts(desc.receptor, &frame)) {   // choose first, then build the one route that runs
+            const RouteInputs in{desc, tiles_, pair_.rec.flag_words, pair_.bin_step, pair_.iface_d2, use_anm_, latency, n_cus_, stream_};
+            if (kernel != "packed" && (kernel == "bm" || !latency)) bm_ = BlockMajorPath::build(in);
+            if (!bm_) packed_.reset(new PackedPath(in, frame));
+            route_ = bm_ ? PairRoute::block_major : PairRoute::packed;
         }
     }
 }
 
 // Tile-ordered SoA copy of one molecule (host/spatial_order.hpp); padding atoms at -1e30
 // (receptor) / +1e30 (ligand) so that no padding/padding pair can ever look close.
-void Scorer::upload_tiled_molecule(const ld_molecule &m, bool is_receptor, TiledSoA &out) {
+void Scorer::upload_tiled_molecule(const ld_molecule &m, bool is_receptor, TiledSoA &out, std::vector<uint32_t> &perm) {
     const size_t n = m.n_atoms;
     const DfireTileLayout layout = dfire_tile_layout(m.coordinates, m.dfire_types, n);
     const std::vector<uint32_t> &order = layout.order;
@@ -358,7 +346,6 @@ void Scorer::upload_tiled_molecule(const ld_molecule &m, bool is_receptor, Tiled
     std::vector<int32_t> slot(np, -1);
     const std::vector<int32_t> &hslot = is_receptor ? host_slot_rec_ : host_slot_lig_;
     // type numbers as the patch layout of the potential wants them (bonded atoms paired up)
-    std::vector<uint32_t> &perm = is_receptor ? type_perm_rec_ : type_perm_lig_;
     perm = layout.type_perm;
     for (size_t i = 0; i < np; i++) {
         const uint32_t a = order[i];
@@ -401,45 +388,83 @@ void Scorer::upload_tiled_molecule(const ld_molecule &m, bool is_receptor, Tiled
     }
 }
 
-// What the pose-major and block-major paths share: both molecules in tile order, the potential in patches, the ligand
-// as the kernels read it, and the pose-major kernel's split.
-void Scorer::build_tile_order(const ld_scorer_desc &desc, bool latency) {
-    upload_tiled_molecule(desc.receptor, true, tiled_rec_soa_);
-    upload_tiled_molecule(desc.ligand, false, tiled_lig_soa_);
-    const TiledSoA &lig = tiled_lig_soa_;
-    tiled_lig_.n_real = lig.n_real;
-    tiled_lig_.n_tiles = lig.n_tiles;
-    tiled_lig_.x = lig.x;
-    tiled_lig_.y = lig.y;
-    tiled_lig_.z = lig.z;
-    tiled_lig_.tindex = lig.tindex;
-    tiled_lig_.slot = lig.slot;
-    tiled_lig_.num_anm = lig.num_anm;
-    tiled_lig_.modes = lig.modes;
-    tiled_lig_.flag_words = pair_.lig.flag_words;
+// What the pose-major and block-major paths share: both molecules in tile order, the ligand as the kernels read it, the
+// potential in patches, the bins that are zero for the whole complex.
+void Scorer::build_tiles(const ld_scorer_desc &desc) {
+    DfireTiles &T = tiles_;
+    upload_tiled_molecule(desc.receptor, true, T.rec, T.type_perm_rec);
+    upload_tiled_molecule(desc.ligand, false, T.lig, T.type_perm_lig);
+    const TiledSoA &lig = T.lig;
+    T.lig_view.n_real = lig.n_real;
+    T.lig_view.n_tiles = lig.n_tiles;
+    T.lig_view.x = lig.x;
+    T.lig_view.y = lig.y;
+    T.lig_view.z = lig.z;
+    T.lig_view.tindex = lig.tindex;
+    T.lig_view.slot = lig.slot;
+    T.lig_view.num_anm = lig.num_anm;
+    T.lig_view.modes = lig.modes;
+    T.lig_view.flag_words = pair_.lig.flag_words;
     {   // potential re-laid out in 2 x 2 x 4 patches, see dfire_tiled.hpp
         std::vector<double> t2(kTiledTableDoubles, 0.0);
         for (uint32_t l = 0; l < 168; l++)
             for (uint32_t b = 0; b < kTiledTableBins; b++)
                 for (uint32_t r = 0; r < 168; r++)
-                    t2[(tiled_lig_term(type_perm_lig_[l]) + tiled_rec_term(type_perm_rec_[r]) + tiled_bin_term(b)) / 8] =
+                    t2[(tiled_lig_term(T.type_perm_lig[l]) + tiled_rec_term(T.type_perm_rec[r]) + tiled_bin_term(b)) / 8] =
                         desc.potential[(size_t)r * kDfireRowStride + l * 20 + b];
-        tiled_table_ = arena_.upload(t2);
+        T.table = arena_.upload(t2);
     }
-    // `split` waves share one ligand tile, each taking every split-th surviving receptor tile.
-    // With thousands of poses per launch there are enough waves anyway and split = 1 is best or
-    // equal (measured on MI355X at 16 384+ poses: 2uuy, 7 ligand tiles, +12 % over split 3; 1k4c,
-    // 52 tiles, +11 %; 1ppe, 4 tiles, +5 % with the packed kernel).  A launch of one swarm (200 poses) of a small ligand
-    // does not fill the GPU: split 3 halves its latency on 1ppe.  The split is fixed per scorer (a
-    // pose's energy must not depend on the batch it travels in), so the default serves
-    // throughput and LIGHTDOCK_TILED_LATENCY=1 -- set by the single-swarm CLI -- serves latency.
-    int split = latency && tiled_lig_.n_tiles < 32 ? 3 : 1;
-    if (const char *e = std::getenv("LIGHTDOCK_TILED_SPLIT")) {
-        int v = std::atoi(e);
-        if (v >= 1 && v <= 8) split = v;
+    // bins in which this complex's potential is zero throughout (bin 20 = the read past the row at r = 15.0)
+    const char *e = std::getenv("LIGHTDOCK_PACKED_ELIDE_ZERO_BINS");
+    if (e && std::strcmp(e, "0") == 0) return;
+    std::vector<char> rec_has(169, 0), lig_has(169, 0);
+    for (size_t i = 0; i < desc.receptor.n_atoms; i++) rec_has[desc.receptor.dfire_types[i]] = 1;
+    for (size_t i = 0; i < desc.ligand.n_atoms; i++) lig_has[desc.ligand.dfire_types[i]] = 1;
+    for (uint32_t b = 0; b <= 20; b++) {
+        bool all_zero = true;
+        for (uint32_t r = 0; r < 169 && all_zero; r++)
+            for (uint32_t l = 0; l < 169 && all_zero; l++)
+                if (rec_has[r] && lig_has[l] && (size_t)r * kDfireRowStride + l * 20 + b < LD_DFIRE_TABLE_LEN &&
+                    desc.potential[(size_t)r * kDfireRowStride + l * 20 + b] != 0.0)
+                    all_zero = false;
+        if (all_zero) T.zero_bins |= 1u << b;
     }
-    tiled_split_ = split;
-    rec_anm_per_pose_ = use_anm_ && tiled_rec_soa_.num_anm > 0;
+}
+
+PackedPrepareLaunch DfireTiles::prepare(const double centre[3], double kappa, double ubound) const {
+    PackedPrepareLaunch p;
+    p.n_real = rec.n_real;
+    p.n_tiles = rec.n_tiles;
+    p.x = rec.x;
+    p.y = rec.y;
+    p.z = rec.z;
+    p.tindex = rec.tindex;
+    p.slot = rec.slot;
+    p.num_anm = rec.num_anm;
+    p.modes = rec.modes;
+    p.cx = centre[0];
+    p.cy = centre[1];
+    p.cz = centre[2];
+    p.kappa = kappa;
+    p.ubound = (float)ubound;
+    return p;
+}
+
+ReceptorImage DfireTiles::static_image(DeviceArena &arena, const double centre[3], double kappa, double ubound, hipStream_t stream) const {
+    const size_t pad = (size_t)rec.n_tiles * 64;
+    ReceptorImage image;
+    image.pairs = static_cast<PackedRecPair *>(arena.alloc_bytes(pad / 2 * sizeof(PackedRecPair)));
+    image.sub = static_cast<TiledBox *>(arena.alloc_bytes(pad / 8 * sizeof(TiledBox)));
+    image.tile = static_cast<TiledBox *>(arena.alloc_bytes(pad / 64 * sizeof(TiledBox)));
+    PackedPrepareLaunch p = prepare(centre, kappa, ubound);
+    p.num_anm = 0;
+    p.n_poses = 1;
+    p.pairs_out = image.pairs;
+    p.sub_out = image.sub;
+    p.tile_out = image.tile;
+    hip_check(launch_packed_prepare(p, stream), "launch dfire_packed_prepare");
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    return image;
 }
 
 // The centre and the largest half extent of the receptor's bounding box: the f32 record frames.
@@ -538,92 +563,133 @@ std::vector<uint32_t> build_packed_lut(int sc, double eps, uint32_t zero_bins) {
     return words;
 }
 
-// The default DFIRE kernel: f32 records in a frame centred on the receptor, the cell LUT of
-// kernels/dfire_packed.hpp (every cell that cannot decide the reference's f64 result is flagged),
-// and the receptor image as pair records.
-bool Scorer::build_packed(const ld_scorer_desc &desc) {
-    double centre[3], half;
-    frame_of_receptor(desc.receptor, centre, &half);
+// LIGHTDOCK_PACKED_EPS_SCALE, a test hook: widens the error bound either culled route builds its LUT for (results must not depend on it)
+static double eps_scale_hook() {
+    const char *e = std::getenv("LIGHTDOCK_PACKED_EPS_SCALE");
+    const double f = e ? std::atof(e) : 1.0;
+    return f >= 1.0 && f <= 1000.0 ? f : 1.0;
+}
+
+// ---------------------------------------------------------------------------------------
+// Pose-major packed DFIRE path (kernels/dfire_packed.hpp): f32 records in a frame centred on the receptor, the cell LUT
+// (every cell that cannot decide the reference's f64 result is flagged), and the receptor image as pair records.
+// ---------------------------------------------------------------------------------------
+bool packed_accepts(const ld_molecule &receptor, PackedFrame *out) {
+    double half;
+    frame_of_receptor(receptor, out->centre, &half);
     // LUT cells per unit of 4 d2: 2 halves the share of pairs in flagged cells for 4 KiB more LDS
-    int sc = kPackedWaves == 1 ? 1 : 2;  // one-wave workgroups: the LUT is per wave, the smaller one keeps 6 waves per SIMD
-    if (const char *e = std::getenv("LIGHTDOCK_PACKED_CELLS")) sc = std::atoi(e) == 1 ? 1 : 2;
-    const double kappa = 2.0 * std::sqrt((double)sc);
+    out->cells = kPackedWaves == 1 ? 1 : 2;  // one-wave workgroups: the LUT is per wave, the smaller one keeps 6 waves per SIMD
+    if (const char *e = std::getenv("LIGHTDOCK_PACKED_CELLS")) out->cells = std::atoi(e) == 1 ? 1 : 2;
+    out->kappa = 2.0 * std::sqrt((double)out->cells);
     // records hold kappa (x - c); room for the cutoff and for ANM deformations (32 A), rounded up to a power of two
-    double ubound = 128.0;
-    while (ubound < kappa * (half + 32.0)) ubound *= 2.0;
-    double eps = dfire_f32_error_bound(ubound, sc);  // units of 4 d2
-    if (const char *e = std::getenv("LIGHTDOCK_PACKED_EPS_SCALE")) {  // test hook: results must not depend on it
-        const double f = std::atof(e);
-        if (f >= 1.0 && f <= 1000.0) eps *= f;
+    out->ubound = 128.0;
+    while (out->ubound < out->kappa * (half + 32.0)) out->ubound *= 2.0;
+    out->eps = dfire_f32_error_bound(out->ubound, out->cells) * eps_scale_hook();  // units of 4 d2
+    return out->eps * out->cells < 0.2;  // false: a receptor thousands of angstroms across -- the all-pairs kernel, all f64
+}
+
+PackedPath::PackedPath(const RouteInputs &in, const PackedFrame &frame) : tiles_(in.tiles) {
+    const DfireTiles &T = in.tiles;
+    PackedLaunch &P = model_;
+    P.lig = T.lig_view;
+    P.use_anm = in.use_anm ? 1 : 0;
+    P.anm_rec = T.rec.num_anm;
+    P.cx = frame.centre[0];
+    P.cy = frame.centre[1];
+    P.cz = frame.centre[2];
+    P.kappa = frame.kappa;
+    P.cells_per_unit = frame.cells;
+    P.ubound = (float)frame.ubound;
+    P.eps = std::nextafter((float)frame.eps, INFINITY);
+    P.table = T.table;
+    P.bin_step = in.bin_step;
+    P.iface_scaled = 4.0 * in.iface_d2;
+    P.lut = arena_.upload(build_packed_lut(frame.cells, (double)P.eps, T.zero_bins));
+    lut_full_ = T.zero_bins ? arena_.upload(build_packed_lut(frame.cells, (double)P.eps, 0)) : P.lut;  // counting launches count every pair
+
+    // `split` waves share one ligand tile, each taking every split-th surviving receptor tile.
+    // With thousands of poses per launch there are enough waves anyway and split = 1 is best or
+    // equal (measured on MI355X at 16 384+ poses: 2uuy, 7 ligand tiles, +12 % over split 3; 1k4c,
+    // 52 tiles, +11 %; 1ppe, 4 tiles, +5 % with the packed kernel).  A launch of one swarm (200 poses) of a small ligand
+    // does not fill the GPU: split 3 halves its latency on 1ppe.  The split is fixed per scorer (a
+    // pose's energy must not depend on the batch it travels in), so the default serves
+    // throughput and LIGHTDOCK_TILED_LATENCY=1 -- set by the single-swarm CLI -- serves latency.
+    P.split = in.latency && P.lig.n_tiles < 32 ? 3 : 1;
+    if (const char *e = std::getenv("LIGHTDOCK_TILED_SPLIT")) {
+        int v = std::atoi(e);
+        if (v >= 1 && v <= 8) P.split = v;
     }
-    if (!(eps * sc < 0.2)) return false;  // a receptor thousands of angstroms across: the all-pairs kernel, all f64
-
-    PackedLaunch &P = packed_;
-    P.lig = tiled_lig_;
-    P.use_anm = use_anm_ ? 1 : 0;
-    P.anm_rec = (int)anm_rec();
-    P.cx = centre[0];
-    P.cy = centre[1];
-    P.cz = centre[2];
-    P.kappa = kappa;
-    P.cells_per_unit = sc;
-    P.ubound = (float)ubound;
-    P.eps = std::nextafter((float)eps, INFINITY);
-    P.table = tiled_table_;
-    P.bin_step = pair_.bin_step;
-    P.iface_scaled = 4.0 * pair_.iface_d2;
-
-    // bins in which this complex's potential is zero throughout (bin 20 = the read past the row at r = 15.0)
-    uint32_t zero_bins = 0;
-    {
-        const char *e = std::getenv("LIGHTDOCK_PACKED_ELIDE_ZERO_BINS");
-        if (!(e && std::strcmp(e, "0") == 0)) {
-            std::vector<char> rec_has(169, 0), lig_has(169, 0);
-            for (size_t i = 0; i < desc.receptor.n_atoms; i++) rec_has[desc.receptor.dfire_types[i]] = 1;
-            for (size_t i = 0; i < desc.ligand.n_atoms; i++) lig_has[desc.ligand.dfire_types[i]] = 1;
-            for (uint32_t b = 0; b <= 20; b++) {
-                bool all_zero = true;
-                for (uint32_t r = 0; r < 169 && all_zero; r++)
-                    for (uint32_t l = 0; l < 169 && all_zero; l++)
-                        if (rec_has[r] && lig_has[l] && (size_t)r * kDfireRowStride + l * 20 + b < LD_DFIRE_TABLE_LEN &&
-                            desc.potential[(size_t)r * kDfireRowStride + l * 20 + b] != 0.0)
-                            all_zero = false;
-                if (all_zero) zero_bins |= 1u << b;
-            }
-        }
-    }
-    packed_zero_bins_ = zero_bins;
-    P.lut = arena_.upload(build_packed_lut(sc, (double)P.eps, zero_bins));
-    packed_lut_full_ = zero_bins ? arena_.upload(build_packed_lut(sc, (double)P.eps, 0)) : P.lut;  // counting launches count every pair
-
-    P.split = tiled_split_;
     P.n_groups = (P.lig.n_tiles * P.split + kPackedWaves - 1) / kPackedWaves;
 
-    P.rec.n_real = tiled_rec_soa_.n_real;
-    P.rec.n_tiles = tiled_rec_soa_.n_tiles;
-    P.rec.flag_words = pair_.rec.flag_words;
-    P.rec.slot = tiled_rec_soa_.slot;
-    P.rec.tindex = tiled_rec_soa_.tindex;
-    if (!rec_anm_per_pose_) {
-        const size_t pad = (size_t)P.rec.n_tiles * 64;
-        PackedRecPair *pairs = static_cast<PackedRecPair *>(arena_.alloc_bytes(pad / 2 * sizeof(PackedRecPair)));
-        TiledBox *sub = static_cast<TiledBox *>(arena_.alloc_bytes(pad / 8 * sizeof(TiledBox)));
-        TiledBox *tile = static_cast<TiledBox *>(arena_.alloc_bytes(pad / 64 * sizeof(TiledBox)));
-        PackedPrepareLaunch p = packed_prepare_launch(nullptr, 0, nullptr, 1);
-        p.num_anm = 0;
-        p.pairs_out = pairs;
-        p.sub_out = sub;
-        p.tile_out = tile;
-        hip_check(launch_packed_prepare(p, stream_), "launch dfire_packed_prepare");
-        hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        P.rec.pairs = pairs;
-        P.rec.sub_boxes = sub;
-        P.rec.tile_boxes = tile;
+    P.rec.n_real = T.rec.n_real;
+    P.rec.n_tiles = T.rec.n_tiles;
+    P.rec.flag_words = in.rec_flag_words;
+    P.rec.slot = T.rec.slot;
+    P.rec.tindex = T.rec.tindex;
+    P.rec.x = T.rec.x;  // undeformed; the exact path applies the modes of a per-pose image itself
+    P.rec.y = T.rec.y;
+    P.rec.z = T.rec.z;
+    image_per_pose_ = T.rec.num_anm > 0;
+    if (!image_per_pose_) {
+        const ReceptorImage image = T.static_image(arena_, frame.centre, frame.kappa, frame.ubound, in.stream);
+        P.rec.pairs = image.pairs;
+        P.rec.sub_boxes = image.sub;
+        P.rec.tile_boxes = image.tile;
     }
-    P.rec.x = tiled_rec_soa_.x;  // undeformed; the exact path applies the modes of a per-pose image itself
-    P.rec.y = tiled_rec_soa_.y;
-    P.rec.z = tiled_rec_soa_.z;
-    return true;
+}
+
+size_t PackedPath::max_batch() const {
+    if (!image_per_pose_) return std::numeric_limits<size_t>::max();
+    const size_t pad = (size_t)model_.rec.n_tiles * 64;
+    const size_t per_pose = pad / 2 * sizeof(PackedRecPair) + (pad / 8 + pad / 64) * sizeof(TiledBox);
+    static const size_t cap = [] {  // LIGHTDOCK_RECEPTOR_IMAGE_MIB: test hook for the slicing
+        const char *e = std::getenv("LIGHTDOCK_RECEPTOR_IMAGE_MIB");
+        const long v = e ? std::atol(e) : 0;
+        return v > 0 ? size_t(v) << 20 : size_t(8) << 30;
+    }();
+    return std::max<size_t>(1, cap / per_pose);
+}
+
+void PackedPath::run(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, const uint32_t *d_list, const uint32_t *d_count,
+                     const PoseOutputs &out, hipStream_t stream) {
+    PackedLaunch t = model_;
+    t.poses = d_poses;
+    t.stride = stride;
+    t.active = d_list ? nullptr : d_active;  // the list holds exactly the active rows
+    t.pose_list = d_list;
+    t.pose_count = d_list ? d_count : nullptr;
+    t.n_poses = n;
+    t.partial = out.partial;
+    t.flags = out.flags;
+    t.count_partial = out.count_partial;
+    t.tested_partial = out.tested_partial;
+    t.exact_partial = out.exact_partial;
+    if (out.count_partial) t.lut = lut_full_;
+    if (image_per_pose_) {  // one deformed receptor image per pose (src/dfire.rs:304-320)
+        const size_t pad = (size_t)t.rec.n_tiles * 64;
+        ws_rec_pairs_.reserve(n * (pad / 2) * sizeof(PackedRecPair));
+        ws_rec_sub_.reserve(n * (pad / 8) * sizeof(TiledBox));
+        ws_rec_tile_.reserve(n * (pad / 64) * sizeof(TiledBox));
+        const double centre[3] = {t.cx, t.cy, t.cz};
+        PackedPrepareLaunch pr = tiles_.prepare(centre, t.kappa, t.ubound);
+        pr.poses = d_poses;
+        pr.stride = stride;
+        pr.active = d_active;
+        pr.n_poses = n;
+        pr.pairs_out = static_cast<PackedRecPair *>(ws_rec_pairs_.ptr);
+        pr.sub_out = static_cast<TiledBox *>(ws_rec_sub_.ptr);
+        pr.tile_out = static_cast<TiledBox *>(ws_rec_tile_.ptr);
+        hip_check(launch_packed_prepare(pr, stream), "launch dfire_packed_prepare");
+        t.rec.pairs = pr.pairs_out;
+        t.rec.sub_boxes = pr.sub_out;
+        t.rec.tile_boxes = pr.tile_out;
+        t.rec.modes = pr.modes;
+        t.rec.num_anm = pr.num_anm;
+        t.rec.pose_stride_pairs = pad / 2;
+        t.rec.pose_stride_sub = pad / 8;
+        t.rec.pose_stride_tile = pad / 64;
+    }
+    hip_check(launch_dfire_packed(t, stream), "launch dfire_packed_pairs");
 }
 
 // ---------------------------------------------------------------------------------------
@@ -852,7 +918,7 @@ static size_t bm_pass_size(size_t tile_pairs) {
 
 // Does the block-major path take this complex?  Every reason for declining, before anything is uploaded or launched; what the
 // decision derived on the way (frame, error bound, tile spheres, fixed-point scale, pass size) goes to `out`.
-static bool bm_accepts(const BmInputs &in, BmFrame *out) {
+static bool bm_accepts(const RouteInputs &in, BmFrame *out) {
 #ifdef LD_DIAG_BUILD
     // (diagnostic builds only, tools/build_variant.sh -- LIGHTDOCK_BM_DIAG_IGNORE_ANM=1: timing experiments, the block-major kernels
     // on an ANM complex as if it were rigid, wrong sums.  The shipped library does not read the variable.)
@@ -862,7 +928,7 @@ static bool bm_accepts(const BmInputs &in, BmFrame *out) {
     constexpr bool diag_rigid = false;
 #endif
     const ld_scorer_desc &desc = in.desc;
-    const TiledSoA &rec = in.rec, &lig = in.lig;
+    const TiledSoA &rec = in.tiles.rec, &lig = in.tiles.lig;
     // Molecules that flex per pose (src/dfire.rs:288-320): the ANM form of the kernels, for up to kBmMaxModes modes a molecule (more:
     // the pose-major kernel -- a stated contract, tests/test_gpu_parity.py::test_which_kernel_a_flexing_complex_gets).  The
     // fixed-point scale's reach count allows for the deformation below (until round 6 a receptor of 8192 atoms or more was declined
@@ -891,11 +957,7 @@ static bool bm_accepts(const BmInputs &in, BmFrame *out) {
     while (ubound < kBmKappa * (half + 16.5) + (anm ? (double)kBmWildUnits : 0.0)) ubound *= 2.0;
     double extent = 0.0;
     for (size_t i = 0; i < desc.ligand.n_atoms * 3; i++) extent = std::max(extent, std::fabs(desc.ligand.coordinates[i]));
-    double eps = dfire_bm_error_bound(ubound, extent, anm);  // LUT cells
-    if (const char *e = std::getenv("LIGHTDOCK_PACKED_EPS_SCALE")) {  // test hook: results must not depend on it
-        const double f = std::atof(e);
-        if (f >= 1.0 && f <= 1000.0) eps *= f;
-    }
+    const double eps = dfire_bm_error_bound(ubound, extent, anm) * eps_scale_hook();  // LUT cells
     if (!(eps < 8.0)) return false;  // a complex thousands of angstroms across: the pose-major kernels
     out->anm = anm;
     out->ubound = ubound;
@@ -1094,46 +1156,30 @@ static void bm_fixed_rows(const double *potential, double fix_scale, std::vector
 
 // ---- (c) the object: the one device round trip, then every upload --------------------------------------------------------
 
-std::unique_ptr<BlockMajorPath> BlockMajorPath::build(const BmInputs &in) {
+std::unique_ptr<BlockMajorPath> BlockMajorPath::build(const RouteInputs &in) {
     BmFrame frame;
     if (!bm_accepts(in, &frame)) return nullptr;
     return std::unique_ptr<BlockMajorPath>(new BlockMajorPath(in, frame));
 }
 
-BlockMajorPath::BlockMajorPath(const BmInputs &in, const BmFrame &frame) {
-    const TiledSoA &rec = in.rec, &lig = in.lig;
+BlockMajorPath::BlockMajorPath(const RouteInputs &in, const BmFrame &frame) {
+    const TiledSoA &rec = in.tiles.rec, &lig = in.tiles.lig;
     const size_t pad = (size_t)rec.n_tiles * 64;
     n_cus_ = in.n_cus;
     chunk_ = frame.chunk;
 
     // THE DEVICE ROUND TRIP: the receptor image in this frame (kappa = 8) by the kernel that builds the packed kernel's, read back
     // for the operands and reaches that are formed from it on the host; the boxes return with their reach words.
-    PackedRecPair *pairs = static_cast<PackedRecPair *>(arena_.alloc_bytes(pad / 2 * sizeof(PackedRecPair)));
-    TiledBox *sub = static_cast<TiledBox *>(arena_.alloc_bytes(pad / 8 * sizeof(TiledBox)));
-    TiledBox *tile = static_cast<TiledBox *>(arena_.alloc_bytes(pad / 64 * sizeof(TiledBox)));
+    const ReceptorImage image = in.tiles.static_image(arena_, frame.centre, kBmKappa, frame.ubound, in.stream);
     std::vector<PackedRecPair> hp(pad / 2);
     std::vector<TiledBox> hb(pad / 8), ht(pad / 64);
-    {
-        PackedPrepareLaunch p = in.prepare;
-        p.num_anm = 0;
-        p.cx = frame.centre[0];
-        p.cy = frame.centre[1];
-        p.cz = frame.centre[2];
-        p.kappa = kBmKappa;
-        p.ubound = (float)frame.ubound;
-        p.pairs_out = pairs;
-        p.sub_out = sub;
-        p.tile_out = tile;
-        hip_check(launch_packed_prepare(p, in.stream), "launch dfire_packed_prepare");
-        hip_check(hipStreamSynchronize(in.stream), "hipStreamSynchronize");
-        hip_check(hipMemcpy(hp.data(), pairs, hp.size() * sizeof(PackedRecPair), hipMemcpyDeviceToHost), "D2H receptor records");
-        hip_check(hipMemcpy(hb.data(), sub, hb.size() * sizeof(TiledBox), hipMemcpyDeviceToHost), "D2H receptor boxes");
-        hip_check(hipMemcpy(ht.data(), tile, ht.size() * sizeof(TiledBox), hipMemcpyDeviceToHost), "D2H receptor tile boxes");
-    }
+    hip_check(hipMemcpy(hp.data(), image.pairs, hp.size() * sizeof(PackedRecPair), hipMemcpyDeviceToHost), "D2H receptor records");
+    hip_check(hipMemcpy(hb.data(), image.sub, hb.size() * sizeof(TiledBox), hipMemcpyDeviceToHost), "D2H receptor boxes");
+    hip_check(hipMemcpy(ht.data(), image.tile, ht.size() * sizeof(TiledBox), hipMemcpyDeviceToHost), "D2H receptor tile boxes");
     const std::vector<float> ops = bm_rec_ops(hp, hb);
     quiet_subtiles_ = bm_box_reaches(in.desc, rec, lig, hb, ht);
-    hip_check(hipMemcpy(sub, hb.data(), hb.size() * sizeof(TiledBox), hipMemcpyHostToDevice), "H2D receptor boxes");
-    hip_check(hipMemcpy(tile, ht.data(), ht.size() * sizeof(TiledBox), hipMemcpyHostToDevice), "H2D receptor tile boxes");
+    hip_check(hipMemcpy(image.sub, hb.data(), hb.size() * sizeof(TiledBox), hipMemcpyHostToDevice), "H2D receptor boxes");
+    hip_check(hipMemcpy(image.tile, ht.data(), ht.size() * sizeof(TiledBox), hipMemcpyHostToDevice), "H2D receptor tile boxes");
 
     // the model: what the scorer shares, then this path's own tables
     BmModel &M = model_;
@@ -1145,18 +1191,18 @@ BlockMajorPath::BlockMajorPath(const BmInputs &in, const BmFrame &frame) {
     M.rec_tindex = rec.tindex;
     M.rec_slot = rec.slot;
     M.rec_flag_words = in.rec_flag_words;
-    M.lig = in.tiled_lig;
+    M.lig = in.tiles.lig_view;
     M.cx = frame.centre[0];
     M.cy = frame.centre[1];
     M.cz = frame.centre[2];
     M.ubound = (float)frame.ubound;
     M.box_pad = std::nextafter((float)(2.0 * dfire_bm_pose_error(frame.ubound, frame.extent, frame.anm)), INFINITY);
-    M.table = in.tiled_table;
+    M.table = in.tiles.table;
     M.iface_scaled = 4.0 * in.iface_d2;
     M.fix_scale = frame.fix_scale;
-    M.rec_pairs = pairs;
-    M.rec_sub = sub;
-    M.rec_tile = tile;
+    M.rec_pairs = image.pairs;
+    M.rec_sub = image.sub;
+    M.rec_tile = image.tile;
     M.rec_ops = arena_.upload(ops);
     {
         const DfireBinning b = build_dfire_binning();
@@ -1164,8 +1210,8 @@ BlockMajorPath::BlockMajorPath(const BmInputs &in, const BmFrame &frame) {
         for (double &v : step4) v *= 4.0;
         M.bin_step = arena_.upload(step4);
     }
-    M.lut = arena_.upload(build_bm_lut(frame.eps, in.zero_bins));
-    M.lut_full = in.zero_bins ? arena_.upload(build_bm_lut(frame.eps, 0)) : M.lut;  // counting launches count every pair
+    M.lut = arena_.upload(build_bm_lut(frame.eps, in.tiles.zero_bins));
+    M.lut_full = in.tiles.zero_bins ? arena_.upload(build_bm_lut(frame.eps, 0)) : M.lut;  // counting launches count every pair
     M.rec_sub_tracked = arena_.upload(bm_tracked_subtiles(rec));
     M.lig_sub_tracked = arena_.upload(bm_tracked_subtiles(lig));
     if (frame.anm) {
@@ -1187,8 +1233,8 @@ BlockMajorPath::BlockMajorPath(const BmInputs &in, const BmFrame &frame) {
     M.rec_rowoff = arena_.upload(bm_type_offsets(rec, (uint32_t)kBmRowBytes));
     M.lig_rowbase = arena_.upload(bm_type_offsets(lig, (uint32_t)(kBmTypes * kBmRowBytes)));
     M.lig_local = arena_.upload(bm_lig_local(lig));
-    M.lig_exact = arena_.upload(bm_exact_rows(lig, in.type_perm_lig, false));
-    M.rec_exact = arena_.upload(bm_exact_rows(rec, in.type_perm_rec, true));
+    M.lig_exact = arena_.upload(bm_exact_rows(lig, in.tiles.type_perm_lig, false));
+    M.rec_exact = arena_.upload(bm_exact_rows(rec, in.tiles.type_perm_rec, true));
     M.lig_tile_sphere = arena_.upload(frame.tile_sphere);
     {
         std::vector<long long> rows, ones;
@@ -1240,7 +1286,7 @@ BmShape BlockMajorPath::shape(size_t n, bool counts, bool debug) const {
 }
 
 void BlockMajorPath::run(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, const uint32_t *d_list, const uint32_t *d_count,
-                         const Outputs &out, hipStream_t stream) {
+                         const PoseOutputs &out, hipStream_t stream) {
     const bool counts = out.count_partial != nullptr;
     const char *dbg = std::getenv("LIGHTDOCK_BM_DEBUG");
     const BmShape s = shape(n, counts, dbg != nullptr);
@@ -1312,29 +1358,6 @@ void BlockMajorPath::run(size_t n, const double *d_poses, size_t stride, const u
     }
 }
 
-PackedPrepareLaunch Scorer::packed_prepare_launch(const double *poses, size_t stride, const uint8_t *active, size_t n) const {
-    PackedPrepareLaunch p;
-    p.n_real = tiled_rec_soa_.n_real;
-    p.n_tiles = tiled_rec_soa_.n_tiles;
-    p.x = tiled_rec_soa_.x;
-    p.y = tiled_rec_soa_.y;
-    p.z = tiled_rec_soa_.z;
-    p.tindex = tiled_rec_soa_.tindex;
-    p.slot = tiled_rec_soa_.slot;
-    p.num_anm = tiled_rec_soa_.num_anm;
-    p.modes = tiled_rec_soa_.modes;
-    p.poses = poses;
-    p.stride = stride;
-    p.active = active;
-    p.n_poses = n;
-    p.cx = packed_.cx;
-    p.cy = packed_.cy;
-    p.cz = packed_.cz;
-    p.kappa = packed_.kappa;
-    p.ubound = packed_.ubound;
-    return p;
-}
-
 Scorer::~Scorer() {
     for (auto &e : events_) {
         (void)hipEventDestroy(e.first);
@@ -1350,14 +1373,17 @@ Scorer::~Scorer() {
 uint64_t Scorer::workspace_generation() const {
     uint64_t g = 0;
     // every buffer a launch of energy_batch_device can touch (ws_poses_ / ws_energies_ serve energy_batch_host only)
-    for (const DeviceBuffer *b : {&ws_partial_, &ws_flags_, &ws_counts_, &ws_tested_, &ws_exact_, &ws_rec_sub_, &ws_rec_tile_, &ws_rec_pairs_})
-        g += b->generation;
-    return g + (bm_ ? bm_->generation() : 0);
+    for (const DeviceBuffer *b : {&ws_partial_, &ws_flags_, &ws_counts_, &ws_tested_, &ws_exact_}) g += b->generation;
+    return g + (bm_ ? bm_->generation() : 0) + (packed_ ? packed_->generation() : 0);
+}
+
+size_t Scorer::partials_per_pose() const {  // (dfire_bm_gather leaves one partial per pose)
+    return bm_ ? 1 : packed_ ? packed_->partials_per_pose() : (size_t)pair_.n_chunks;
 }
 
 void Scorer::reserve_workspace(size_t n_poses, bool counts) {
     const size_t words = (size_t)(pair_.rec.flag_words + pair_.lig.flag_words);
-    const size_t chunks = (size_t)std::max(pair_.n_chunks, route_ == PairRoute::all_pairs ? 0 : packed_.n_groups * kPackedPartialsPerGroup);
+    const size_t chunks = partials_per_pose();
     ws_partial_.reserve(n_poses * chunks * 2 * sizeof(double));
     ws_flags_.reserve(std::max<size_t>(n_poses * words * sizeof(uint32_t), 16));
     if (counts) {
@@ -1375,39 +1401,28 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
     if (stride < pose_len()) throw Error(LD_ERR_INVALID, "energy_batch: stride shorter than a pose row");
     // the list is the compacted form of the mask: the pair kernels walk the list, the tail kernel the mask
     if (d_list && (!d_active || !d_count)) throw Error(LD_ERR_INVALID, "energy_batch: a pose list needs its device-side count and the matching active mask");
-    if (route_ == PairRoute::packed && rec_anm_per_pose_) {   // (the block-major path keeps a pose's receptor BOXES only: 36 bytes an atom less)
-        // every pose carries its own deformed receptor image: bound that workspace (8 GiB) by
-        // slicing very large batches; poses are independent, so the results do not change
-        const size_t pad = (size_t)packed_.rec.n_tiles * 64;
-        const size_t per_pose = pad / 2 * sizeof(PackedRecPair) + (pad / 8 + pad / 64) * sizeof(TiledBox);
-        static const size_t cap = [] {  // LIGHTDOCK_RECEPTOR_IMAGE_MIB: test hook for the slicing
-            const char *e = std::getenv("LIGHTDOCK_RECEPTOR_IMAGE_MIB");
-            const long v = e ? std::atol(e) : 0;
-            return v > 0 ? size_t(v) << 20 : size_t(8) << 30;
-        }();
-        const size_t max_n = std::max<size_t>(1, cap / per_pose);
-        if (n > max_n) {
-            for (size_t off = 0; off < n; off += max_n)
-                energy_batch_device(std::min(max_n, n - off), d_poses + off * stride, stride,
-                                    d_active ? d_active + off : nullptr, d_energies + off,
-                                    d_pair_counts ? d_pair_counts + off : nullptr);  // slices go by the mask, not the list
-            return;
-        }
+    // A packed route whose every pose carries its own deformed receptor image bounds that workspace by slicing very large
+    // batches; poses are independent, so the results do not change.  (The block-major path keeps a pose's receptor BOXES only.)
+    const size_t max_n = packed_ ? packed_->max_batch() : n;
+    if (n > max_n) {
+        for (size_t off = 0; off < n; off += max_n)
+            energy_batch_device(std::min(max_n, n - off), d_poses + off * stride, stride, d_active ? d_active + off : nullptr,
+                                d_energies + off, d_pair_counts ? d_pair_counts + off : nullptr);  // slices go by the mask, not the list
+        return;
     }
     reserve_workspace(n, d_pair_counts != nullptr);
 
-    PairLaunch p = pair_;
-    p.poses = d_poses;
-    p.stride = stride;
-    p.active = d_active;
-    p.n_poses = n;
-    p.partial = static_cast<double *>(ws_partial_.ptr);
-    p.flags = static_cast<uint32_t *>(ws_flags_.ptr);
-    p.count_partial = d_pair_counts ? static_cast<uint32_t *>(ws_counts_.ptr) : nullptr;
-
-    const size_t words = (size_t)(p.rec.flag_words + p.lig.flag_words);
+    PoseOutputs out;
+    out.flags = static_cast<uint32_t *>(ws_flags_.ptr);
+    out.partial = static_cast<double *>(ws_partial_.ptr);
+    if (d_pair_counts) {
+        out.count_partial = static_cast<uint32_t *>(ws_counts_.ptr);
+        out.tested_partial = static_cast<uint32_t *>(ws_tested_.ptr);
+        out.exact_partial = static_cast<uint32_t *>(ws_exact_.ptr);
+    }
+    const size_t words = (size_t)(pair_.rec.flag_words + pair_.lig.flag_words);
     // (the block-major path clears a pose's flag words in dfire_bm_pose: one launch less per step)
-    if (words > 0 && route_ != PairRoute::block_major) hip_check(hipMemsetAsync(p.flags, 0, n * words * sizeof(uint32_t), stream_), "hipMemsetAsync(flags)");
+    if (words > 0 && route_ != PairRoute::block_major) hip_check(hipMemsetAsync(out.flags, 0, n * words * sizeof(uint32_t), stream_), "hipMemsetAsync(flags)");
     const bool timing = timing_ && !capturing_;
     if (timing) {
         if (events_used_ == events_.size()) {
@@ -1427,59 +1442,24 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
         hip_check(hipEventRecord(events_[events_used_].first, stream_), "hipEventRecord");
     }
     switch (route_) {
-    case PairRoute::block_major: {
-        p.n_chunks = 1;  // dfire_bm_gather leaves one partial per pose
-        BlockMajorPath::Outputs out;
-        out.flags = p.flags;
-        out.partial = p.partial;
-        if (d_pair_counts) {
-            out.count_partial = p.count_partial;
-            out.tested_partial = static_cast<uint32_t *>(ws_tested_.ptr);
-            out.exact_partial = static_cast<uint32_t *>(ws_exact_.ptr);
-        }
+    case PairRoute::block_major:
         bm_->run(n, d_poses, stride, d_active, d_list, d_count, out, stream_);
         break;
-    }
-    case PairRoute::packed: {
-        PackedLaunch t = packed_;
-        t.poses = d_poses;
-        t.stride = stride;
-        t.active = d_list ? nullptr : d_active;  // the list holds exactly the active rows
-        t.pose_list = d_list;
-        t.pose_count = d_list ? d_count : nullptr;
-        t.n_poses = n;
-        t.partial = p.partial;
-        t.flags = p.flags;
-        t.count_partial = p.count_partial;
-        if (p.count_partial) t.lut = packed_lut_full_;
-        t.tested_partial = p.count_partial ? static_cast<uint32_t *>(ws_tested_.ptr) : nullptr;
-        t.exact_partial = p.count_partial ? static_cast<uint32_t *>(ws_exact_.ptr) : nullptr;
-        p.n_chunks = t.n_groups * kPackedPartialsPerGroup;  // the tail kernel folds this many partials
-        if (rec_anm_per_pose_) {  // one deformed receptor image per pose (src/dfire.rs:304-320)
-            const size_t pad = (size_t)t.rec.n_tiles * 64;
-            ws_rec_pairs_.reserve(n * (pad / 2) * sizeof(PackedRecPair));
-            ws_rec_sub_.reserve(n * (pad / 8) * sizeof(TiledBox));
-            ws_rec_tile_.reserve(n * (pad / 64) * sizeof(TiledBox));
-            PackedPrepareLaunch pr = packed_prepare_launch(d_poses, stride, d_active, n);
-            pr.pairs_out = static_cast<PackedRecPair *>(ws_rec_pairs_.ptr);
-            pr.sub_out = static_cast<TiledBox *>(ws_rec_sub_.ptr);
-            pr.tile_out = static_cast<TiledBox *>(ws_rec_tile_.ptr);
-            hip_check(launch_packed_prepare(pr, stream_), "launch dfire_packed_prepare");
-            t.rec.pairs = pr.pairs_out;
-            t.rec.sub_boxes = pr.sub_out;
-            t.rec.tile_boxes = pr.tile_out;
-            t.rec.modes = pr.modes;
-            t.rec.num_anm = pr.num_anm;
-            t.rec.pose_stride_pairs = pad / 2;
-            t.rec.pose_stride_sub = pad / 8;
-            t.rec.pose_stride_tile = pad / 64;
-        }
-        hip_check(launch_dfire_packed(t, stream_), "launch dfire_packed_pairs");
+    case PairRoute::packed:
+        packed_->run(n, d_poses, stride, d_active, d_list, d_count, out, stream_);
         break;
-    }
-    case PairRoute::all_pairs:
+    case PairRoute::all_pairs: {
+        PairLaunch p = pair_;
+        p.poses = d_poses;
+        p.stride = stride;
+        p.active = d_active;
+        p.n_poses = n;
+        p.partial = out.partial;
+        p.flags = out.flags;
+        p.count_partial = out.count_partial;
         hip_check(launch_pair_kernel(p, stream_), "launch pose_energy_pairs");
         break;
+    }
     }
     if (timing) {
         hip_check(hipEventRecord(events_[events_used_].second, stream_), "hipEventRecord");
@@ -1488,13 +1468,13 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
 
     FinishLaunch f;
     f.method = method_;
-    f.n_chunks = p.n_chunks;
-    f.rec_flag_words = p.rec.flag_words;
-    f.lig_flag_words = p.lig.flag_words;
+    f.n_chunks = (int)partials_per_pose();
+    f.rec_flag_words = pair_.rec.flag_words;
+    f.lig_flag_words = pair_.lig.flag_words;
     f.tail = tail_;
-    f.partial = p.partial;
-    f.flags = p.flags;
-    f.count_partial = p.count_partial;
+    f.partial = out.partial;
+    f.flags = out.flags;
+    f.count_partial = out.count_partial;
     f.active = d_active;
     f.n_poses = n;
     f.energies = d_energies;
@@ -1517,7 +1497,7 @@ void Scorer::energy_batch_host(size_t n, const double *poses, size_t stride, dou
 void Scorer::last_block_counts(size_t n, uint32_t *out_host) {
     if (route_ == PairRoute::all_pairs) throw Error(LD_ERR_UNSUPPORTED, "block counts exist for a box-culled, tiled DFIRE kernel only (block-major or packed), not for all pairs");
     if (!out_host) throw Error(LD_ERR_INVALID, "null output");
-    const size_t groups = (size_t)(route_ == PairRoute::block_major ? 1 : packed_.n_groups * kPackedPartialsPerGroup);
+    const size_t groups = partials_per_pose();
     if (ws_tested_.bytes < n * groups * sizeof(uint32_t)) throw Error(LD_ERR_INVALID, "no counting launch of that size has run");
     std::vector<uint32_t> part(n * groups);
     hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
@@ -1559,8 +1539,8 @@ void Scorer::kernel_info(ld_kernel_info *out) const {
     case PairRoute::packed:
         out->pair_kernel_name = "dfire_packed_pairs";
         out->block_threads = (uint32_t)kPackedWaves * 64;
-        out->receptor_chunks = (uint32_t)packed_.n_groups;
-        out->lds_bytes = (uint32_t)packed_kernel_lds_bytes(packed_.cells_per_unit);
+        out->receptor_chunks = (uint32_t)packed_->model().n_groups;
+        out->lds_bytes = (uint32_t)packed_kernel_lds_bytes(packed_->model().cells_per_unit);
         break;
     case PairRoute::all_pairs:
         out->pair_kernel_name = pair_kernel_name(method_);

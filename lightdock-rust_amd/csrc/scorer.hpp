@@ -87,6 +87,76 @@ struct TiledSoA {  // a molecule in tile order, SoA, padded to whole tiles
     std::vector<double> hmodes;       // host copy of `modes`: [mode][xyz][padded atoms]
 };
 
+struct ReceptorImage {  // the receptor as pair records and boxes in an f32 frame (dfire_packed_prepare's output)
+    PackedRecPair *pairs = nullptr;
+    TiledBox *sub = nullptr, *tile = nullptr;
+};
+
+// What the two culled DFIRE routes share (Scorer::build_tiles, before either route is chosen): both molecules in tile order,
+// the ligand as the kernels read it, the potential in patches, and the bins no pair of this complex draws a value from.
+struct DfireTiles {
+    TiledSoA rec, lig;
+    TiledLigand lig_view;              // `lig` as the culled kernels read it
+    const double *table = nullptr;     // the potential in 2 x 2 x 4 patches (kernels/dfire_tiled.hpp)
+    std::vector<uint32_t> type_perm_rec, type_perm_lig;  // DFIRE type -> number used by the patch table's layout
+    uint32_t zero_bins = 0;            // bit b: the potential is zero in bin b for every type pair of the complex (LIGHTDOCK_PACKED_ELIDE_ZERO_BINS=0: none)
+    // dfire_packed_prepare's arguments for the frame (centre, kappa, ubound): the receptor's; poses and outputs are the caller's
+    PackedPrepareLaunch prepare(const double centre[3], double kappa, double ubound) const;
+    // the undeformed receptor's image in that frame, in `arena`: one launch on `stream`, synchronised
+    ReceptorImage static_image(DeviceArena &arena, const double centre[3], double kappa, double ubound, hipStream_t stream) const;
+};
+
+// What a culled route takes from the scorer that builds it.
+struct RouteInputs {
+    const ld_scorer_desc &desc;
+    const DfireTiles &tiles;
+    int rec_flag_words;
+    const double *bin_step;   // kDfireSteps, d2 units (the all-pairs launch's)
+    double iface_d2;
+    bool use_anm;
+    bool latency;             // LIGHTDOCK_TILED_LATENCY: launches of one swarm
+    int n_cus;
+    hipStream_t stream;       // of the one launch a route's construction needs
+};
+
+// The per-pose buffers every route writes (the scorer's): one pose's partial sums, as many as the route leaves, and its flag words.
+struct PoseOutputs {
+    uint32_t *flags = nullptr;
+    double *partial = nullptr;
+    uint32_t *count_partial = nullptr, *tested_partial = nullptr, *exact_partial = nullptr;   // counting launches only
+};
+
+// ---------------------------------------------------------------------------------------
+// The pose-major packed-f32 DFIRE route (kernels/dfire_packed.hpp) as one object
+// ---------------------------------------------------------------------------------------
+// What packed_accepts() derives of a receptor the route takes (host arithmetic only).
+struct PackedFrame {
+    double centre[3] = {0, 0, 0}, kappa = 2.0, ubound = 0.0, eps = 0.0;   // the record frame; the LUT's error bound (units of 4 d2)
+    int cells = 1;                                                        // LUT cells per unit of 4 d2
+};
+bool packed_accepts(const ld_molecule &receptor, PackedFrame *out);   // false: the receptor is too long for the f32 frame (all pairs, f64)
+
+class PackedPath {
+   public:
+    PackedPath(const RouteInputs &in, const PackedFrame &frame);
+    // The largest batch run() takes: a receptor that flexes carries one image per pose, bounded to 8 GiB (LIGHTDOCK_RECEPTOR_IMAGE_MIB).
+    size_t max_batch() const;
+    // One batch: with a receptor that flexes dfire_packed_prepare, then dfire_packed_pairs, on `stream`.
+    void run(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, const uint32_t *d_list, const uint32_t *d_count,
+             const PoseOutputs &out, hipStream_t stream);
+    uint64_t generation() const { return ws_rec_pairs_.generation + ws_rec_sub_.generation + ws_rec_tile_.generation; }
+    size_t partials_per_pose() const { return (size_t)model_.n_groups * kPackedPartialsPerGroup; }
+    const PackedLaunch &model() const { return model_; }
+
+   private:
+    const DfireTiles &tiles_;
+    DeviceArena arena_;                           // the LUTs and a rigid receptor's image
+    PackedLaunch model_;
+    const uint32_t *lut_full_ = nullptr;          // the LUT without elided zero bins (counting launches)
+    bool image_per_pose_ = false;                 // receptor ANM: one receptor image per pose per launch
+    DeviceBuffer ws_rec_pairs_, ws_rec_sub_, ws_rec_tile_;
+};
+
 // ---------------------------------------------------------------------------------------
 // The block-major DFIRE route (kernels/dfire_bm.hpp) as one object
 // ---------------------------------------------------------------------------------------
@@ -108,25 +178,6 @@ struct BmWorkspace {
     }
 };
 
-// What the block-major path takes from the scorer that builds it: the complex, both molecules in tile order (already
-// uploaded), the tables the culled routes share, and the stream of the one launch its construction needs.
-struct BmInputs {
-    const ld_scorer_desc &desc;
-    const TiledSoA &rec, &lig;
-    const std::vector<uint32_t> &type_perm_rec, &type_perm_lig;
-    BmInputs(const ld_scorer_desc &d, const TiledSoA &r, const TiledSoA &l, const std::vector<uint32_t> &pr, const std::vector<uint32_t> &pl)
-        : desc(d), rec(r), lig(l), type_perm_rec(pr), type_perm_lig(pl) {}
-    TiledLigand tiled_lig;
-    const double *tiled_table = nullptr;
-    uint32_t zero_bins = 0;      // bins in which this complex's potential is zero throughout (build_packed)
-    int rec_flag_words = 0;
-    double iface_d2 = 0.0;
-    bool use_anm = false;
-    int n_cus = 256;
-    PackedPrepareLaunch prepare;   // dfire_packed_prepare's receptor arguments (frame and outputs: the path's own)
-    hipStream_t stream = nullptr;
-};
-
 // What bm_accepts() derives of a complex the path takes (host arithmetic only).
 struct BmFrame {
     bool anm = false;
@@ -139,7 +190,7 @@ struct BmFrame {
 class BlockMajorPath {
    public:
     // nullptr: declined -- the complex stays with the pose-major kernels, and nothing was uploaded or launched for this path
-    static std::unique_ptr<BlockMajorPath> build(const BmInputs &in);
+    static std::unique_ptr<BlockMajorPath> build(const RouteInputs &in);
     ~BlockMajorPath();
     BlockMajorPath(const BlockMajorPath &) = delete;
     BlockMajorPath &operator=(const BlockMajorPath &) = delete;
@@ -148,18 +199,13 @@ class BlockMajorPath {
     void reserve(size_t n, bool counts) { ws_.reserve(bm_layout(shape(n, counts, false))); }
     // One batch: passes of at most pass_poses(n) poses, each dfire_bm_pose .. dfire_bm_gather, on `stream` (and, two passes in
     // flight, the path's second stream, joined before returning).  Leaves one partial per pose in `partial`.
-    struct Outputs {   // the per-pose buffers every route shares (the scorer's)
-        uint32_t *flags = nullptr;
-        double *partial = nullptr;
-        uint32_t *count_partial = nullptr, *tested_partial = nullptr, *exact_partial = nullptr;   // counting launches only
-    };
     void run(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, const uint32_t *d_list, const uint32_t *d_count,
-             const Outputs &out, hipStream_t stream);
+             const PoseOutputs &out, hipStream_t stream);
     uint64_t generation() const { return ws_.generation(); }
     uint32_t quiet_subtiles() const { return quiet_subtiles_; }
 
    private:
-    BlockMajorPath(const BmInputs &in, const BmFrame &frame);
+    BlockMajorPath(const RouteInputs &in, const BmFrame &frame);
     size_t pass_poses(size_t n) const;   // poses per pass of a batch of n
     size_t sets(size_t n) const;         // workspace sets a batch of n poses needs (2 while two passes are in flight)
     BmShape shape(size_t n, bool counts, bool debug) const;
@@ -219,10 +265,9 @@ class Scorer {
                          std::vector<uint32_t> &group_offsets, std::vector<uint32_t> &group_slots,
                          std::vector<uint32_t> &membrane_slots);
     void reserve_workspace(size_t n_poses, bool counts);
-    void build_tile_order(const ld_scorer_desc &desc, bool latency);  // what the culled paths share: tile order, patch table, ligand view, split
-    bool build_packed(const ld_scorer_desc &desc);  // after build_tile_order; false: declined (the receptor is too long for the f32 frame)
-    void upload_tiled_molecule(const ld_molecule &m, bool is_receptor, TiledSoA &out);
-    PackedPrepareLaunch packed_prepare_launch(const double *poses, size_t stride, const uint8_t *active, size_t n) const;
+    size_t partials_per_pose() const;  // what the route that runs leaves for pose_energy_finish to fold
+    void build_tiles(const ld_scorer_desc &desc);  // what the culled routes share (tiles_)
+    void upload_tiled_molecule(const ld_molecule &m, bool is_receptor, TiledSoA &out, std::vector<uint32_t> &type_perm);
 
     int device_ = 0;
     hipStream_t stream_ = nullptr;
@@ -237,23 +282,13 @@ class Scorer {
     // kernel (kernels/dfire_packed.hpp), or the all-pairs kernel of pose_energy.hpp (DNA, and DFIRE where the culled paths decline)
     enum class PairRoute { block_major, packed, all_pairs };
     PairRoute route_ = PairRoute::all_pairs;
-    TiledLigand tiled_lig_;                 // the ligand in tile order, as the culled kernels read it
-    const double *tiled_table_ = nullptr;   // the potential in 2 x 2 x 4 patches (kernels/dfire_tiled.hpp)
-    int tiled_split_ = 1;                   // waves sharing one ligand tile in the pose-major kernel
-    PackedLaunch packed_;
-    const uint32_t *packed_lut_full_ = nullptr;  // the LUT without elided zero bins (counting launches)
-    uint32_t packed_zero_bins_ = 0;
-    DeviceBuffer ws_rec_pairs_, ws_exact_;
-    std::unique_ptr<BlockMajorPath> bm_;    // set: route_ == block_major (after build_packed; rigid molecules, and the ANM form for molecules that flex)
-    TiledSoA tiled_lig_soa_;
+    DfireTiles tiles_;                      // DFIRE unless LIGHTDOCK_DFIRE_KERNEL=allpairs; the routes below read it
+    std::unique_ptr<BlockMajorPath> bm_;    // set: route_ == block_major
+    std::unique_ptr<PackedPath> packed_;    // set: route_ == packed
     int n_cus_ = 256;
-    TiledSoA tiled_rec_soa_;          // receptor in tile order (input of dfire_packed_prepare)
-    bool rec_anm_per_pose_ = false;   // receptor ANM: one receptor image per pose per launch
-    DeviceBuffer ws_rec_sub_, ws_rec_tile_;
-    std::vector<uint32_t> type_perm_rec_, type_perm_lig_;  // DFIRE type -> number used by the patch table's layout
     std::vector<int32_t> host_slot_rec_, host_slot_lig_;  // per original atom, as uploaded to the all-pairs path
     HostMolecule host_rec_, host_lig_;
-    DeviceBuffer ws_partial_, ws_flags_, ws_counts_, ws_tested_, ws_poses_, ws_energies_;
+    DeviceBuffer ws_partial_, ws_flags_, ws_counts_, ws_tested_, ws_exact_, ws_poses_, ws_energies_;
     bool timing_ = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events_;  // pool, reused
     size_t events_used_ = 0;

@@ -143,7 +143,10 @@ hipError_t launch_bm_gather(const BmLaunch &t, hipStream_t) {
     }
     return hipSuccess;
 }
+static size_t packed_prepare_launches = 0;
+extern "C" size_t ld_stub_packed_prepare_launches(void) { return packed_prepare_launches; }   // host_check: what a scorer's construction launched
 hipError_t launch_packed_prepare(const PackedPrepareLaunch &p, hipStream_t) {
+    packed_prepare_launches++;
     if (p.n_poses && p.pairs_out) std::memset(p.pairs_out, 0, p.n_poses * (size_t)p.n_tiles * 32 * sizeof(PackedRecPair));
     if (p.n_poses && p.sub_out) std::memset(p.sub_out, 0, p.n_poses * (size_t)p.n_tiles * 8 * sizeof(TiledBox));
     if (p.n_poses && p.tile_out) std::memset(p.tile_out, 0, p.n_poses * (size_t)p.n_tiles * sizeof(TiledBox));

@@ -23,6 +23,7 @@ static int failures = 0;
     } while (0)
 
 extern "C" size_t ld_stub_device_allocations(void);   // tests/asan/hip_stub.cpp
+extern "C" size_t ld_stub_packed_prepare_launches(void);
 
 // A DFIRE scorer through every form of a block-major batch: plain, counting (the sequence runs twice), the single-pose call.
 // Device memory is host memory in this build, so the device-pointer call takes host vectors.
@@ -214,6 +215,22 @@ int main(int argc, char **argv) {
         CHECK(d != nullptr && ld_stub_device_allocations() - before == declined);
         if (d) ld_scorer_destroy(d);
         unsetenv("LIGHTDOCK_DFIRE_KERNEL");
+    }
+    {   // and the mirror: a rigid scorer builds the receptor image of the route it runs, once -- nothing of the packed route under a
+        // block-major scorer, nothing of either culled route under the all-pairs kernel
+        const char *kernels[3] = {nullptr, "packed", "allpairs"};
+        const char *names[3] = {"dfire_bm_pairs", "dfire_packed_pairs", "pose_energy_pairs<0"};
+        const size_t want[3] = {1, 1, 0};
+        for (int k = 0; k < 3; k++) {
+            if (kernels[k]) setenv("LIGHTDOCK_DFIRE_KERNEL", kernels[k], 1);
+            const size_t before = ld_stub_packed_prepare_launches();
+            ld_scorer *c = dfire(nullptr, nullptr, 0, table.data());
+            CHECK(c != nullptr && ld_stub_packed_prepare_launches() - before == want[k]);
+            ld_kernel_info info;
+            CHECK(c && ld_scorer_kernel_info(c, &info) == LD_OK && std::strcmp(info.pair_kernel_name, names[k]) == 0);
+            if (c) ld_scorer_destroy(c);
+            unsetenv("LIGHTDOCK_DFIRE_KERNEL");
+        }
     }
     CHECK(ld_scorer_create_from_pdb(7, rec1.c_str(), lig1.c_str(), nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, nullptr, 0,
                                     nullptr, 0, 0, 0, table.data()) == nullptr);

@@ -1212,7 +1212,7 @@ def test_receptor_larger_than_one_ballot(pkg, orc, table, tmp_path, n_rec, box):
 
 def test_receptor_too_long_for_the_packed_frame(pkg, orc, table, tmp_path):
     """A receptor more than ~8100 A long on one axis: no f32 frame of the packed kernels holds it with a small enough error
-    bound (scorer.cpp, build_packed), so the scorer takes the all-pairs kernel -- the oracle's energies and in-cutoff pair
+    bound (scorer.cpp, packed_accepts), so the scorer takes the all-pairs kernel -- the oracle's energies and in-cutoff pair
     counts.  Two residue clumps 8300 A apart, the ligand posed next to either of them or far from both."""
     torch = pytest.importorskip("torch")
     rng = np.random.default_rng(41)
@@ -1244,7 +1244,7 @@ def test_receptor_too_long_for_the_packed_frame(pkg, orc, table, tmp_path):
 
 def test_which_kernel_a_flexing_complex_gets(pkg, orc, table, tmp_path):
     """The fallbacks of the block-major path's ANM form as a stated contract (VERDICT r05 item 5 ii; lightdock-rust_amd/csrc/scorer.cpp,
-    build_bm): up to ten modes a molecule run `dfire_bm_pairs` -- since round 6 also with a receptor of 8192 atoms or more (the
+    bm_accepts): up to ten modes a molecule run `dfire_bm_pairs` -- since round 6 also with a receptor of 8192 atoms or more (the
     fixed-point scale then allows for the atoms a flexed ligand tile can reach) --, an eleventh mode sends the complex to the
     pose-major `dfire_packed_pairs`; both give the oracle's energies and in-cutoff pair counts (src/dfire.rs:288-320)."""
     torch = pytest.importorskip("torch")
