@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "complex.hpp"
 #include "gso.hpp"
 #include "host/cli.hpp"
 #include "host/docking_model.hpp"
@@ -51,8 +52,6 @@ std::vector<std::string> to_strings(const char *const *list, size_t n) {
 }
 
 }  // namespace
-
-void ld::set_last_error(const std::string &msg) { g_last_error = msg; }
 
 extern "C" {
 
@@ -407,6 +406,70 @@ int ld_gso_save_many(ld_gso *g, size_t n, const size_t *swarms, const char *cons
             d[k] = dirs[k];
         }
         g->impl.save_many(std::vector<size_t>(swarms, swarms + n), step, d);
+    });
+}
+
+/* ---- the analysis half of a run ---------------------------------------------------------- */
+
+ld_complex *ld_complex_create(const char *receptor_pdb, const char *ligand_pdb, const double *rec_nmodes,
+                              size_t rec_nmodes_len, size_t rec_num_anm, const double *lig_nmodes, size_t lig_nmodes_len,
+                              size_t lig_num_anm) {
+    ld_complex *c = nullptr;
+    int rc = guarded([&] {
+        c = new ld_complex(receptor_pdb, ligand_pdb, rec_nmodes, rec_nmodes_len, rec_num_anm, lig_nmodes, lig_nmodes_len, lig_num_anm);
+    });
+    return rc == LD_OK ? c : nullptr;
+}
+void ld_complex_destroy(ld_complex *c) { delete c; }
+
+size_t ld_complex_pose_len(const ld_complex *c) { return c ? c->impl.pose_len() : 0; }
+size_t ld_complex_num_atoms(const ld_complex *c, int side) { return c ? c->impl.num_atoms(side) : 0; }
+size_t ld_complex_num_residues(const ld_complex *c, int side) { return c ? c->impl.num_residues(side) : 0; }
+
+int ld_complex_residue_id(const ld_complex *c, int side, size_t index, char *buf, size_t buf_len) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null argument");
+        c->impl.residue_id(side, index, buf, buf_len);
+    });
+}
+int ld_complex_residue_of_atom(const ld_complex *c, int side, uint32_t *out) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null argument");
+        c->impl.residue_of_atom(side, out);
+    });
+}
+
+int ld_complex_coordinates(ld_complex *c, size_t n, const double *poses, size_t stride, double *xyz_out) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null argument");
+        c->impl.coordinates(n, poses, stride, xyz_out);
+    });
+}
+int ld_complex_cluster(ld_complex *c, size_t n_swarms, size_t n_glowworms, const double *poses, size_t stride,
+                       const double *scoring, double cutoff, int32_t *cluster_of, int32_t *representatives,
+                       uint32_t *n_clusters) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.cluster(n_swarms, n_glowworms, poses, stride, scoring, cutoff, cluster_of, representatives, n_clusters);
+    });
+}
+int ld_complex_contacts(ld_complex *c, size_t n, const double *poses, size_t stride, double cutoff, uint32_t *rec_bits,
+                        uint32_t *lig_bits) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.contacts(n, poses, stride, cutoff, rec_bits, lig_bits);
+    });
+}
+int ld_complex_last_kernel_ms(const ld_complex *c, double *ms_out) {
+    return guarded([&] {
+        if (!c || !ms_out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        *ms_out = c->impl.last_kernel_ms();
+    });
+}
+int ld_complex_write_pdb(ld_complex *c, const double *pose, const char *path) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null argument");
+        c->impl.write_pdb(pose, path);
     });
 }
 

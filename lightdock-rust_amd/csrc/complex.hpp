@@ -1,0 +1,65 @@
+// complex.hpp -- the object behind an `ld_complex*`: a receptor and a ligand as their PDB files give them, device-resident,
+// and the workspace of the analysis kernels (kernels/cluster.hpp).  What lightdock_hip.h says of ld_complex_*
+// holds for the methods of the same names; refusals are ld::Error.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "device_memory.hpp"
+#include "host/pdb_file.hpp"
+#include "kernels/cluster.hpp"
+
+namespace ld {
+
+class Complex {
+   public:
+    Complex(const char *receptor_pdb, const char *ligand_pdb, const double *rec_nmodes, size_t rec_nmodes_len, size_t rec_num_anm,
+            const double *lig_nmodes, size_t lig_nmodes_len, size_t lig_num_anm);
+    ~Complex() { destroy(); }
+    Complex(const Complex &) = delete;
+    Complex &operator=(const Complex &) = delete;
+
+    size_t pose_len() const { return 7 + (size_t)dev_.anm_rec + (size_t)dev_.anm_lig; }
+    size_t num_atoms(int side) const { return side == 0 ? rec_.lines.size() : side == 1 ? lig_.lines.size() : backbone_.size(); }
+    size_t num_residues(int side) const { return side == 0 ? rec_.res_id.size() : side == 1 ? lig_.res_id.size() : 0; }
+    void residue_id(int side, size_t index, char *buf, size_t buf_len) const;
+    void residue_of_atom(int side, uint32_t *out) const;
+
+    void coordinates(size_t n, const double *poses, size_t stride, double *xyz_out);
+    void cluster(size_t n_swarms, size_t n_glowworms, const double *poses, size_t stride, const double *scoring, double cutoff,
+                 int32_t *cluster_of, int32_t *representatives, uint32_t *n_clusters);
+    void contacts(size_t n, const double *poses, size_t stride, double cutoff, uint32_t *rec_bits, uint32_t *lig_bits);
+    void write_pdb(const double *pose, const char *path);
+    double last_kernel_ms() const { return last_kernel_ms_; }
+
+   private:
+    size_t n_atoms() const { return rec_.lines.size() + lig_.lines.size(); }
+    const PdbFile &side_file(int side) const;
+    void check_poses(size_t n, const double *poses, size_t stride) const;
+    void upload_poses(size_t n, const double *poses, size_t stride);  // n rows of `stride` doubles, copied as they are
+    void pose_all(size_t n, const double *poses, size_t stride, double *out);  // all atoms of n poses, unrounded
+    void finish_timed(const int *d_overflow, const char *what, const char *overflow_message);
+    void destroy();
+
+    PdbFile rec_, lig_;
+    std::vector<uint32_t> backbone_;  // complex atom indices: receptor CA / P, then ligand CA / P (offset by n_rec)
+    DeviceArena arena_;
+    ComplexDevice dev_;
+    const uint32_t *d_backbone_ = nullptr;
+    ContactsDevice contacts_;
+    DeviceBuffer d_poses_, d_scores_, d_out_, d_ws_, d_ids_;
+    hipStream_t stream_ = nullptr;
+    hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
+    double last_kernel_ms_ = 0.0;
+};
+
+}  // namespace ld
+
+struct ld_complex {
+    ld::Complex impl;
+    ld_complex(const char *receptor_pdb, const char *ligand_pdb, const double *rec_nmodes, size_t rec_nmodes_len, size_t rec_num_anm,
+               const double *lig_nmodes, size_t lig_nmodes_len, size_t lig_num_anm)
+        : impl(receptor_pdb, ligand_pdb, rec_nmodes, rec_nmodes_len, rec_num_anm, lig_nmodes, lig_nmodes_len, lig_num_anm) {}
+};

@@ -19,7 +19,4 @@ class Error : public std::runtime_error {
     ld_status code_;
 };
 
-// Sets the thread-local message ld_last_error() returns (capi.cpp), for entry points defined elsewhere.
-void set_last_error(const std::string &msg);
-
 }  // namespace ld

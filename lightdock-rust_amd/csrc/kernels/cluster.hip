@@ -1,4 +1,5 @@
-// cluster.hip -- K3: the analysis half of a LightDock run (gfx950) and the ld_complex_* entry points.
+// cluster.hip -- K3: the analysis half of a LightDock run (gfx950).  Kernels and their launchers
+// (kernels/cluster.hpp); the host side is complex.cpp.
 //   complex_pose_xyz:          poses x atoms -> posed f64 coordinates (ld_complex_coordinates, ld_complex_write_pdb);
 //   complex_pose_thousandths:  poses x CA / P atoms -> posed coordinates as the integer thousandths "%8.3f" prints
 //                              (lgd_cluster_bsas.py clusters the PDB files it wrote, so it sees exactly those);
@@ -10,39 +11,17 @@
 // i.e. the ligand's modes in the ligand frame -- NOT the energy's convention (src/dfire.rs:282-302).  f64, qt.rs order,
 // -ffp-contract=off.  Workspace: the thousandths of a chunk of swarms, at most kClusterWorkspaceBytes (or one swarm's
 // n_glowworms x n_backbone x 12 B if more; 1czy: 420 KB a swarm); ld_complex_coordinates poses in chunks of that bound.
-#include <hip/hip_runtime.h>
+#include "kernels/cluster.hpp"
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <memory>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "host/error.hpp"
-#include "lightdock_hip.h"
-#include "scorer.hpp"
 
 namespace ld {
 
 namespace {
 
-constexpr int kMaxGlowworms = 4096;  // ld_gso_create's limit; the sort keys of a swarm fill 48 KiB of LDS
-constexpr int kBsasThreads = 256;
-constexpr int kPoseThreads = 256;
-constexpr size_t kClusterWorkspaceBytes = size_t(256) << 20;
 constexpr int kEarlyExitAtoms = 32;  // the RMSD test is re-checked on the partial sum every this many atoms
-
-struct ComplexDevice {
-    int n_rec = 0, n_lig = 0, anm_rec = 0, anm_lig = 0;
-    const double *rec_xyz = nullptr, *lig_xyz = nullptr;      // n x 3, file order
-    const double *rec_modes = nullptr, *lig_modes = nullptr;  // anm x n x 3 (lightdock_<side>.nm.npy, C order)
-};
 
 struct P3 {
     double x, y, z;
@@ -253,22 +232,8 @@ unsigned grid_for(size_t total) {
 //   4. bits are ORed in LDS and every output word is stored once.
 // Every coordinate is within +-kCoordBound (the call fails otherwise), so the difference of any two fits an int32.
 
-constexpr int kContactThreads = 512;
-constexpr int kContactSlots = 1024;            // 256 CUs x 4 resident workgroups
-constexpr int kResGroup = 8;
 constexpr int kCoordBound = 1000000000;        // thousandths: +-1.0e6 A
 constexpr uint32_t kAxisClamp = 32767;         // > 30000 >= C
-constexpr size_t kMaxContactWords = 16384;     // bit words of both sides, kept in LDS (64 KiB: 524 288 residues)
-constexpr size_t kMaxBoxLdsBytes = 40 << 10;   // 24 B a box: up to 1706 residues + ligand groups (1k4c: 1327) keep four workgroups a CU
-
-struct ContactsDevice {
-    int n_atoms = 0, n_rec_res = 0, n_lig_res = 0, n_lig_grp = 0;  // groups: kResGroup consecutive ligand residues
-    int boxes_in_lds = 0;
-    const uint32_t *res_start = nullptr;  // n_rec_res + n_lig_res + 1 complex atom indices, receptor residues first
-    const uint32_t *res_of_atom = nullptr;  // n_atoms residue indices, the ligand's after the receptor's
-    __host__ __device__ int n_boxes() const { return n_rec_res + n_lig_res + n_lig_grp; }
-    size_t box_bytes() const { return (size_t)n_boxes() * 6 * sizeof(int); }
-};
 
 // min(|d|, 32767) of a coordinate difference.  32767 > 30000 >= C: a clamped axis alone already exceeds the cutoff,
 // so clamping never changes dx^2 + dy^2 + dz^2 <= C^2, and the sum of three squares stays below 3 * 2^30 < 2^32:
@@ -434,386 +399,39 @@ __global__ void __launch_bounds__(kContactThreads, 8) complex_contacts(ComplexDe
     }
 }
 
-// --- host side -------------------------------------------------------------------------------------------------
-
-struct PdbFile {
-    std::vector<std::string> lines;  // ATOM / HETATM records as read (other records are dropped)
-    std::vector<double> xyz;
-    std::vector<uint32_t> backbone;  // atoms named CA or P
-    // residues: maximal runs of consecutive records with the same columns 18-20, 22, 23-26 and 27
-    std::vector<uint32_t> res_start;     // first atom of each residue, then the atom count
-    std::vector<uint32_t> res_of_atom;
-    std::vector<std::string> res_id;     // "<chain>.<resname>.<serial><icode>", AtomRecord::residue_id() (src/dfire.rs:139-142)
-};
-
-std::string trimmed(const std::string &s) {
-    const size_t b = s.find_first_not_of(' ');
-    return b == std::string::npos ? std::string() : s.substr(b, s.find_last_not_of(' ') - b + 1);
-}
-
-void cut_residues(PdbFile &f) {
-    for (size_t a = 0; a < f.lines.size(); a++) {
-        const std::string &line = f.lines[a];
-        // resname; chain, serial, icode
-        if (a == 0 || line.compare(17, 3, f.lines[a - 1], 17, 3) != 0 || line.compare(21, 6, f.lines[a - 1], 21, 6) != 0) {
-            f.res_start.push_back((uint32_t)a);
-            f.res_id.push_back(trimmed(line.substr(21, 1)) + "." + trimmed(line.substr(17, 3)) + "." +
-                               std::to_string(std::strtol(line.substr(22, 4).c_str(), nullptr, 10)) + trimmed(line.substr(26, 1)));
-        }
-        f.res_of_atom.push_back((uint32_t)f.res_id.size() - 1);
-    }
-    f.res_start.push_back((uint32_t)f.lines.size());
-}
-
-PdbFile read_pdb_file_order(const char *path) {
-    if (!path) throw Error(LD_ERR_INVALID, "PDB path missing");
-    std::ifstream in(path);
-    if (!in) throw Error(LD_ERR_IO, std::string("cannot open PDB file ") + path);
-    PdbFile f;
-    std::string line;
-    while (std::getline(in, line)) {
-        if (!line.empty() && line.back() == '\r') line.pop_back();
-        if (line.compare(0, 6, "ATOM  ") != 0 && line.compare(0, 6, "HETATM") != 0) continue;
-        if (line.size() < 54) throw Error(LD_ERR_IO, std::string(path) + ": ATOM/HETATM record shorter than 54 columns");
-        for (int k = 0; k < 3; k++) {
-            const std::string field = line.substr(30 + 8 * k, 8);
-            char *end = nullptr;
-            const double v = std::strtod(field.c_str(), &end);
-            if (end == field.c_str()) throw Error(LD_ERR_IO, std::string(path) + ": unreadable coordinate '" + field + "'");
-            f.xyz.push_back(v);
-        }
-        std::string name = line.substr(12, 4);
-        name.erase(name.find_last_not_of(' ') + 1);
-        name.erase(0, name.find_first_not_of(' '));
-        if (name == "CA" || name == "P") f.backbone.push_back((uint32_t)f.lines.size());
-        f.lines.push_back(line);
-    }
-    if (f.lines.empty()) throw Error(LD_ERR_INVALID, std::string(path) + ": no ATOM/HETATM records");
-    cut_residues(f);
-    return f;
-}
-
-void check_poses(size_t n, const double *poses, size_t stride, size_t pose_len) {
-    if (n && !poses) throw Error(LD_ERR_INVALID, "null poses");
-    if (stride < pose_len) throw Error(LD_ERR_INVALID, "pose stride below the pose length");
-    for (size_t i = 0; i < n; i++) {
-        const double *row = poses + i * stride;
-        for (size_t k = 0; k < pose_len; k++)
-            if (!std::isfinite(row[k])) throw Error(LD_ERR_INVALID, "pose " + std::to_string(i) + " is not finite");
-        if (row[3] == 0.0 && row[4] == 0.0 && row[5] == 0.0 && row[6] == 0.0)
-            throw Error(LD_ERR_INVALID, "pose " + std::to_string(i) + " has a zero quaternion");
-    }
-}
-
 }  // namespace
+
+hipError_t launch_complex_pose_xyz(const ComplexDevice &m, const double *poses, size_t stride, size_t n, double *out,
+                                   hipStream_t stream) {
+    const uint32_t n_atoms = (uint32_t)(m.n_rec + m.n_lig);
+    hipLaunchKernelGGL(complex_pose_xyz, dim3(grid_for(n * n_atoms)), dim3(kPoseThreads), 0, stream, m, poses, stride, n, n_atoms,
+                       out);
+    return hipGetLastError();
+}
+
+hipError_t launch_complex_pose_thousandths(const ComplexDevice &m, const double *poses, size_t stride, int n_swarms, int G,
+                                           const uint32_t *backbone, int n_bb, int32_t *ws, int *overflow, hipStream_t stream) {
+    hipLaunchKernelGGL(complex_pose_thousandths, dim3(grid_for((size_t)n_swarms * n_bb * G)), dim3(kPoseThreads), 0, stream, m,
+                       poses, stride, n_swarms, G, backbone, n_bb, ws, overflow);
+    return hipGetLastError();
+}
+
+hipError_t launch_complex_bsas(const int32_t *ws, const double *scoring, int n_swarms, int G, int n_bb, double cutoff,
+                               int32_t *cluster_of, int32_t *representatives, uint32_t *n_clusters, hipStream_t stream) {
+    hipLaunchKernelGGL(complex_bsas, dim3((unsigned)n_swarms), dim3(kBsasThreads), 0, stream, ws, scoring, G, n_bb, cutoff,
+                       cluster_of, representatives, n_clusters);
+    return hipGetLastError();
+}
+
+hipError_t launch_complex_contacts(const ComplexDevice &m, const ContactsDevice &d, const double *poses, size_t stride, size_t n,
+                                   uint32_t C2, size_t slots, int4 *atoms_ws, int *boxes_ws, uint32_t *rec_bits,
+                                   uint32_t *lig_bits, int *overflow, hipStream_t stream) {
+    // the bit words of both sides, then the boxes if they fit
+    const size_t words = ((size_t)d.n_rec_res + 31) / 32 + ((size_t)d.n_lig_res + 31) / 32;
+    const size_t lds = words * sizeof(uint32_t) + (d.boxes_in_lds ? d.box_bytes() : 0);
+    hipLaunchKernelGGL(complex_contacts, dim3((unsigned)slots), dim3(kContactThreads), lds, stream, m, d, poses, stride, n, C2,
+                       atoms_ws, boxes_ws, rec_bits, lig_bits, overflow);
+    return hipGetLastError();
+}
 
 }  // namespace ld
-
-struct ld_complex {
-    ld::PdbFile rec, lig;
-    std::vector<uint32_t> backbone;  // complex atom indices: receptor CA / P, then ligand CA / P (offset by n_rec)
-    ld::DeviceArena arena;
-    ld::ComplexDevice dev;
-    const uint32_t *d_backbone = nullptr;
-    ld::ContactsDevice contacts;
-    ld::DeviceBuffer d_poses, d_scores, d_out, d_ws, d_ids;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double last_kernel_ms = 0.0;
-
-    size_t n_atoms() const { return rec.lines.size() + lig.lines.size(); }
-    size_t pose_len() const { return 7 + (size_t)dev.anm_rec + (size_t)dev.anm_lig; }
-
-    ~ld_complex() {
-        // the buffers are freed after this body: nothing queued (a call that threw halfway) may still use them
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-
-    // n poses (rows of `stride` doubles) to the device, checked and copied as they are
-    void upload_poses(size_t n, const double *poses, size_t stride) {
-        d_poses.reserve(n * stride * sizeof(double));
-        ld::hip_check(hipMemcpyAsync(d_poses.ptr, poses, n * stride * sizeof(double), hipMemcpyHostToDevice, stream),
-                      "hipMemcpy H2D poses");
-    }
-
-    // all atoms of `n` poses, unrounded, into out (n x n_atoms x 3)
-    void pose_all(size_t n, const double *poses, size_t stride, double *out) {
-        const size_t per_pose = n_atoms() * 3 * sizeof(double);
-        const size_t chunk = std::max<size_t>(1, ld::kClusterWorkspaceBytes / per_pose);
-        upload_poses(n, poses, stride);
-        for (size_t i0 = 0; i0 < n; i0 += chunk) {
-            const size_t m = std::min(chunk, n - i0);
-            d_out.reserve(m * per_pose);
-            const size_t total = m * n_atoms();
-            hipLaunchKernelGGL(ld::complex_pose_xyz, dim3(ld::grid_for(total)), dim3(ld::kPoseThreads), 0, stream, dev,
-                               static_cast<const double *>(d_poses.ptr) + i0 * stride, stride, m, (uint32_t)n_atoms(),
-                               static_cast<double *>(d_out.ptr));
-            ld::hip_check(hipGetLastError(), "complex_pose_xyz launch");
-            ld::hip_check(hipMemcpyAsync(out + i0 * n_atoms() * 3, d_out.ptr, m * per_pose, hipMemcpyDeviceToHost, stream),
-                          "hipMemcpy D2H coordinates");
-        }
-        ld::hip_check(hipStreamSynchronize(stream), "complex_pose_xyz");
-    }
-};
-
-namespace {
-
-template <typename F>
-int guarded_complex(F &&f) {
-    try {
-        f();
-        return LD_OK;
-    } catch (const ld::Error &e) {
-        ld::set_last_error(e.what());
-        return e.code();
-    } catch (const std::bad_alloc &) {
-        ld::set_last_error("out of host memory");
-        return LD_ERR_NOMEM;
-    } catch (const std::exception &e) {
-        ld::set_last_error(e.what());
-        return LD_ERR_INVALID;
-    }
-}
-
-void check_modes(const char *side, const double *modes, size_t len, size_t num_anm, size_t n_atoms) {
-    if (len != num_anm * n_atoms * 3 || (len && !modes))
-        throw ld::Error(LD_ERR_INVALID, std::string(side) + ": " + std::to_string(len) +
-                                            " mode values, expected num_anm x atoms x 3 = " + std::to_string(num_anm * n_atoms * 3));
-}
-
-}  // namespace
-
-extern "C" {
-
-ld_complex *ld_complex_create(const char *receptor_pdb, const char *ligand_pdb, const double *rec_nmodes,
-                              size_t rec_nmodes_len, size_t rec_num_anm, const double *lig_nmodes, size_t lig_nmodes_len,
-                              size_t lig_num_anm) {
-    ld_complex *c = nullptr;
-    int rc = guarded_complex([&] {
-        ld::PdbFile rec = ld::read_pdb_file_order(receptor_pdb);
-        ld::PdbFile lig = ld::read_pdb_file_order(ligand_pdb);
-        check_modes("receptor", rec_nmodes, rec_nmodes_len, rec_num_anm, rec.lines.size());
-        check_modes("ligand", lig_nmodes, lig_nmodes_len, lig_num_anm, lig.lines.size());
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-            throw ld::Error(LD_ERR_DEVICE, "no HIP device available: the analysis path has no CPU fallback");
-        int device = 0;
-        ld::hip_check(hipGetDevice(&device), "hipGetDevice");
-        hipDeviceProp_t prop;
-        ld::hip_check(hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties");
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            throw ld::Error(LD_ERR_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
-
-        std::unique_ptr<ld_complex> h(new ld_complex);
-        h->rec = std::move(rec);
-        h->lig = std::move(lig);
-        ld::hip_check(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking), "hipStreamCreate");
-        ld::hip_check(hipEventCreate(&h->ev0), "hipEventCreate");
-        ld::hip_check(hipEventCreate(&h->ev1), "hipEventCreate");
-        ld::ComplexDevice &d = h->dev;
-        d.n_rec = (int)h->rec.lines.size();
-        d.n_lig = (int)h->lig.lines.size();
-        d.anm_rec = (int)rec_num_anm;
-        d.anm_lig = (int)lig_num_anm;
-        d.rec_xyz = h->arena.upload(h->rec.xyz);
-        d.lig_xyz = h->arena.upload(h->lig.xyz);
-        d.rec_modes = h->arena.upload(std::vector<double>(rec_nmodes, rec_nmodes + rec_nmodes_len));
-        d.lig_modes = h->arena.upload(std::vector<double>(lig_nmodes, lig_nmodes + lig_nmodes_len));
-        h->backbone = h->rec.backbone;
-        for (uint32_t a : h->lig.backbone) h->backbone.push_back(a + (uint32_t)d.n_rec);
-        h->d_backbone = h->arena.upload(h->backbone);
-        std::vector<uint32_t> res_start(h->rec.res_start.begin(), h->rec.res_start.end() - 1);
-        for (uint32_t a : h->lig.res_start) res_start.push_back(a + (uint32_t)d.n_rec);
-        ld::ContactsDevice &k = h->contacts;
-        k.n_atoms = d.n_rec + d.n_lig;
-        k.n_rec_res = (int)h->rec.res_id.size();
-        k.n_lig_res = (int)h->lig.res_id.size();
-        k.n_lig_grp = (k.n_lig_res + ld::kResGroup - 1) / ld::kResGroup;
-        k.res_start = h->arena.upload(res_start);
-        std::vector<uint32_t> res_of_atom = h->rec.res_of_atom;
-        for (uint32_t r : h->lig.res_of_atom) res_of_atom.push_back(r + (uint32_t)k.n_rec_res);
-        k.res_of_atom = h->arena.upload(res_of_atom);
-        k.boxes_in_lds = k.box_bytes() <= ld::kMaxBoxLdsBytes;
-        c = h.release();
-    });
-    return rc == LD_OK ? c : nullptr;
-}
-
-void ld_complex_destroy(ld_complex *c) { delete c; }
-
-size_t ld_complex_pose_len(const ld_complex *c) { return c ? c->pose_len() : 0; }
-
-size_t ld_complex_num_atoms(const ld_complex *c, int side) {
-    if (!c) return 0;
-    return side == 0 ? c->rec.lines.size() : side == 1 ? c->lig.lines.size() : c->backbone.size();
-}
-
-int ld_complex_coordinates(ld_complex *c, size_t n, const double *poses, size_t stride, double *xyz_out) {
-    return guarded_complex([&] {
-        if (!c || (n && !xyz_out)) throw ld::Error(LD_ERR_INVALID, "null argument");
-        ld::check_poses(n, poses, stride, c->pose_len());
-        if (n) c->pose_all(n, poses, stride, xyz_out);
-    });
-}
-
-int ld_complex_cluster(ld_complex *c, size_t n_swarms, size_t n_glowworms, const double *poses, size_t stride,
-                       const double *scoring, double cutoff, int32_t *cluster_of, int32_t *representatives,
-                       uint32_t *n_clusters) {
-    return guarded_complex([&] {
-        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
-        if (n_glowworms == 0 || n_glowworms > (size_t)ld::kMaxGlowworms)
-            throw ld::Error(LD_ERR_INVALID, "n_glowworms must be 1 .. 4096");
-        if (std::isnan(cutoff)) throw ld::Error(LD_ERR_INVALID, "cutoff is NaN");
-        if (c->backbone.empty()) throw ld::Error(LD_ERR_INVALID, "the complex has no atom named CA or P");
-        if (n_swarms == 0) return;
-        if (!scoring || !cluster_of || !representatives || !n_clusters) throw ld::Error(LD_ERR_INVALID, "null argument");
-        const size_t n = n_swarms * n_glowworms;
-        ld::check_poses(n, poses, stride, c->pose_len());
-        for (size_t i = 0; i < n; i++)
-            if (!std::isfinite(scoring[i])) throw ld::Error(LD_ERR_INVALID, "scoring " + std::to_string(i) + " is not finite");
-
-        const int G = (int)n_glowworms, n_bb = (int)c->backbone.size();
-        const size_t per_swarm = (size_t)G * n_bb * 3 * sizeof(int32_t);
-        const size_t chunk = std::max<size_t>(1, ld::kClusterWorkspaceBytes / per_swarm);
-        hipStream_t st = c->stream;
-        c->upload_poses(n, poses, stride);
-        c->d_scores.reserve(n * sizeof(double));
-        ld::hip_check(hipMemcpyAsync(c->d_scores.ptr, scoring, n * sizeof(double), hipMemcpyHostToDevice, st), "hipMemcpy H2D scoring");
-        c->d_ids.reserve(2 * n * sizeof(int32_t) + n_swarms * sizeof(uint32_t) + sizeof(int));
-        int32_t *d_cluster = static_cast<int32_t *>(c->d_ids.ptr);
-        int32_t *d_reps = d_cluster + n;
-        uint32_t *d_count = reinterpret_cast<uint32_t *>(d_reps + n);
-        int *d_overflow = reinterpret_cast<int *>(d_count + n_swarms);
-        ld::hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), st), "hipMemset");
-        c->d_ws.reserve(std::min(chunk, n_swarms) * per_swarm);
-        const double *d_poses = static_cast<const double *>(c->d_poses.ptr);
-        const double *d_scores = static_cast<const double *>(c->d_scores.ptr);
-        ld::hip_check(hipEventRecord(c->ev0, st), "hipEventRecord");
-        for (size_t s0 = 0; s0 < n_swarms; s0 += chunk) {
-            const size_t m = std::min(chunk, n_swarms - s0);
-            hipLaunchKernelGGL(ld::complex_pose_thousandths, dim3(ld::grid_for(m * n_bb * G)), dim3(ld::kPoseThreads), 0, st,
-                               c->dev, d_poses + s0 * G * stride, stride, (int)m, G, c->d_backbone, n_bb,
-                               static_cast<int32_t *>(c->d_ws.ptr), d_overflow);
-            ld::hip_check(hipGetLastError(), "complex_pose_thousandths launch");
-            hipLaunchKernelGGL(ld::complex_bsas, dim3((unsigned)m), dim3(ld::kBsasThreads), 0, st,
-                               static_cast<const int32_t *>(c->d_ws.ptr), d_scores + s0 * G, G, n_bb, cutoff,
-                               d_cluster + s0 * G, d_reps + s0 * G, d_count + s0);
-            ld::hip_check(hipGetLastError(), "complex_bsas launch");
-        }
-        ld::hip_check(hipEventRecord(c->ev1, st), "hipEventRecord");
-        int overflow = 0;
-        ld::hip_check(hipMemcpyAsync(&overflow, d_overflow, sizeof(int), hipMemcpyDeviceToHost, st), "hipMemcpy D2H");
-        ld::hip_check(hipStreamSynchronize(st), "complex_bsas");
-        if (overflow) throw ld::Error(LD_ERR_INVALID, "a posed backbone coordinate is beyond +-2.1e6 A");
-        float ms = 0.0f;
-        ld::hip_check(hipEventElapsedTime(&ms, c->ev0, c->ev1), "hipEventElapsedTime");
-        c->last_kernel_ms = ms;
-        ld::hip_check(hipMemcpy(cluster_of, d_cluster, n * sizeof(int32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
-        ld::hip_check(hipMemcpy(representatives, d_reps, n * sizeof(int32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
-        ld::hip_check(hipMemcpy(n_clusters, d_count, n_swarms * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
-    });
-}
-
-int ld_complex_last_kernel_ms(const ld_complex *c, double *ms_out) {
-    return guarded_complex([&] {
-        if (!c || !ms_out) throw ld::Error(LD_ERR_INVALID, "null argument");
-        *ms_out = c->last_kernel_ms;
-    });
-}
-
-size_t ld_complex_num_residues(const ld_complex *c, int side) {
-    if (!c) return 0;
-    return side == 0 ? c->rec.res_id.size() : side == 1 ? c->lig.res_id.size() : 0;
-}
-
-int ld_complex_residue_id(const ld_complex *c, int side, size_t index, char *buf, size_t buf_len) {
-    return guarded_complex([&] {
-        if (!c || !buf) throw ld::Error(LD_ERR_INVALID, "null argument");
-        if (side != 0 && side != 1) throw ld::Error(LD_ERR_INVALID, "side must be 0 (receptor) or 1 (ligand)");
-        const std::vector<std::string> &ids = side == 0 ? c->rec.res_id : c->lig.res_id;
-        if (index >= ids.size()) throw ld::Error(LD_ERR_INVALID, "residue index out of range");
-        if (ids[index].size() + 1 > buf_len) throw ld::Error(LD_ERR_INVALID, "buffer too short for the residue id");
-        std::memcpy(buf, ids[index].c_str(), ids[index].size() + 1);
-    });
-}
-
-int ld_complex_residue_of_atom(const ld_complex *c, int side, uint32_t *out) {
-    return guarded_complex([&] {
-        if (!c || !out) throw ld::Error(LD_ERR_INVALID, "null argument");
-        if (side != 0 && side != 1) throw ld::Error(LD_ERR_INVALID, "side must be 0 (receptor) or 1 (ligand)");
-        const std::vector<uint32_t> &of = side == 0 ? c->rec.res_of_atom : c->lig.res_of_atom;
-        std::copy(of.begin(), of.end(), out);
-    });
-}
-
-int ld_complex_contacts(ld_complex *c, size_t n, const double *poses, size_t stride, double cutoff, uint32_t *rec_bits,
-                        uint32_t *lig_bits) {
-    return guarded_complex([&] {
-        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
-        const double scaled = cutoff * 1000.0;
-        if (!(scaled > 0.0 && scaled < 30001.0)) throw ld::Error(LD_ERR_INVALID, "cutoff must be 0.001 .. 30 A");
-        const long long C = std::llrint(scaled);
-        if (C < 1 || C > 30000) throw ld::Error(LD_ERR_INVALID, "cutoff must be 0.001 .. 30 A");
-        if (n == 0) return;
-        ld::check_poses(n, poses, stride, c->pose_len());
-        const ld::ContactsDevice &k = c->contacts;
-        const size_t rw = ((size_t)k.n_rec_res + 31) / 32, lw = ((size_t)k.n_lig_res + 31) / 32;
-        if (rw + lw > ld::kMaxContactWords) throw ld::Error(LD_ERR_INVALID, "more than 524288 residues");
-        // a workspace slot a workgroup in flight: the atoms, and the boxes when LDS does not hold them
-        const size_t per_slot = (size_t)k.n_atoms * sizeof(int4) + (k.boxes_in_lds ? 0 : k.box_bytes());
-        const size_t slots = std::min(n, std::min<size_t>(ld::kContactSlots, std::max<size_t>(1, ld::kClusterWorkspaceBytes / per_slot)));
-        const size_t lds = (rw + lw) * sizeof(uint32_t) + (k.boxes_in_lds ? k.box_bytes() : 0);
-        hipStream_t st = c->stream;
-        c->upload_poses(n, poses, stride);
-        c->d_ids.reserve(n * (rw + lw) * sizeof(uint32_t) + sizeof(int));
-        uint32_t *d_rec = static_cast<uint32_t *>(c->d_ids.ptr);
-        uint32_t *d_lig = d_rec + n * rw;
-        int *d_overflow = reinterpret_cast<int *>(d_lig + n * lw);
-        ld::hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), st), "hipMemset");
-        c->d_ws.reserve(slots * per_slot);
-        int4 *d_atoms = static_cast<int4 *>(c->d_ws.ptr);
-        ld::hip_check(hipEventRecord(c->ev0, st), "hipEventRecord");
-        hipLaunchKernelGGL(ld::complex_contacts, dim3((unsigned)slots), dim3(ld::kContactThreads), lds, st, c->dev, k,
-                           static_cast<const double *>(c->d_poses.ptr), stride, n, (uint32_t)(C * C), d_atoms,
-                           reinterpret_cast<int *>(d_atoms + slots * k.n_atoms), d_rec, d_lig, d_overflow);
-        ld::hip_check(hipGetLastError(), "complex_contacts launch");
-        ld::hip_check(hipEventRecord(c->ev1, st), "hipEventRecord");
-        int overflow = 0;
-        ld::hip_check(hipMemcpyAsync(&overflow, d_overflow, sizeof(int), hipMemcpyDeviceToHost, st), "hipMemcpy D2H");
-        ld::hip_check(hipStreamSynchronize(st), "complex_contacts");
-        if (overflow) throw ld::Error(LD_ERR_INVALID, "a posed coordinate is beyond +-1.0e6 A");
-        float ms = 0.0f;
-        ld::hip_check(hipEventElapsedTime(&ms, c->ev0, c->ev1), "hipEventElapsedTime");
-        c->last_kernel_ms = ms;
-        if (rec_bits) ld::hip_check(hipMemcpy(rec_bits, d_rec, n * rw * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
-        if (lig_bits) ld::hip_check(hipMemcpy(lig_bits, d_lig, n * lw * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
-    });
-}
-
-int ld_complex_write_pdb(ld_complex *c, const double *pose, const char *path) {
-    return guarded_complex([&] {
-        if (!c || !pose || !path) throw ld::Error(LD_ERR_INVALID, "null argument");
-        ld::check_poses(1, pose, c->pose_len(), c->pose_len());
-        std::vector<double> xyz(c->n_atoms() * 3);
-        c->pose_all(1, pose, c->pose_len(), xyz.data());
-        std::string text;
-        text.reserve(c->n_atoms() * 82);
-        char buf[32];
-        size_t a = 0;
-        for (const ld::PdbFile *f : {&c->rec, &c->lig})
-            for (const std::string &line : f->lines) {  // line[:30] + "%8.3f%8.3f%8.3f" + line[54:]
-                std::snprintf(buf, sizeof buf, "%8.3f%8.3f%8.3f", xyz[3 * a], xyz[3 * a + 1], xyz[3 * a + 2]);
-                text.append(line, 0, 30).append(buf).append(line, 54, std::string::npos).push_back('\n');
-                a++;
-            }
-        std::FILE *out = std::fopen(path, "wb");
-        if (!out) throw ld::Error(LD_ERR_IO, std::string("cannot write ") + path);
-        const bool ok = std::fwrite(text.data(), 1, text.size(), out) == text.size();
-        if (std::fclose(out) != 0 || !ok) throw ld::Error(LD_ERR_IO, std::string("cannot write ") + path);
-    });
-}
-
-}  // extern "C"

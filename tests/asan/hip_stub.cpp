@@ -1,8 +1,8 @@
 // hip_stub.cpp -- TEST INFRASTRUCTURE for the sanitizer build of the host side (`make asan`).
 //
 // GPU AddressSanitizer is not available on this pool, so the host C++ (PDB / setup.json / npy /
-// DCparams readers, docking-model builders, tile layout, scorer and GSO bookkeeping, both CLIs'
-// error paths) is compiled with g++ -fsanitize=address,undefined and linked against THIS file
+// DCparams readers, docking-model builders, tile layout, scorer and GSO bookkeeping, the analysis
+// half's checks, workspace sizing and PDB writer, both CLIs' error paths) is compiled with g++ -fsanitize=address,undefined and linked against THIS file
 // instead of the HIP runtime and the kernels: device memory is host memory (so every upload,
 // download and workspace size is checked by ASan), streams / events are no-ops, kernel launches do
 // nothing, graph capture is refused (the eager path runs).  Energies are therefore meaningless in
@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "kernels/cluster.hpp"
 #include "kernels/dfire_bm.hpp"
 #include "kernels/dfire_packed.hpp"
 #include "kernels/dfire_tiled.hpp"
@@ -141,6 +142,62 @@ hipError_t launch_bm_gather(const BmLaunch &t, hipStream_t) {
         touch(t.tested_partial + t.first, t.n_poses);
         touch(t.exact_partial + t.first, t.n_poses);
     }
+    return hipSuccess;
+}
+// The analysis launches (kernels/cluster.hpp) likewise: the first and the last element of every buffer a kernel reads or writes,
+// the extents from the launch arguments as the kernels of cluster.hip index them, not from complex.cpp's sizing.
+template <typename T>
+static void peek(const T *base, size_t count) {
+    if (!count) return;
+    volatile T first = base[0], last = base[count - 1];
+    (void)first;
+    (void)last;
+}
+static void peek_complex(const ComplexDevice &m, const double *poses, size_t stride, size_t n_poses) {
+    peek(m.rec_xyz, 3 * (size_t)m.n_rec);
+    peek(m.lig_xyz, 3 * (size_t)m.n_lig);
+    peek(m.rec_modes, (size_t)m.anm_rec * m.n_rec * 3);
+    peek(m.lig_modes, (size_t)m.anm_lig * m.n_lig * 3);
+    if (n_poses) peek(poses, (n_poses - 1) * stride + 7 + m.anm_rec + m.anm_lig);   // row i: poses + i * stride
+}
+hipError_t launch_complex_pose_xyz(const ComplexDevice &m, const double *poses, size_t stride, size_t n, double *out, hipStream_t) {
+    peek_complex(m, poses, stride, n);
+    std::memset(out, 0, n * (size_t)(m.n_rec + m.n_lig) * 3 * sizeof(double));   // ld_complex_write_pdb prints these
+    return hipSuccess;
+}
+hipError_t launch_complex_pose_thousandths(const ComplexDevice &m, const double *poses, size_t stride, int n_swarms, int G,
+                                           const uint32_t *backbone, int n_bb, int32_t *ws, int *overflow, hipStream_t) {
+    peek_complex(m, poses, stride, (size_t)n_swarms * G);   // row s * G + g
+    peek(backbone, (size_t)n_bb);
+    touch(ws, (size_t)n_swarms * n_bb * 3 * G);             // ws[((s * n_bb + b) * 3 + c) * G + g]
+    peek(overflow, 1);                                      // set, never cleared, by the kernel
+    return hipSuccess;
+}
+hipError_t launch_complex_bsas(const int32_t *ws, const double *scoring, int n_swarms, int G, int n_bb, double, int32_t *cluster_of,
+                               int32_t *representatives, uint32_t *n_clusters, hipStream_t) {
+    if (G < 1 || G > kMaxGlowworms) return hipErrorInvalidValue;   // the sort keys' LDS
+    peek(ws, (size_t)n_swarms * n_bb * 3 * G);
+    peek(scoring, (size_t)n_swarms * G);
+    touch(cluster_of, (size_t)n_swarms * G);
+    touch(representatives, (size_t)n_swarms * G);
+    touch(n_clusters, (size_t)n_swarms);
+    return hipSuccess;
+}
+hipError_t launch_complex_contacts(const ComplexDevice &m, const ContactsDevice &d, const double *poses, size_t stride, size_t n, uint32_t,
+                                   size_t slots, int4 *atoms_ws, int *boxes_ws, uint32_t *rec_bits, uint32_t *lig_bits, int *overflow,
+                                   hipStream_t) {
+    const size_t rw = ((size_t)d.n_rec_res + 31) >> 5, lw = ((size_t)d.n_lig_res + 31) >> 5;
+    const size_t n_boxes = (size_t)d.n_rec_res + d.n_lig_res + d.n_lig_grp;
+    if (slots < 1 || slots > (size_t)kContactSlots) return hipErrorInvalidValue;
+    if ((rw + lw) * sizeof(uint32_t) + (d.boxes_in_lds ? n_boxes * 6 * sizeof(int) : 0) > 160 * 1024) return hipErrorInvalidValue;   // a CU's LDS
+    peek_complex(m, poses, stride, n);
+    peek(d.res_start, (size_t)d.n_rec_res + d.n_lig_res + 1);
+    peek(d.res_of_atom, (size_t)d.n_atoms);
+    touch(atoms_ws, slots * d.n_atoms);                               // atoms_ws + blockIdx * n_atoms
+    if (!d.boxes_in_lds) touch(boxes_ws, slots * 6 * n_boxes);        // boxes_ws + blockIdx * 6 * n_boxes
+    touch(rec_bits, n * rw);
+    touch(lig_bits, n * lw);
+    peek(overflow, 1);
     return hipSuccess;
 }
 static size_t packed_prepare_launches = 0;

@@ -5,12 +5,14 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "kernels/cluster.hpp"   // the analysis section sizes its inputs from the constants; every call goes through the C ABI
 #include "lightdock_hip.h"
 
 static int failures = 0;
@@ -45,6 +47,233 @@ static int cli(std::vector<std::string> args) {
     for (auto &a : args) argv.push_back(&a[0]);
     argv.push_back(nullptr);
     return ld_cli_main((int)args.size(), argv.data());
+}
+
+// ---- the analysis half (complex.cpp, host/pdb_file.cpp; ld_complex_*) ---------------------------------------------------------
+static void put(const std::string &path, const std::string &text) {
+    FILE *f = std::fopen(path.c_str(), "wb");
+    std::fwrite(text.data(), 1, text.size(), f);
+    std::fclose(f);
+}
+
+// An ATOM record of exactly 54 columns.
+static std::string atom_line(int serial, const char *name, const char *res, int res_seq, double x, double y, double z) {
+    char buf[96];
+    std::snprintf(buf, sizeof buf, "ATOM  %5d %-4s %3s A%4d    %8.3f%8.3f%8.3f", serial, name, res, res_seq, x, y, z);
+    return buf;
+}
+
+static std::vector<double> identity_poses(size_t n, size_t stride) {
+    std::vector<double> poses(n * stride, 0.0);
+    for (size_t i = 0; i < n; i++) poses[i * stride + 3] = 1.0;
+    return poses;
+}
+
+static size_t count_lines(const std::string &path, size_t *longest) {
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) return 0;
+    size_t lines = 0, len = 0;
+    *longest = 0;
+    for (int ch; (ch = std::fgetc(f)) != EOF;) {
+        if (ch == '\n') {
+            lines++;
+            if (len > *longest) *longest = len;
+            len = 0;
+        } else {
+            len++;
+        }
+    }
+    std::fclose(f);
+    return lines;
+}
+
+static bool refused_create(const std::string &rec, const std::string &lig, const double *rec_nm, size_t rec_len, size_t rec_anm,
+                           const char *message) {
+    ld_complex *c = ld_complex_create(rec.c_str(), lig.c_str(), rec_nm, rec_len, rec_anm, nullptr, 0, 0);
+    if (c) ld_complex_destroy(c);
+    return !c && std::strstr(ld_last_error(), message) != nullptr;
+}
+
+static void analysis(const std::string &rec1, const std::string &lig1, const std::string &scratch) {
+    const double nan = std::nan("");
+    ld_complex *rigid = ld_complex_create(rec1.c_str(), lig1.c_str(), nullptr, 0, 0, nullptr, 0, 0);
+    CHECK(rigid != nullptr && ld_complex_pose_len(rigid) == 7);
+    const size_t nr = ld_complex_num_atoms(rigid, 0), nl = ld_complex_num_atoms(rigid, 1);
+    CHECK(nr == 1615 && nl == 221);
+    if (rigid) ld_complex_destroy(rigid);
+    std::vector<double> rec_nm(2 * nr * 3), lig_nm(3 * nl * 3);
+    for (size_t i = 0; i < rec_nm.size(); i++) rec_nm[i] = 0.01 * (double)((i * 2654435761u) % 200) - 1.0;
+    for (size_t i = 0; i < lig_nm.size(); i++) lig_nm[i] = 0.01 * (double)((i * 40503u) % 200) - 1.0;
+    auto create = [&] { return ld_complex_create(rec1.c_str(), lig1.c_str(), rec_nm.data(), rec_nm.size(), 2, lig_nm.data(), lig_nm.size(), 3); };
+
+    ld_complex *c = create();
+    CHECK(c != nullptr);
+    if (!c) return;
+    const size_t len = ld_complex_pose_len(c);
+    CHECK(len == 12);
+    {   // coordinates (rows further apart than a pose is long), write_pdb, contacts, the residue and atom accessors
+        const size_t n = 5, stride = len + 2;
+        const std::vector<double> poses = identity_poses(n, stride);
+        std::vector<double> xyz(n * (nr + nl) * 3);
+        CHECK(ld_complex_coordinates(c, n, poses.data(), stride, xyz.data()) == LD_OK);
+        CHECK(ld_complex_coordinates(c, 0, nullptr, len, nullptr) == LD_OK);
+        const std::string model = scratch + "/model.pdb";
+        size_t longest = 0;
+        CHECK(ld_complex_write_pdb(c, poses.data(), model.c_str()) == LD_OK && count_lines(model, &longest) == nr + nl);
+        CHECK(ld_complex_write_pdb(c, poses.data(), (scratch + "/no/such/dir/model.pdb").c_str()) == LD_ERR_IO);
+        const size_t rres = ld_complex_num_residues(c, 0), lres = ld_complex_num_residues(c, 1);
+        CHECK(rres > 0 && lres > 0 && ld_complex_num_residues(c, 2) == 0);
+        std::vector<uint32_t> rec_bits(n * ((rres + 31) / 32)), lig_bits(n * ((lres + 31) / 32));
+        CHECK(ld_complex_contacts(c, n, poses.data(), stride, 3.9, rec_bits.data(), lig_bits.data()) == LD_OK);
+        CHECK(ld_complex_contacts(c, n, poses.data(), stride, 3.9, nullptr, nullptr) == LD_OK);
+        double ms = -1.0;
+        CHECK(ld_complex_last_kernel_ms(c, &ms) == LD_OK && ms == 0.0);
+        char id[32];
+        CHECK(ld_complex_residue_id(c, 0, 0, id, sizeof id) == LD_OK && std::strcmp(id, "E.ILE.16") == 0);
+        CHECK(ld_complex_residue_id(c, 1, lres - 1, id, sizeof id) == LD_OK);
+        CHECK(ld_complex_residue_id(c, 0, 0, id, std::strlen("E.ILE.16")) == LD_ERR_INVALID);   // no room for the terminator
+        CHECK(ld_complex_residue_id(c, 0, rres, id, sizeof id) == LD_ERR_INVALID);
+        CHECK(ld_complex_residue_id(c, 2, 0, id, sizeof id) == LD_ERR_INVALID);
+        CHECK(ld_complex_residue_id(c, 0, 0, nullptr, 0) == LD_ERR_INVALID);
+        std::vector<uint32_t> of(nr);
+        CHECK(ld_complex_residue_of_atom(c, 0, of.data()) == LD_OK && of.back() == rres - 1);
+        of.resize(nl);
+        CHECK(ld_complex_residue_of_atom(c, 1, of.data()) == LD_OK && of.back() == lres - 1);
+        CHECK(ld_complex_residue_of_atom(c, 2, of.data()) == LD_ERR_INVALID);
+        CHECK(ld_complex_residue_of_atom(c, 0, nullptr) == LD_ERR_INVALID);
+    }
+    {   // clustering: swarms of kMaxGlowworms, two more than one chunk of the workspace holds, on a handle of its own (its buffers'
+        // first reservations are this call's)
+        ld_complex *k = create();
+        CHECK(k != nullptr);
+        const size_t G = ld::kMaxGlowworms, n_bb = ld_complex_num_atoms(c, 2);
+        CHECK(n_bb > 0);
+        const size_t chunk = ld::kClusterWorkspaceBytes / (G * n_bb * 3 * sizeof(int32_t)), n_swarms = chunk + 2;
+        CHECK(chunk >= 1);
+        if (k && n_bb && chunk) {
+            const std::vector<double> poses = identity_poses(n_swarms * G, len);
+            std::vector<double> scoring(n_swarms * G, 1.0);
+            std::vector<int32_t> cluster_of(n_swarms * G), reps(n_swarms * G);
+            std::vector<uint32_t> count(n_swarms);
+            CHECK(ld_complex_cluster(k, n_swarms, G, poses.data(), len, scoring.data(), 4.0, cluster_of.data(), reps.data(), count.data()) == LD_OK);
+            CHECK(ld_complex_cluster(k, 3, 50, poses.data(), len, scoring.data(), 4.0, cluster_of.data(), reps.data(), count.data()) == LD_OK);
+            CHECK(ld_complex_cluster(k, 0, 50, nullptr, len, nullptr, 4.0, nullptr, nullptr, nullptr) == LD_OK);
+        }
+        if (k) ld_complex_destroy(k);
+    }
+    {   // every refusal of a call, by status
+        std::vector<double> poses = identity_poses(4, len), scoring(4, 1.0), xyz(4 * (nr + nl) * 3);
+        std::vector<int32_t> cluster_of(4), reps(4);
+        std::vector<uint32_t> count(4), bits(4 * 64);
+        auto cluster = [&](ld_complex *h, size_t G, const double *p, size_t stride, const double *s, double cutoff) {
+            return ld_complex_cluster(h, 2, G, p, stride, s, cutoff, cluster_of.data(), reps.data(), count.data());
+        };
+        CHECK(cluster(c, 2, poses.data(), len, scoring.data(), 4.0) == LD_OK);
+        // null arguments
+        CHECK(ld_complex_pose_len(nullptr) == 0 && ld_complex_num_atoms(nullptr, 0) == 0 && ld_complex_num_residues(nullptr, 0) == 0);
+        CHECK(ld_complex_coordinates(nullptr, 4, poses.data(), len, xyz.data()) == LD_ERR_INVALID);
+        CHECK(ld_complex_coordinates(c, 4, poses.data(), len, nullptr) == LD_ERR_INVALID);
+        CHECK(ld_complex_coordinates(c, 4, nullptr, len, xyz.data()) == LD_ERR_INVALID);
+        CHECK(cluster(nullptr, 2, poses.data(), len, scoring.data(), 4.0) == LD_ERR_INVALID);
+        CHECK(cluster(c, 2, nullptr, len, scoring.data(), 4.0) == LD_ERR_INVALID);
+        CHECK(cluster(c, 2, poses.data(), len, nullptr, 4.0) == LD_ERR_INVALID);
+        CHECK(ld_complex_cluster(c, 2, 2, poses.data(), len, scoring.data(), 4.0, nullptr, reps.data(), count.data()) == LD_ERR_INVALID);
+        CHECK(ld_complex_contacts(nullptr, 4, poses.data(), len, 3.9, bits.data(), bits.data()) == LD_ERR_INVALID);
+        CHECK(ld_complex_contacts(c, 4, nullptr, len, 3.9, bits.data(), bits.data()) == LD_ERR_INVALID);
+        CHECK(ld_complex_write_pdb(nullptr, poses.data(), (scratch + "/x.pdb").c_str()) == LD_ERR_INVALID);
+        CHECK(ld_complex_write_pdb(c, nullptr, (scratch + "/x.pdb").c_str()) == LD_ERR_INVALID);
+        CHECK(ld_complex_write_pdb(c, poses.data(), nullptr) == LD_ERR_INVALID);
+        double ms = 0.0;
+        CHECK(ld_complex_last_kernel_ms(nullptr, &ms) == LD_ERR_INVALID && ld_complex_last_kernel_ms(c, nullptr) == LD_ERR_INVALID);
+        ld_complex_destroy(nullptr);
+        // poses: stride below the pose length, a NaN, a zero quaternion -- through each call that takes poses
+        for (int what = 0; what < 3; what++) {
+            std::vector<double> bad = poses;
+            size_t stride = len;
+            if (what == 0) stride = len - 1;
+            if (what == 1) bad[3 * len + len - 1] = nan;   // the last mode amplitude of the last pose
+            if (what == 2) bad[2 * len + 3] = 0.0;
+            CHECK(ld_complex_coordinates(c, 4, bad.data(), stride, xyz.data()) == LD_ERR_INVALID);
+            CHECK(cluster(c, 2, bad.data(), stride, scoring.data(), 4.0) == LD_ERR_INVALID);
+            CHECK(ld_complex_contacts(c, 4, bad.data(), stride, 3.9, bits.data(), bits.data()) == LD_ERR_INVALID);
+            if (what) CHECK(ld_complex_write_pdb(c, bad.data() + (what == 1 ? 3 : 2) * len, (scratch + "/x.pdb").c_str()) == LD_ERR_INVALID);
+        }
+        // clustering: the glowworm count, the cutoff, the scoring
+        CHECK(cluster(c, 0, poses.data(), len, scoring.data(), 4.0) == LD_ERR_INVALID);
+        CHECK(cluster(c, (size_t)ld::kMaxGlowworms + 1, poses.data(), len, scoring.data(), 4.0) == LD_ERR_INVALID);
+        CHECK(cluster(c, 2, poses.data(), len, scoring.data(), nan) == LD_ERR_INVALID);
+        for (double v : {nan, (double)INFINITY, -(double)INFINITY}) {
+            std::vector<double> bad = scoring;
+            bad[3] = v;
+            CHECK(cluster(c, 2, poses.data(), len, bad.data(), 4.0) == LD_ERR_INVALID);
+        }
+        // contacts: cutoffs outside 0.001 .. 30 A, whichever way their thousandths round; the ends themselves pass
+        for (double cutoff : {0.0, 0.0004, 30.001, 31.0, -1.0, nan})
+            CHECK(ld_complex_contacts(c, 4, poses.data(), len, cutoff, bits.data(), bits.data()) == LD_ERR_INVALID);
+        for (double cutoff : {0.001, 30.0})
+            CHECK(ld_complex_contacts(c, 4, poses.data(), len, cutoff, bits.data(), bits.data()) == LD_OK);
+    }
+    ld_complex_destroy(c);
+
+    {   // files and modes a handle is refused for
+        const std::string bad = scratch + "/bad_complex.pdb", good = atom_line(1, " CA", "ALA", 1, 1.0, 2.0, 3.0);
+        CHECK(good.size() == 54);
+        CHECK(refused_create(scratch + "/missing.pdb", lig1, nullptr, 0, 0, "cannot open PDB file"));
+        CHECK(refused_create(rec1, scratch + "/missing.pdb", nullptr, 0, 0, "cannot open PDB file"));
+        put(bad, "");
+        CHECK(refused_create(bad, lig1, nullptr, 0, 0, "no ATOM/HETATM records"));
+        put(bad, "REMARK nothing else\nEND\n");
+        CHECK(refused_create(bad, lig1, nullptr, 0, 0, "no ATOM/HETATM records"));
+        put(bad, good + "\n" + good.substr(0, 53) + "\n");
+        CHECK(refused_create(bad, lig1, nullptr, 0, 0, "shorter than 54 columns"));
+        put(bad, "ATOM\n");
+        CHECK(refused_create(rec1, bad, nullptr, 0, 0, "no ATOM/HETATM records"));   // "ATOM" alone is no record
+        put(bad, "HETATM\n");
+        CHECK(refused_create(rec1, bad, nullptr, 0, 0, "shorter than 54 columns"));
+        put(bad, good.substr(0, 38) + "   abc  " + good.substr(46) + "\n");
+        CHECK(refused_create(bad, lig1, nullptr, 0, 0, "unreadable coordinate"));
+        CHECK(refused_create(rec1, lig1, rec_nm.data(), rec_nm.size() - 1, 2, "mode values"));
+        CHECK(refused_create(rec1, lig1, rec_nm.data(), rec_nm.size(), 3, "mode values"));
+        CHECK(refused_create(rec1, lig1, nullptr, rec_nm.size(), 2, "mode values"));
+        ld_complex *none = ld_complex_create(nullptr, lig1.c_str(), nullptr, 0, 0, nullptr, 0, 0);
+        CHECK(none == nullptr);
+    }
+    {   // "\r\n" line ends, records of exactly 54 columns, records that are not atoms: one line out per record in, no '\r'
+        std::string text = "REMARK a file from elsewhere\r\n";
+        for (int a = 0; a < 7; a++) text += atom_line(a + 1, a % 2 ? " CA" : " N", "GLY", 1 + a / 2, a, 2.0 * a, -a) + "\r\n";
+        text += "TER\r\nEND\r\n";
+        const std::string crlf = scratch + "/crlf.pdb", model = scratch + "/crlf_model.pdb";
+        put(crlf, text);
+        ld_complex *w = ld_complex_create(crlf.c_str(), crlf.c_str(), nullptr, 0, 0, nullptr, 0, 0);
+        CHECK(w != nullptr && ld_complex_num_atoms(w, 0) == 7 && ld_complex_num_atoms(w, 2) == 6 && ld_complex_num_residues(w, 1) == 4);
+        if (w) {
+            const std::vector<double> pose = identity_poses(1, 7);
+            size_t longest = 0;
+            CHECK(ld_complex_write_pdb(w, pose.data(), model.c_str()) == LD_OK);
+            CHECK(count_lines(model, &longest) == 14 && longest == 54);
+            ld_complex_destroy(w);
+        }
+    }
+    {   // residue boxes that do not fit kMaxBoxLdsBytes (24 bytes a box: one-atom residues, more than 1706 of them), so that a
+        // workspace slot also holds the boxes; more poses than kContactSlots, so that slots are reused
+        const int n_rec = 1800, n_lig = 12;
+        CHECK((size_t)(n_rec + n_lig + (n_lig + ld::kResGroup - 1) / ld::kResGroup) * 24 > ld::kMaxBoxLdsBytes);
+        std::string rec, lig;
+        for (int a = 0; a < n_rec; a++) rec += atom_line(a + 1, " CA", "ALA", a + 1, a % 30, (a / 30) % 30, a / 900) + "\n";
+        for (int a = 0; a < n_lig; a++) lig += atom_line(a + 1, " P", "  A", a + 1, 40.0 + a, 0.0, 0.0) + "\n";
+        put(scratch + "/wide_rec.pdb", rec);
+        put(scratch + "/wide_lig.pdb", lig);
+        ld_complex *w = ld_complex_create((scratch + "/wide_rec.pdb").c_str(), (scratch + "/wide_lig.pdb").c_str(), nullptr, 0, 0, nullptr, 0, 0);
+        CHECK(w != nullptr && ld_complex_num_residues(w, 0) == (size_t)n_rec && ld_complex_num_residues(w, 1) == (size_t)n_lig);
+        if (w) {
+            const size_t n = ld::kContactSlots + 6;
+            const std::vector<double> poses = identity_poses(n, 7);
+            std::vector<uint32_t> rec_bits(n * ((n_rec + 31) / 32)), lig_bits(n * ((n_lig + 31) / 32));
+            CHECK(ld_complex_contacts(w, n, poses.data(), 7, 5.0, rec_bits.data(), lig_bits.data()) == LD_OK);
+            CHECK(ld_complex_contacts(w, 2, poses.data(), 7, 5.0, rec_bits.data(), lig_bits.data()) == LD_OK);   // fewer poses than slots
+            ld_complex_destroy(w);
+        }
+    }
 }
 
 int main(int argc, char **argv) {
@@ -234,6 +463,8 @@ int main(int argc, char **argv) {
     }
     CHECK(ld_scorer_create_from_pdb(7, rec1.c_str(), lig1.c_str(), nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, nullptr, 0,
                                     nullptr, 0, 0, 0, table.data()) == nullptr);
+
+    analysis(rec1, lig1, scratch);
 
     // ---- the CLI (src/bin/lightdock-rust.rs:77-333): usage errors return 0, panics 101 ---------------
     CHECK(chdir(scratch.c_str()) == 0);

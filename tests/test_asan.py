@@ -5,7 +5,11 @@ available -- GPU AddressSanitizer is not, on this pool).
     ASan + UBSan against tests/asan/hip_stub.cpp (device memory = host memory, kernels = no-ops) and
     driven through the C ABI by tests/asan/host_check.cpp: PDB / setup.json / npy / DCparams readers,
     model builders, tile layout, LUT builders, scorer and GSO bookkeeping, gso_*.out writers, the
-    CLI's usage-error and panic paths;
+    CLI's usage-error and panic paths; and the analysis half (csrc/complex.cpp, csrc/host/pdb_file.cpp):
+    the file-order PDB reader on "\r\n" files and records of exactly 54 columns, coordinates / write_pdb /
+    contacts (residue boxes in and out of LDS, more poses than workspace slots) / cluster (more swarms
+    than one workspace chunk holds) with launch stubs that touch both ends of every buffer a kernel
+    reads or writes, and every refusal of ld_complex_* by status;
   * the oracle CLI, same flags, a few GSO steps of the 1azp example.
 """
 import os
