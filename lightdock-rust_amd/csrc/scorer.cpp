@@ -169,54 +169,18 @@ void check_molecule(const ld_molecule &m, int method, const char *who, bool use_
     if (m.num_anm > 64) throw Error(LD_ERR_INVALID, w + ": more than 64 ANM modes");
 }
 
-}  // namespace
-
-void Scorer::upload_molecule(const ld_molecule &m, bool is_receptor, DeviceMolecule &dev, HostMolecule &host,
-                             std::vector<uint32_t> &group_offsets, std::vector<uint32_t> &group_slots,
-                             std::vector<uint32_t> &membrane_slots) {
-    const size_t n = m.n_atoms;
-    const size_t n_pad = (n + 63) / 64 * 64;
-    dev.n = (int)n;
-    dev.n_pad = (int)n_pad;
-
-    host.coordinates.assign(m.coordinates, m.coordinates + 3 * n);
-    std::vector<double> x(n_pad, 0.0), y(n_pad, 0.0), z(n_pad, 0.0);
-    for (size_t i = 0; i < n; i++) {
-        x[i] = m.coordinates[3 * i];
-        y[i] = m.coordinates[3 * i + 1];
-        z[i] = m.coordinates[3 * i + 2];
-    }
-    dev.x = arena_.upload(x);
-    dev.y = arena_.upload(y);
-    dev.z = arena_.upload(z);
-
-    if (method_ == LD_METHOD_DFIRE) {
-        host.dfire_types.assign(m.dfire_types, m.dfire_types + n);
-        std::vector<uint32_t> t(n_pad, 0);
-        // potential[atoma*169*20 + atomb*20 + bin] (src/dfire.rs:338): receptor carries the
-        // row base, ligand the column base.
-        for (size_t i = 0; i < n; i++) t[i] = m.dfire_types[i] * (is_receptor ? kDfireRowStride : 20u);
-        dev.tindex = arena_.upload(t);
-    } else {
-        host.ele_charges.assign(m.ele_charges, m.ele_charges + n);
-        host.vdw_charges.assign(m.vdw_charges, m.vdw_charges + n);
-        host.vdw_radii.assign(m.vdw_radii, m.vdw_radii + n);
-        dev.charge = arena_.upload(host.ele_charges, n_pad);
-        {   // the kernel multiplies sqrt(eps_i) * sqrt(eps_j) instead of sqrt(eps_i * eps_j) per pair
-            std::vector<double> root(host.vdw_charges);
-            for (double &v : root) v = std::sqrt(v);
-            dev.well_depth = arena_.upload(root, n_pad);
-        }
-        dev.radius = arena_.upload(host.vdw_radii, n_pad);
-    }
-
-    // Interface flags are only needed for restraint atoms and membrane beads
-    // (src/scoring.rs:21-47): give each such atom one bit ("slot") of the per-pose flag set.
-    std::vector<int32_t> slot(n_pad, -1);
+// Interface flags are only needed for restraint atoms and membrane beads (src/scoring.rs:21-47): each such atom gets one bit
+// ("slot") of the per-pose flag set.  Fills the side's facts and the restraint-group CSR / membrane beads over slots that
+// TailTables is uploaded from.  No HIP call: every route reads the same slots.
+void slot_molecule(const ld_molecule &m, bool use_anm, SideFacts &facts, std::vector<uint32_t> &group_offsets,
+                   std::vector<uint32_t> &group_slots, std::vector<uint32_t> &membrane_slots) {
+    facts.n = (int)m.n_atoms;
+    facts.num_anm = use_anm ? (int)m.num_anm : 0;
+    facts.slot.assign(m.n_atoms, -1);
     uint32_t next = 0;
     auto slot_of = [&](uint32_t atom) {
-        if (slot[atom] < 0) slot[atom] = (int32_t)next++;
-        return (uint32_t)slot[atom];
+        if (facts.slot[atom] < 0) facts.slot[atom] = (int32_t)next++;
+        return (uint32_t)facts.slot[atom];
     };
     group_offsets.assign(1, 0);
     group_slots.clear();
@@ -227,13 +191,68 @@ void Scorer::upload_molecule(const ld_molecule &m, bool is_receptor, DeviceMolec
     }
     membrane_slots.clear();
     for (size_t k = 0; k < m.n_membrane; k++) membrane_slots.push_back(slot_of(m.membrane[k]));
-    dev.slot = arena_.upload(slot);
-    dev.flag_words = (int)((next + 31) / 32);
-    (is_receptor ? host_slot_rec_ : host_slot_lig_).assign(slot.begin(), slot.begin() + (long)n);
+    facts.flag_words = (int)((next + 31) / 32);
+}
 
-    dev.num_anm = 0;
-    dev.modes = nullptr;
-    if (use_anm_ && m.num_anm > 0) {
+HostMolecule host_molecule_of(const ld_molecule &m, int method) {
+    const size_t n = m.n_atoms;
+    HostMolecule host;
+    host.coordinates.assign(m.coordinates, m.coordinates + 3 * n);
+    if (method == LD_METHOD_DFIRE) {
+        host.dfire_types.assign(m.dfire_types, m.dfire_types + n);
+    } else {
+        host.ele_charges.assign(m.ele_charges, m.ele_charges + n);
+        host.vdw_charges.assign(m.vdw_charges, m.vdw_charges + n);
+        host.vdw_radii.assign(m.vdw_radii, m.vdw_radii + n);
+    }
+    return host;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------
+// All-pairs path (kernels/pose_energy.hpp): both molecules SoA, padded to whole waves; DFIRE reads the potential in the
+// reference's layout through the cell LUT.
+// ---------------------------------------------------------------------------------------
+DeviceMolecule AllPairsPath::upload_molecule(const ld_molecule &m, const SideFacts &facts, bool is_receptor) {
+    const size_t n = m.n_atoms;
+    const size_t n_pad = (n + 63) / 64 * 64;
+    DeviceMolecule dev;
+    dev.n = (int)n;
+    dev.n_pad = (int)n_pad;
+
+    std::vector<double> x(n_pad, 0.0), y(n_pad, 0.0), z(n_pad, 0.0);
+    for (size_t i = 0; i < n; i++) {
+        x[i] = m.coordinates[3 * i];
+        y[i] = m.coordinates[3 * i + 1];
+        z[i] = m.coordinates[3 * i + 2];
+    }
+    dev.x = arena_.upload(x);
+    dev.y = arena_.upload(y);
+    dev.z = arena_.upload(z);
+
+    if (model_.method == LD_METHOD_DFIRE) {
+        std::vector<uint32_t> t(n_pad, 0);
+        // potential[atoma*169*20 + atomb*20 + bin] (src/dfire.rs:338): receptor carries the
+        // row base, ligand the column base.
+        for (size_t i = 0; i < n; i++) t[i] = m.dfire_types[i] * (is_receptor ? kDfireRowStride : 20u);
+        dev.tindex = arena_.upload(t);
+    } else {
+        dev.charge = arena_.upload(std::vector<double>(m.ele_charges, m.ele_charges + n), n_pad);
+        {   // the kernel multiplies sqrt(eps_i) * sqrt(eps_j) instead of sqrt(eps_i * eps_j) per pair
+            std::vector<double> root(m.vdw_charges, m.vdw_charges + n);
+            for (double &v : root) v = std::sqrt(v);
+            dev.well_depth = arena_.upload(root, n_pad);
+        }
+        dev.radius = arena_.upload(std::vector<double>(m.vdw_radii, m.vdw_radii + n), n_pad);
+    }
+
+    std::vector<int32_t> slot(facts.slot);
+    slot.resize(n_pad, -1);
+    dev.slot = arena_.upload(slot);
+    dev.flag_words = facts.flag_words;
+
+    if (facts.num_anm > 0) {
         // (mode, atom, xyz) -> [mode][xyz][n_pad]
         std::vector<double> modes(m.num_anm * 3 * n_pad, 0.0);
         for (size_t k = 0; k < m.num_anm; k++)
@@ -242,6 +261,48 @@ void Scorer::upload_molecule(const ld_molecule &m, bool is_receptor, DeviceMolec
         dev.modes = arena_.upload(modes);
         dev.num_anm = (int)m.num_anm;
     }
+    return dev;
+}
+
+AllPairsPath::AllPairsPath(const ld_scorer_desc &desc, const SideFacts &rec, const SideFacts &lig, const double *bin_step, double iface_d2,
+                           int method, bool use_anm) {
+    PairLaunch &P = model_;
+    P.method = method;
+    P.use_anm = use_anm ? 1 : 0;
+    P.rec = upload_molecule(desc.receptor, rec, true);
+    P.lig = upload_molecule(desc.ligand, lig, false);
+    if (method == LD_METHOD_DFIRE) {
+        P.table = arena_.upload(std::vector<double>(desc.potential, desc.potential + LD_DFIRE_TABLE_LEN));
+        P.lut = arena_.upload(build_dfire_binning().lut);
+    }
+    P.bin_step = bin_step;
+    P.iface_d2 = iface_d2;
+
+    // Receptor chunking: <= 512 (DFIRE) / 256 (DNA) atoms per workgroup = 16 KiB of LDS
+    // records, balanced over the chunks.  Fixed per scorer so that a pose's energy does not
+    // depend on the batch it is evaluated in.
+    int max_chunk = method == LD_METHOD_DFIRE ? 512 : 256;
+    if (const char *e = std::getenv("LIGHTDOCK_CHUNK_ATOMS")) {
+        int v = std::atoi(e);
+        if (v >= 64 && v <= 2048) max_chunk = v;
+    }
+    P.n_chunks = (P.rec.n + max_chunk - 1) / max_chunk;
+    P.chunk_atoms = (P.rec.n + P.n_chunks - 1) / P.n_chunks;
+    const int n_groups = (P.lig.n + 63) / 64;
+    P.split_j = (n_groups % kWaves != 0 && n_groups < 4 * kWaves) ? 1 : 0;
+}
+
+void AllPairsPath::run(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, const uint32_t *, const uint32_t *,
+                       const PoseOutputs &out, hipStream_t stream) {
+    PairLaunch p = model_;
+    p.poses = d_poses;
+    p.stride = stride;
+    p.active = d_active;
+    p.n_poses = n;
+    p.partial = out.partial;
+    p.flags = out.flags;
+    p.count_partial = out.count_partial;
+    hip_check(launch_pair_kernel(p, stream), "launch pose_energy_pairs");
 }
 
 Scorer::Scorer(const ld_scorer_desc &desc) {
@@ -274,8 +335,10 @@ Scorer::Scorer(const ld_scorer_desc &desc) {
     stream_ = own_stream_;
 
     std::vector<uint32_t> rgo, rgs, rms, lgo, lgs, lms;
-    upload_molecule(desc.receptor, true, pair_.rec, host_rec_, rgo, rgs, rms);
-    upload_molecule(desc.ligand, false, pair_.lig, host_lig_, lgo, lgs, lms);
+    slot_molecule(desc.receptor, use_anm_, rec_, rgo, rgs, rms);
+    slot_molecule(desc.ligand, use_anm_, lig_, lgo, lgs, lms);
+    host_rec_ = host_molecule_of(desc.receptor, method_);
+    host_lig_ = host_molecule_of(desc.ligand, method_);
     // src/scoring.rs:38-47 is only ever applied to the receptor (src/dfire.rs:357); ligand
     // beads get a slot but no reader.
     tail_.n_rec_groups = (int)rgo.size() - 1;
@@ -287,31 +350,13 @@ Scorer::Scorer(const ld_scorer_desc &desc) {
     tail_.lig_group_slots = arena_.upload(lgs);
     tail_.membrane_slots = arena_.upload(rms);
 
-    pair_.method = method_;
-    pair_.use_anm = use_anm_ ? 1 : 0;
+    // what every DFIRE route reads of the binning: the exact first d2 of each bin, and the interface distance
+    const double *bin_step = nullptr;
+    double iface_d2 = 3.9 * 3.9;  // INTERFACE_CUTOFF2, src/constants.rs:15
     if (method_ == LD_METHOD_DFIRE) {
-        std::vector<double> table(desc.potential, desc.potential + LD_DFIRE_TABLE_LEN);
-        pair_.table = arena_.upload(table);
-        const DfireBinning binning = build_dfire_binning();
-        pair_.lut = arena_.upload(binning.lut);
-        pair_.bin_step = arena_.upload(binning.step);
-        pair_.iface_d2 = dfire_interface_d2();
-    } else {
-        pair_.iface_d2 = 3.9 * 3.9;  // INTERFACE_CUTOFF2, src/constants.rs:15
+        bin_step = arena_.upload(build_dfire_binning().step);
+        iface_d2 = dfire_interface_d2();
     }
-
-    // Receptor chunking: <= 512 (DFIRE) / 256 (DNA) atoms per workgroup = 16 KiB of LDS
-    // records, balanced over the chunks.  Fixed per scorer so that a pose's energy does not
-    // depend on the batch it is evaluated in.
-    int max_chunk = method_ == LD_METHOD_DFIRE ? 512 : 256;
-    if (const char *e = std::getenv("LIGHTDOCK_CHUNK_ATOMS")) {
-        int v = std::atoi(e);
-        if (v >= 64 && v <= 2048) max_chunk = v;
-    }
-    pair_.n_chunks = (pair_.rec.n + max_chunk - 1) / max_chunk;
-    pair_.chunk_atoms = (pair_.rec.n + pair_.n_chunks - 1) / pair_.n_chunks;
-    const int n_groups = (pair_.lig.n + 63) / 64;
-    pair_.split_j = (n_groups % kWaves != 0 && n_groups < 4 * kWaves) ? 1 : 0;
 
     if (method_ == LD_METHOD_DFIRE) {
         // LIGHTDOCK_DFIRE_KERNEL: "bm" (and any other value, the default): the block-major path (kernels/dfire_bm.hpp; its ANM
@@ -325,12 +370,13 @@ Scorer::Scorer(const ld_scorer_desc &desc) {
         PackedFrame frame;
         if (kernel != "allpairs") build_tiles(desc);
         if (kernel != "allpairs" && packed_accepts(desc.receptor, &frame)) {   // choose first, then build the one route that runs
-            const RouteInputs in{desc, tiles_, pair_.rec.flag_words, pair_.bin_step, pair_.iface_d2, use_anm_, latency, n_cus_, stream_};
+            const RouteInputs in{desc, tiles_, rec_.flag_words, bin_step, iface_d2, use_anm_, latency, n_cus_, stream_};
             if (kernel != "packed" && (kernel == "bm" || !latency)) bm_ = BlockMajorPath::build(in);
             if (!bm_) packed_.reset(new PackedPath(in, frame));
             route_ = bm_ ? PairRoute::block_major : PairRoute::packed;
         }
     }
+    if (route_ == PairRoute::all_pairs) all_pairs_.reset(new AllPairsPath(desc, rec_, lig_, bin_step, iface_d2, method_, use_anm_));
 }
 
 // Tile-ordered SoA copy of one molecule (host/spatial_order.hpp); padding atoms at -1e30
@@ -344,7 +390,7 @@ void Scorer::upload_tiled_molecule(const ld_molecule &m, bool is_receptor, Tiled
     std::vector<double> x(np, is_receptor ? -1.0e30 : 1.0e30), y(np, 0.0), z(np, 0.0);
     std::vector<uint32_t> t(np, 0);
     std::vector<int32_t> slot(np, -1);
-    const std::vector<int32_t> &hslot = is_receptor ? host_slot_rec_ : host_slot_lig_;
+    const std::vector<int32_t> &hslot = (is_receptor ? rec_ : lig_).slot;
     // type numbers as the patch layout of the potential wants them (bonded atoms paired up)
     perm = layout.type_perm;
     for (size_t i = 0; i < np; i++) {
@@ -404,7 +450,7 @@ void Scorer::build_tiles(const ld_scorer_desc &desc) {
     T.lig_view.slot = lig.slot;
     T.lig_view.num_anm = lig.num_anm;
     T.lig_view.modes = lig.modes;
-    T.lig_view.flag_words = pair_.lig.flag_words;
+    T.lig_view.flag_words = lig_.flag_words;
     {   // potential re-laid out in 2 x 2 x 4 patches, see dfire_tiled.hpp
         std::vector<double> t2(kTiledTableDoubles, 0.0);
         for (uint32_t l = 0; l < 168; l++)
@@ -1367,7 +1413,7 @@ Scorer::~Scorer() {
         (void)hipStreamSynchronize(own_stream_);
         (void)hipStreamDestroy(own_stream_);
     }
-    // (the workspace buffers and the block-major path free themselves after this body, behind the synchronisation above)
+    // (the workspace buffers and the route's object free themselves after this body, behind the synchronisation above)
 }
 
 uint64_t Scorer::workspace_generation() const {
@@ -1378,11 +1424,11 @@ uint64_t Scorer::workspace_generation() const {
 }
 
 size_t Scorer::partials_per_pose() const {  // (dfire_bm_gather leaves one partial per pose)
-    return bm_ ? 1 : packed_ ? packed_->partials_per_pose() : (size_t)pair_.n_chunks;
+    return bm_ ? 1 : packed_ ? packed_->partials_per_pose() : all_pairs_->partials_per_pose();
 }
 
 void Scorer::reserve_workspace(size_t n_poses, bool counts) {
-    const size_t words = (size_t)(pair_.rec.flag_words + pair_.lig.flag_words);
+    const size_t words = (size_t)(rec_.flag_words + lig_.flag_words);
     const size_t chunks = partials_per_pose();
     ws_partial_.reserve(n_poses * chunks * 2 * sizeof(double));
     ws_flags_.reserve(std::max<size_t>(n_poses * words * sizeof(uint32_t), 16));
@@ -1420,7 +1466,7 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
         out.tested_partial = static_cast<uint32_t *>(ws_tested_.ptr);
         out.exact_partial = static_cast<uint32_t *>(ws_exact_.ptr);
     }
-    const size_t words = (size_t)(pair_.rec.flag_words + pair_.lig.flag_words);
+    const size_t words = (size_t)(rec_.flag_words + lig_.flag_words);
     // (the block-major path clears a pose's flag words in dfire_bm_pose: one launch less per step)
     if (words > 0 && route_ != PairRoute::block_major) hip_check(hipMemsetAsync(out.flags, 0, n * words * sizeof(uint32_t), stream_), "hipMemsetAsync(flags)");
     const bool timing = timing_ && !capturing_;
@@ -1448,18 +1494,9 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
     case PairRoute::packed:
         packed_->run(n, d_poses, stride, d_active, d_list, d_count, out, stream_);
         break;
-    case PairRoute::all_pairs: {
-        PairLaunch p = pair_;
-        p.poses = d_poses;
-        p.stride = stride;
-        p.active = d_active;
-        p.n_poses = n;
-        p.partial = out.partial;
-        p.flags = out.flags;
-        p.count_partial = out.count_partial;
-        hip_check(launch_pair_kernel(p, stream_), "launch pose_energy_pairs");
+    case PairRoute::all_pairs:
+        all_pairs_->run(n, d_poses, stride, d_active, d_list, d_count, out, stream_);
         break;
-    }
     }
     if (timing) {
         hip_check(hipEventRecord(events_[events_used_].second, stream_), "hipEventRecord");
@@ -1469,8 +1506,8 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
     FinishLaunch f;
     f.method = method_;
     f.n_chunks = (int)partials_per_pose();
-    f.rec_flag_words = pair_.rec.flag_words;
-    f.lig_flag_words = pair_.lig.flag_words;
+    f.rec_flag_words = rec_.flag_words;
+    f.lig_flag_words = lig_.flag_words;
     f.tail = tail_;
     f.partial = out.partial;
     f.flags = out.flags;
@@ -1545,16 +1582,16 @@ void Scorer::kernel_info(ld_kernel_info *out) const {
     case PairRoute::all_pairs:
         out->pair_kernel_name = pair_kernel_name(method_);
         out->block_threads = (uint32_t)kBlockThreads;
-        out->receptor_chunks = (uint32_t)pair_.n_chunks;
-        out->lds_bytes = (uint32_t)pair_kernel_lds_bytes(pair_);
+        out->receptor_chunks = (uint32_t)all_pairs_->model().n_chunks;
+        out->lds_bytes = (uint32_t)pair_kernel_lds_bytes(all_pairs_->model());
         break;
     }
-    out->pair_tests_per_pose = (uint64_t)pair_.rec.n * (uint64_t)pair_.lig.n;
+    out->pair_tests_per_pose = (uint64_t)rec_.n * (uint64_t)lig_.n;
     // DFIRE 26 B/atom (3 f64 + u16 type), DNA 48 B/atom (6 f64), + 240 B/atom
     // per ANM-deformed molecule (10 modes x 24 B), + 56 B pose in + 8 B energy out.
-    const uint64_t atoms = (uint64_t)pair_.rec.n + (uint64_t)pair_.lig.n;
+    const uint64_t atoms = (uint64_t)rec_.n + (uint64_t)lig_.n;
     uint64_t bytes = (method_ == LD_METHOD_DFIRE ? 26 : 48) * atoms + 64;
-    if (use_anm_) bytes += 24ull * pair_.rec.num_anm * pair_.rec.n + 24ull * pair_.lig.num_anm * pair_.lig.n;
+    bytes += 24ull * rec_.num_anm * rec_.n + 24ull * lig_.num_anm * lig_.n;
     out->stream_bytes_per_pose = bytes;
 }
 

@@ -26,6 +26,14 @@ struct HostMolecule {  // what ld_scorer_model_arrays hands back
     std::vector<double> ele_charges, vdw_charges, vdw_radii;
 };
 
+// What the scorer knows of one molecule whichever route runs (slot_molecule: host arithmetic only).
+struct SideFacts {
+    int n = 0;                   // atoms
+    int num_anm = 0;             // ANM modes a pose carries for this side: 0 unless the scorer uses ANM
+    int flag_words = 0;          // uint32 words of interface flags per pose for this side
+    std::vector<int32_t> slot;   // per original atom: its bit of the per-pose flag set, or -1
+};
+
 // DFIRE's distance binning as a lookup over cells of 0.25 A^2 (DESIGN.md "bin LUT").
 int dfire_bin_reference(double dist2);               // the formula, src/dfire.rs:49-53,336-337
 struct DfireBinning {
@@ -76,7 +84,7 @@ struct RouteInputs {
     const ld_scorer_desc &desc;
     const DfireTiles &tiles;
     int rec_flag_words;
-    const double *bin_step;   // kDfireSteps, d2 units (the all-pairs launch's)
+    const double *bin_step;   // kDfireSteps, d2 units (the scorer's upload, shared by every DFIRE route)
     double iface_d2;
     bool use_anm;
     bool latency;             // LIGHTDOCK_TILED_LATENCY: launches of one swarm
@@ -120,6 +128,27 @@ class PackedPath {
     const uint32_t *lut_full_ = nullptr;          // the LUT without elided zero bins (counting launches)
     bool image_per_pose_ = false;                 // receptor ANM: one receptor image per pose per launch
     DeviceBuffer ws_rec_pairs_, ws_rec_sub_, ws_rec_tile_;
+};
+
+// ---------------------------------------------------------------------------------------
+// The all-pairs route (kernels/pose_energy.hpp) as one object: DNA / PYDOCK, and DFIRE where no culled route runs
+// ---------------------------------------------------------------------------------------
+class AllPairsPath {
+   public:
+    // bin_step / iface_d2: the scorer's (bin_step is null for DNA)
+    AllPairsPath(const ld_scorer_desc &desc, const SideFacts &rec, const SideFacts &lig, const double *bin_step, double iface_d2, int method,
+                 bool use_anm);
+    // One batch: pose_energy_pairs on `stream`, by the mask (d_list / d_count are not read).
+    void run(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, const uint32_t *d_list, const uint32_t *d_count,
+             const PoseOutputs &out, hipStream_t stream);
+    size_t partials_per_pose() const { return (size_t)model_.n_chunks; }
+    const PairLaunch &model() const { return model_; }
+
+   private:
+    DeviceMolecule upload_molecule(const ld_molecule &m, const SideFacts &facts, bool is_receptor);
+
+    DeviceArena arena_;   // both molecules as the kernel reads them; DFIRE: the reference-layout potential and the cell LUT
+    PairLaunch model_;    // molecule / table pointers and the chunking, filled once; batch fields per run()
 };
 
 // ---------------------------------------------------------------------------------------
@@ -194,10 +223,10 @@ class Scorer {
 
     int method() const { return method_; }
     bool use_anm() const { return use_anm_; }
-    size_t anm_rec() const { return use_anm_ ? (size_t)pair_.rec.num_anm : 0; }
-    size_t anm_lig() const { return use_anm_ ? (size_t)pair_.lig.num_anm : 0; }
+    size_t anm_rec() const { return (size_t)rec_.num_anm; }
+    size_t anm_lig() const { return (size_t)lig_.num_anm; }
     size_t pose_len() const { return 7 + anm_rec() + anm_lig(); }
-    size_t num_atoms(int side) const { return side ? (size_t)pair_.lig.n : (size_t)pair_.rec.n; }
+    size_t num_atoms(int side) const { return side ? (size_t)lig_.n : (size_t)rec_.n; }
     const HostMolecule &host_molecule(int side) const { return side ? host_lig_ : host_rec_; }
     int device() const { return device_; }
     hipStream_t stream() const { return stream_; }
@@ -226,9 +255,6 @@ class Scorer {
     void pair_kernel_time(double *total_ms, uint64_t *launches);
 
    private:
-    void upload_molecule(const ld_molecule &m, bool is_receptor, DeviceMolecule &dev, HostMolecule &host,
-                         std::vector<uint32_t> &group_offsets, std::vector<uint32_t> &group_slots,
-                         std::vector<uint32_t> &membrane_slots);
     void reserve_workspace(size_t n_poses, bool counts);
     size_t partials_per_pose() const;  // what the route that runs leaves for pose_energy_finish to fold
     void build_tiles(const ld_scorer_desc &desc);  // what the culled routes share (tiles_)
@@ -241,7 +267,7 @@ class Scorer {
     int method_ = 0;
     bool use_anm_ = false;
     DeviceArena arena_;
-    PairLaunch pair_;     // receptor / ligand / table pointers filled once; batch fields per call
+    SideFacts rec_, lig_;
     TailTables tail_;
     // K1, fixed in the constructor: the block-major path (kernels/dfire_bm.hpp, the DFIRE default), the pose-major packed-f32
     // kernel (kernels/dfire_packed.hpp), or the all-pairs kernel of pose_energy.hpp (DNA, and DFIRE where the culled paths decline)
@@ -250,8 +276,8 @@ class Scorer {
     DfireTiles tiles_;                      // DFIRE unless LIGHTDOCK_DFIRE_KERNEL=allpairs; the routes below read it
     std::unique_ptr<BlockMajorPath> bm_;    // set: route_ == block_major
     std::unique_ptr<PackedPath> packed_;    // set: route_ == packed
+    std::unique_ptr<AllPairsPath> all_pairs_;   // set: route_ == all_pairs
     int n_cus_ = 256;
-    std::vector<int32_t> host_slot_rec_, host_slot_lig_;  // per original atom, as uploaded to the all-pairs path
     HostMolecule host_rec_, host_lig_;
     DeviceBuffer ws_partial_, ws_flags_, ws_counts_, ws_tested_, ws_exact_, ws_poses_, ws_energies_;
     bool timing_ = false;

@@ -9,8 +9,10 @@
 // this build; nothing of it ships.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 #include "kernels/cluster.hpp"
 #include "kernels/dfire_bm.hpp"
@@ -18,6 +20,7 @@
 #include "kernels/dfire_tiled.hpp"
 #include "kernels/gso_step.hpp"
 #include "kernels/pose_energy.hpp"
+#include "lightdock_hip.h"
 
 extern "C" {
 hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
@@ -28,9 +31,10 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_t *p, int) {
     std::strcpy(p->gcnArchName, "gfx950:sramecc+:xnack-");
     return hipSuccess;
 }
-static size_t device_allocations = 0;
-size_t ld_stub_device_allocations(void) { return device_allocations; }   // host_check: what a scorer's construction allocated
-hipError_t hipMalloc(void **p, size_t n) { device_allocations++; *p = std::malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+static std::vector<size_t> allocation_sizes;   // of every hipMalloc so far
+size_t ld_stub_device_allocations(void) { return allocation_sizes.size(); }   // host_check: what a scorer's construction allocated
+size_t ld_stub_device_allocations_of(size_t bytes) { return (size_t)std::count(allocation_sizes.begin(), allocation_sizes.end(), bytes); }   // ... in blocks of exactly that size
+hipError_t hipMalloc(void **p, size_t n) { allocation_sizes.push_back(n); *p = std::malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void *p) { std::free(p); return hipSuccess; }
 hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { std::memcpy(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t) { std::memcpy(d, s, n); return hipSuccess; }
@@ -59,10 +63,56 @@ const char *hipGetErrorString(hipError_t) { return "hip stub"; }
 
 namespace ld {
 // kernel launch entry points: the arguments are touched, nothing runs
+// touch / peek: the first and the last element of a buffer a kernel writes / reads, the extent as the kernel indexes it
+template <typename T>
+static void touch(T *base, size_t count) {
+    if (!count) return;
+    base[0] = T();
+    base[count - 1] = T();
+}
+template <typename T>
+static void peek(const T *base, size_t count) {
+    if (!count) return;
+    volatile T first = base[0], last = base[count - 1];
+    (void)first;
+    (void)last;
+}
 size_t pair_kernel_lds_bytes(const PairLaunch &) { return 0; }
 const char *pair_kernel_name(int method) { return method == 0 ? "pose_energy_pairs<0" : "pose_energy_pairs<1"; }
+static void peek_molecule(const DeviceMolecule &m, bool dfire) {
+    const size_t n_pad = (size_t)m.n_pad;
+    peek(m.x, n_pad);
+    peek(m.y, n_pad);
+    peek(m.z, n_pad);
+    peek(m.slot, n_pad);
+    if (dfire) {
+        peek(m.tindex, n_pad);
+    } else {
+        peek(m.charge, n_pad);
+        peek(m.well_depth, n_pad);
+        peek(m.radius, n_pad);
+    }
+    peek(m.modes, (size_t)m.num_anm * 3 * n_pad);   // [mode][xyz][n_pad]
+}
+static size_t pair_kernel_launches = 0;
+extern "C" size_t ld_stub_pair_kernel_launches(void) { return pair_kernel_launches; }   // host_check: which route a batch took
 hipError_t launch_pair_kernel(const PairLaunch &p, hipStream_t) {
-    if (p.n_poses && p.partial) p.partial[0] = 0.0;
+    pair_kernel_launches++;
+    const bool dfire = p.method == LD_METHOD_DFIRE;
+    if (p.rec.n_pad < p.rec.n || p.lig.n_pad < p.lig.n || p.n_chunks * p.chunk_atoms < p.rec.n) return hipErrorInvalidValue;
+    peek_molecule(p.rec, dfire);
+    peek_molecule(p.lig, dfire);
+    if (dfire) {
+        peek(p.table, (size_t)LD_DFIRE_TABLE_LEN);
+        peek(p.lut, (size_t)kDfireLutCells);
+        peek(p.bin_step, (size_t)kDfireSteps);
+    }
+    if (!p.n_poses) return hipSuccess;
+    peek(p.poses, (p.n_poses - 1) * p.stride + 7 + (p.use_anm ? (size_t)(p.rec.num_anm + p.lig.num_anm) : 0));   // row i: poses + i * stride
+    if (p.active) peek(p.active, p.n_poses);
+    touch(p.partial, p.n_poses * (size_t)p.n_chunks * 2);                            // [pose][chunk][2]
+    touch(p.flags, p.n_poses * (size_t)(p.rec.flag_words + p.lig.flag_words));     // [pose][rec words + lig words]
+    if (p.count_partial) touch(p.count_partial, p.n_poses * (size_t)p.n_chunks);   // [pose][chunk]
     return hipSuccess;
 }
 hipError_t launch_finish_kernel(const FinishLaunch &f, hipStream_t) {
@@ -79,12 +129,6 @@ size_t bm_pairs_lds_bytes() { return 0; }
 // The block-major launches write the first and the last element of EVERY workspace region of the launch's set, indexed from the
 // BmLaunch fields the way the kernels index them (kernels/dfire_bm.hpp: the comments of BmLaunch) -- not through bm_layout(), so
 // that ASan checks the layout's offsets and sizes independently.  Rows of the pass run to t.cap, the room a set has.
-template <typename T>
-static void touch(T *base, size_t count) {
-    if (!count) return;
-    base[0] = T();
-    base[count - 1] = T();
-}
 hipError_t launch_bm_pose(const BmLaunch &t, hipStream_t) {
     if (!t.n_poses) return hipSuccess;
     const size_t tile_pairs = (size_t)t.m.lig.n_tiles * t.m.rec_n_tiles;
@@ -146,13 +190,6 @@ hipError_t launch_bm_gather(const BmLaunch &t, hipStream_t) {
 }
 // The analysis launches (kernels/cluster.hpp) likewise: the first and the last element of every buffer a kernel reads or writes,
 // the extents from the launch arguments as the kernels of cluster.hip index them, not from complex.cpp's sizing.
-template <typename T>
-static void peek(const T *base, size_t count) {
-    if (!count) return;
-    volatile T first = base[0], last = base[count - 1];
-    (void)first;
-    (void)last;
-}
 static void peek_complex(const ComplexDevice &m, const double *poses, size_t stride, size_t n_poses) {
     peek(m.rec_xyz, 3 * (size_t)m.n_rec);
     peek(m.lig_xyz, 3 * (size_t)m.n_lig);

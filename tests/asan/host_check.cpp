@@ -25,10 +25,14 @@ static int failures = 0;
     } while (0)
 
 extern "C" size_t ld_stub_device_allocations(void);   // tests/asan/hip_stub.cpp
+extern "C" size_t ld_stub_device_allocations_of(size_t bytes);
 extern "C" size_t ld_stub_packed_prepare_launches(void);
+extern "C" size_t ld_stub_pair_kernel_launches(void);
 
 // A DFIRE scorer through every form of a block-major batch: plain, counting (the sequence runs twice), the single-pose call.
 // Device memory is host memory in this build, so the device-pointer call takes host vectors.
+// A culled route (block-major, packed) leaves the all-pairs kernel uncalled and has block counts; the all-pairs route launches it
+// once a call and has none.
 static void bm_batches(ld_scorer *s, size_t n, const char *want_kernel) {
     const size_t len = ld_scorer_pose_len(s);
     std::vector<double> poses(len * n, 0.0), e(n);
@@ -36,10 +40,13 @@ static void bm_batches(ld_scorer *s, size_t n, const char *want_kernel) {
     std::vector<uint32_t> counts(n), blocks(n);
     ld_kernel_info info;
     CHECK(ld_scorer_kernel_info(s, &info) == LD_OK && std::strcmp(info.pair_kernel_name, want_kernel) == 0);
+    const bool all_pairs = std::strncmp(want_kernel, "pose_energy_pairs", 17) == 0;
+    const size_t before = ld_stub_pair_kernel_launches();
     CHECK(ld_scorer_energy_batch(s, n, poses.data(), len, e.data()) == LD_OK);
     CHECK(ld_scorer_energy_batch_device(s, n, poses.data(), len, nullptr, e.data(), counts.data()) == LD_OK);
-    CHECK(ld_scorer_last_block_counts(s, n, blocks.data()) == LD_OK);
+    CHECK(ld_scorer_last_block_counts(s, n, blocks.data()) == (all_pairs ? LD_ERR_UNSUPPORTED : LD_OK));
     CHECK(ld_scorer_energy_batch(s, 1, poses.data(), len, e.data()) == LD_OK);   // a smaller batch after a larger one
+    CHECK(ld_stub_pair_kernel_launches() - before == (all_pairs ? 3u : 0u));
 }
 
 static int cli(std::vector<std::string> args) {
@@ -450,16 +457,36 @@ int main(int argc, char **argv) {
         const char *kernels[3] = {nullptr, "packed", "allpairs"};
         const char *names[3] = {"dfire_bm_pairs", "dfire_packed_pairs", "pose_energy_pairs<0"};
         const size_t want[3] = {1, 1, 0};
+        // the potential in the reference's layout (LD_DFIRE_TABLE_LEN doubles; the culled routes' patch table has another size) is
+        // the all-pairs route's alone
+        const size_t table_bytes = LD_DFIRE_TABLE_LEN * sizeof(double), want_tables[3] = {0, 0, 1};
         for (int k = 0; k < 3; k++) {
             if (kernels[k]) setenv("LIGHTDOCK_DFIRE_KERNEL", kernels[k], 1);
-            const size_t before = ld_stub_packed_prepare_launches();
+            const size_t before = ld_stub_packed_prepare_launches(), tables_before = ld_stub_device_allocations_of(table_bytes);
             ld_scorer *c = dfire(nullptr, nullptr, 0, table.data());
             CHECK(c != nullptr && ld_stub_packed_prepare_launches() - before == want[k]);
+            CHECK(ld_stub_device_allocations_of(table_bytes) - tables_before == want_tables[k]);
             ld_kernel_info info;
             CHECK(c && ld_scorer_kernel_info(c, &info) == LD_OK && std::strcmp(info.pair_kernel_name, names[k]) == 0);
+            if (c) bm_batches(c, 70, names[k]);
             if (c) ld_scorer_destroy(c);
             unsetenv("LIGHTDOCK_DFIRE_KERNEL");
         }
+    }
+    {   // a DNA scorer (restraints on both sides): the all-pairs route without a DFIRE table; LIGHTDOCK_CHUNK_ATOMS: more
+        // receptor chunks, i.e. partials a pose, than the default
+        const std::string base = gold + "/unit/1azp/";
+        const char *rec_active[] = {"A.MET.1"}, *lig_active[] = {"B.DG.1"};
+        for (int chunked = 0; chunked < 2; chunked++) {
+            if (chunked) setenv("LIGHTDOCK_CHUNK_ATOMS", "64", 1);
+            const size_t tables_before = ld_stub_device_allocations_of(LD_DFIRE_TABLE_LEN * sizeof(double));
+            ld_scorer *c = ld_scorer_create_from_pdb(LD_METHOD_DNA, (base + "1azp_receptor.pdb").c_str(), (base + "1azp_ligand.pdb").c_str(), rec_active, 1,
+                                                     nullptr, 0, nullptr, 0, 0, lig_active, 1, nullptr, 0, nullptr, 0, 0, 0, nullptr);
+            CHECK(c != nullptr && ld_stub_device_allocations_of(LD_DFIRE_TABLE_LEN * sizeof(double)) == tables_before);
+            if (c) bm_batches(c, 70, "pose_energy_pairs<1");
+            if (c) ld_scorer_destroy(c);
+        }
+        unsetenv("LIGHTDOCK_CHUNK_ATOMS");
     }
     CHECK(ld_scorer_create_from_pdb(7, rec1.c_str(), lig1.c_str(), nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, nullptr, 0,
                                     nullptr, 0, 0, 0, table.data()) == nullptr);
