@@ -1709,8 +1709,9 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
 
 // ---------------------------------------------------------------------------------------------
 // dfire_bm_gather: eight lanes = row of the pass: the pose's (ligand tile, row) sums -- integers, filled by the pair kernel's
-// atomics, each below 2^61 -- added as f64 in a fixed order (a pose's total can pass 63 bits for an extreme table), plus the
-// exact path's sum.  A counting launch (count_mode) sums ones.
+// atomics, each below 2^63 in magnitude (64 K 2^(44 - x) < 2^63: scorer.cpp, dfire_bm_fix_scale) -- added
+// as f64 in a fixed order (a pose's total can pass 63 bits for an extreme table: tests/test_gpu_dfire_tables.py drives one that
+// does), plus the exact path's sum.  A counting launch (count_mode) sums ones.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void dfire_bm_gather(const BmLaunch launch_arguments) {
     BmArgs *T = LD_BM_ARGS;

@@ -45,7 +45,9 @@ def bm_err(got, want):
     in the worst case, 2-4e-12 observed (tools/err_probe.py) -- whatever the size of the energy, which is
     4.7 - 0.0157 * sum and passes through zero.  BM_ATOL = 1e-11 is an EMPIRICAL allowance, two to five times what is observed and far
     below the model's worst case: a legitimate worst-case batch could exceed it and would have to be judged against the model
-    (bench.py derives its allowance from the model: P_cut * 2^-(45-e) * 0.0157 per pose)."""
+    (bench.py derives its allowance from the model: P_cut * 2^-(45-e) * 0.0157 per pose).  Where the fixed point is held
+    EXACTLY -- at every scale exponent e and extra bit x, against integer arithmetic, to the roundings of the tail -- is
+    tests/test_gpu_dfire_tables.py; this measure stays what it was for the tests here."""
     return np.max(np.maximum(np.abs(got - want) - BM_ATOL, 0.0) / np.maximum(np.abs(want), 1e-9))
 
 
