@@ -309,7 +309,7 @@ int ld_complex_cluster(ld_complex *c, size_t n_swarms, size_t n_glowworms, const
                        int32_t *cluster_of /* n_swarms x n_glowworms */,
                        int32_t *representatives /* n_swarms x n_glowworms */,
                        uint32_t *n_clusters /* n_swarms */);
-int ld_complex_last_kernel_ms(const ld_complex *c, double *ms_out); /* kernels of the last cluster or contacts call (HIP events) */
+int ld_complex_last_kernel_ms(const ld_complex *c, double *ms_out); /* kernels of the last cluster, contacts or assess call (HIP events) */
 /* lgd_top.py: receptor then ligand ATOM/HETATM lines as line[:30] + "%8.3f%8.3f%8.3f" + line[54:] */
 int ld_complex_write_pdb(ld_complex *c, const double *pose, const char *path);
 
@@ -342,6 +342,53 @@ int ld_complex_residue_of_atom(const ld_complex *c, int side, uint32_t *out /* n
 int ld_complex_contacts(ld_complex *c, size_t n, const double *poses, size_t stride, double cutoff,
                         uint32_t *rec_bits /* n x ceil(n_rec_res / 32) */,
                         uint32_t *lig_bits /* n x ceil(n_lig_res / 32) */);
+
+/* Model quality: how close every pose is to a reference (bound) complex -- fnat, i-RMSD, L-RMSD, from which DockQ and
+ * the CAPRI class follow by host arithmetic (lightdock-rust_amd/assess.py).  The rule is this library's own, modelled
+ * on CAPRI / DockQ; no byte compatibility with any outside tool is claimed.
+ *   Reference: two PDB files, receptor and ligand of the bound complex, read like the model's (ATOM/HETATM records in
+ *     file order).  Both share one frame, which may be any frame; it need not be the model's.
+ *   Matching: a model atom is matched when the reference file of its side has a record with the same chain (column
+ *     22), sequence number (23-26), insertion code (27), residue name (18-20) and atom name (13-16), blanks trimmed;
+ *     the first such record in file order wins.  Everything below is over matched atoms only, on both sides; all
+ *     matched atoms count (hydrogens, hetero atoms, beads).
+ *   Coordinates: model atoms posed as above, then the integer thousandths "%8.3f" prints; reference coordinates
+ *     llrint(x * 1000).  So a pose's measures are those of the file ld_complex_write_pdb writes for it.
+ *   Native contacts: C = llrint(contact_cutoff * 1000), 1 <= C <= 30000.  A pair (receptor residue i, ligand residue
+ *     j; residues and indices of the MODEL, as under "Interface contacts") is native iff in the reference some matched
+ *     atom of i and some matched atom of j have dx^2 + dy^2 + dz^2 <= C^2 in exact integers.  The list is sorted by
+ *     (i, j).  Per pose, kept = the native pairs for which the same test holds in the model; fnat = kept / n_native.
+ *   Fit atoms: matched atoms named N, CA, C, O or P.
+ *   L-RMSD: the proper rotation and translation that best superimpose the model's receptor fit atoms on the
+ *     reference's are applied to the model; L-RMSD is then the RMSD over the ligand's fit atoms.
+ *   i-RMSD: an interface residue is a residue of either side with a matched atom within interface_cutoff (same
+ *     integer test, same bounds) of a matched atom of the other side in the reference; i-RMSD is the RMSD of the
+ *     fit atoms of the interface residues of both sides together after their own best superposition.
+ *   Proper rotations only: a mirror image is not a fit.
+ *   DockQ = (fnat + 1 / (1 + (iRMSD / 1.5)^2) + 1 / (1 + (LRMSD / 8.5)^2)) / 3.  CAPRI class, best first: high:
+ *     fnat >= 0.5 and (L <= 1 or i <= 1); medium: fnat >= 0.3 and (L <= 5 or i <= 2); acceptable: fnat >= 0.1 and
+ *     (L <= 10 or i <= 4); otherwise incorrect.
+ *   Numerics: per superposition the sums  sum m, sum |m|^2, sum m r^T  (m model, r reference centred once on the
+ *     integer-rounded centroid of its receptor fit atoms) are accumulated as integers, exact and order-free, so a
+ *     pose's results are the same bits whatever the batch, its place in it or the chunking.  Only centring, Horn's
+ *     symmetric 4 x 4, its largest eigenvalue and eigenvector (cyclic Jacobi) and the square roots are f64; a valid
+ *     pose never gives NaN.  When the receptor's fit atoms are collinear the best rotation is not unique and L-RMSD
+ *     is unspecified (finite); i-RMSD is still the optimum.
+ * ld_complex_set_reference refuses with LD_ERR_INVALID, leaving the complex WITHOUT a reference: fewer than 3 receptor
+ * fit atoms, no ligand fit atom, fewer than 3 interface fit atoms, no native pair, a cutoff out of bounds, a reference
+ * atom beyond 2000 A of the centroid of its receptor fit atoms; a file that cannot be read is LD_ERR_IO.
+ * ld_complex_assess refuses with LD_ERR_INVALID, nothing written: no reference set, non-finite poses, a zero
+ * quaternion, stride < pose_len, a posed coordinate of a used atom (a fit atom or an atom of a residue of a native
+ * pair) beyond +-2000 A.  Device workspace: one slot of used atoms x 16 B per workgroup in flight, at most 1024 slots,
+ * and 320 B a pose of a chunk of 65536 poses; together within 256 MiB (or one slot). */
+int ld_complex_set_reference(ld_complex *c, const char *ref_receptor_pdb, const char *ref_ligand_pdb,
+                             double contact_cutoff /* 5.0 */, double interface_cutoff /* 10.0 */);
+int ld_complex_reference_counts(const ld_complex *c, uint32_t *out /* 6: matched rec, matched lig, native pairs,
+                                rec fit, lig fit, interface fit */);
+int ld_complex_native_pairs(const ld_complex *c, uint32_t *pairs /* n_native x 2: rec residue, lig residue */);
+/* Any output may be NULL; n == 0 is LD_OK.  ld_complex_last_kernel_ms then reports this call's kernels. */
+int ld_complex_assess(ld_complex *c, size_t n, const double *poses, size_t stride,
+                      uint32_t *kept /* n */, double *lrmsd /* n */, double *irmsd /* n */);
 
 /* ------------------------------------------------------------------------------------
  * The reference command line (src/bin/lightdock-rust.rs:77-333) as a function:

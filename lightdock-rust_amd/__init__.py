@@ -154,6 +154,10 @@ def load_library():
     lib.ld_complex_residue_id.argtypes = [vp, C.c_int, sz, C.c_char_p, sz]
     lib.ld_complex_residue_of_atom.argtypes = [vp, C.c_int, vp]
     lib.ld_complex_contacts.argtypes = [vp, sz, vp, sz, C.c_double, vp, vp]
+    lib.ld_complex_set_reference.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_double, C.c_double]
+    lib.ld_complex_reference_counts.argtypes = [vp, vp]
+    lib.ld_complex_native_pairs.argtypes = [vp, vp]
+    lib.ld_complex_assess.argtypes = [vp, sz, vp, sz, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -629,6 +633,35 @@ class Complex:
         if pose.size != self.pose_len:
             raise ValueError("pose must have %d values" % self.pose_len)
         _check(self.lib.ld_complex_write_pdb(self._h, _ptr(pose), os.fsencode(path)))
+
+    def set_reference(self, ref_receptor_pdb, ref_ligand_pdb, contact_cutoff=5.0, interface_cutoff=10.0):
+        """The bound complex assess() measures against (ld_complex_set_reference; lightdock_hip.h, "Model quality").
+        A refusal leaves the complex without a reference."""
+        _check(self.lib.ld_complex_set_reference(self._h, os.fsencode(ref_receptor_pdb), os.fsencode(ref_ligand_pdb),
+                                                 C.c_double(contact_cutoff), C.c_double(interface_cutoff)))
+
+    def reference_counts(self):
+        """dict: matched_rec, matched_lig, native_pairs, rec_fit, lig_fit, interface_fit."""
+        out = np.zeros(6, dtype=np.uint32)
+        _check(self.lib.ld_complex_reference_counts(self._h, _ptr(out)))
+        return dict(zip(("matched_rec", "matched_lig", "native_pairs", "rec_fit", "lig_fit", "interface_fit"), (int(v) for v in out)))
+
+    def native_pairs(self):
+        """(n_native, 2) residue indices (receptor, ligand) of the reference's native pairs, sorted."""
+        out = np.zeros((self.reference_counts()["native_pairs"], 2), dtype=np.uint32)
+        _check(self.lib.ld_complex_native_pairs(self._h, _ptr(out)))
+        return out
+
+    def assess(self, poses):
+        """(n, >= pose_len) poses -> {"kept": native pairs in contact, "fnat", "lrmsd", "irmsd"} per pose (ld_complex_assess)."""
+        poses = _f64(poses)
+        if poses.ndim != 2:
+            raise ValueError("poses must be (n, pose_len)")
+        n = poses.shape[0]
+        kept, lrmsd, irmsd = np.zeros(n, dtype=np.uint32), np.zeros(n), np.zeros(n)
+        n_native = self.reference_counts()["native_pairs"]
+        _check(self.lib.ld_complex_assess(self._h, n, _ptr(poses), poses.shape[1], _ptr(kept), _ptr(lrmsd), _ptr(irmsd)))
+        return {"kept": kept, "fnat": kept / float(n_native), "lrmsd": lrmsd, "irmsd": irmsd}
 
 
 def cli_main(argv):

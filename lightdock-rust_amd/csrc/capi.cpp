@@ -460,6 +460,31 @@ int ld_complex_contacts(ld_complex *c, size_t n, const double *poses, size_t str
         c->impl.contacts(n, poses, stride, cutoff, rec_bits, lig_bits);
     });
 }
+int ld_complex_set_reference(ld_complex *c, const char *ref_receptor_pdb, const char *ref_ligand_pdb, double contact_cutoff,
+                             double interface_cutoff) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.set_reference(ref_receptor_pdb, ref_ligand_pdb, contact_cutoff, interface_cutoff);
+    });
+}
+int ld_complex_reference_counts(const ld_complex *c, uint32_t *out) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.reference_counts(out);
+    });
+}
+int ld_complex_native_pairs(const ld_complex *c, uint32_t *pairs) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.native_pairs(pairs);
+    });
+}
+int ld_complex_assess(ld_complex *c, size_t n, const double *poses, size_t stride, uint32_t *kept, double *lrmsd, double *irmsd) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.assess(n, poses, stride, kept, lrmsd, irmsd);
+    });
+}
 int ld_complex_last_kernel_ms(const ld_complex *c, double *ms_out) {
     return guarded([&] {
         if (!c || !ms_out) throw ld::Error(LD_ERR_INVALID, "null argument");

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <map>
 
 namespace ld {
 
@@ -15,6 +16,15 @@ void check_modes(const char *side, const double *modes, size_t len, size_t num_a
     if (len != num_anm * n_atoms * 3 || (len && !modes))
         throw Error(LD_ERR_INVALID, std::string(side) + ": " + std::to_string(len) +
                                         " mode values, expected num_anm x atoms x 3 = " + std::to_string(num_anm * n_atoms * 3));
+}
+
+// C = llrint(cutoff * 1000), 1 .. 30000, of a contact cutoff in A (lightdock_hip.h, "Interface contacts").
+long long cutoff_thousandths(double cutoff, const char *message) {
+    const double scaled = cutoff * 1000.0;
+    if (!(scaled > 0.0 && scaled < 30001.0)) throw Error(LD_ERR_INVALID, message);
+    const long long C = std::llrint(scaled);
+    if (C < 1 || C > 30000) throw Error(LD_ERR_INVALID, message);
+    return C;
 }
 
 }  // namespace
@@ -192,10 +202,7 @@ void Complex::cluster(size_t n_swarms, size_t n_glowworms, const double *poses, 
 }
 
 void Complex::contacts(size_t n, const double *poses, size_t stride, double cutoff, uint32_t *rec_bits, uint32_t *lig_bits) {
-    const double scaled = cutoff * 1000.0;
-    if (!(scaled > 0.0 && scaled < 30001.0)) throw Error(LD_ERR_INVALID, "cutoff must be 0.001 .. 30 A");
-    const long long C = std::llrint(scaled);
-    if (C < 1 || C > 30000) throw Error(LD_ERR_INVALID, "cutoff must be 0.001 .. 30 A");
+    const long long C = cutoff_thousandths(cutoff, "cutoff must be 0.001 .. 30 A");
     if (n == 0) return;
     check_poses(n, poses, stride);
     const ContactsDevice &k = contacts_;
@@ -219,6 +226,231 @@ void Complex::contacts(size_t n, const double *poses, size_t stride, double cuto
     finish_timed(d_overflow, "complex_contacts", "a posed coordinate is beyond +-1.0e6 A");
     if (rec_bits) hip_check(hipMemcpy(rec_bits, d_rec, n * rw * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
     if (lig_bits) hip_check(hipMemcpy(lig_bits, d_lig, n * lw * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
+}
+
+// --- model quality against a reference complex (lightdock_hip.h, "Model quality"; kernels/assess.hpp) ------------------
+
+namespace {
+
+std::string trimmed_field(const std::string &line, size_t pos, size_t len) {
+    const std::string s = line.substr(pos, len);
+    const size_t b = s.find_first_not_of(' ');
+    return b == std::string::npos ? std::string() : s.substr(b, s.find_last_not_of(' ') - b + 1);
+}
+
+// chain, sequence number, insertion code, residue name, atom name: columns 22, 23-26, 27, 18-20, 13-16, blanks trimmed
+std::string record_key(const std::string &line) {
+    return trimmed_field(line, 21, 1) + '\n' + trimmed_field(line, 22, 4) + '\n' + trimmed_field(line, 26, 1) + '\n' +
+           trimmed_field(line, 17, 3) + '\n' + trimmed_field(line, 12, 4);
+}
+
+bool fit_name(const std::string &line) {
+    const std::string name = trimmed_field(line, 12, 4);
+    return name == "N" || name == "CA" || name == "C" || name == "O" || name == "P";
+}
+
+// For every record of `model` the first record of `reference` with the same key, or -1.
+std::vector<int> match_records(const PdbFile &model, const PdbFile &reference) {
+    std::map<std::string, int> first;
+    for (size_t a = 0; a < reference.lines.size(); a++) first.emplace(record_key(reference.lines[a]), (int)a);
+    std::vector<int> of(model.lines.size(), -1);
+    for (size_t a = 0; a < model.lines.size(); a++) {
+        const auto it = first.find(record_key(model.lines[a]));
+        if (it != first.end()) of[a] = it->second;
+    }
+    return of;
+}
+
+struct RefSums {  // of a set of reference points, exact
+    long long n = 0, s[3] = {};
+    assess_wide ss = 0;
+    void add(const long long r[3]) {
+        n++;
+        for (int k = 0; k < 3; k++) s[k] += r[k], ss += (assess_wide)r[k] * r[k];
+    }
+};
+
+template <typename T>
+const T *upload_into(DeviceBuffer &buffer, const std::vector<T> &host) {
+    buffer.reserve(std::max<size_t>(1, host.size()) * sizeof(T));
+    if (!host.empty()) hip_check(hipMemcpy(buffer.ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy H2D");
+    return static_cast<const T *>(buffer.ptr);
+}
+
+}  // namespace
+
+void Complex::set_reference(const char *ref_receptor_pdb, const char *ref_ligand_pdb, double contact_cutoff, double interface_cutoff) {
+    if (stream_) hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");  // nothing queued reads the old reference
+    ref_ = Reference();  // a refusal below leaves the complex without a reference
+    const long long C = cutoff_thousandths(contact_cutoff, "contact_cutoff must be 0.001 .. 30 A");
+    const long long I = cutoff_thousandths(interface_cutoff, "interface_cutoff must be 0.001 .. 30 A");
+    const PdbFile ref[2] = {read_pdb_file_order(ref_receptor_pdb), read_pdb_file_order(ref_ligand_pdb)};
+    const PdbFile *model[2] = {&rec_, &lig_};
+    const size_t n_rec = rec_.lines.size();
+
+    // matching; the reference's thousandths of every matched model atom (complex atom index)
+    std::vector<int> matched[2] = {match_records(rec_, ref[0]), match_records(lig_, ref[1])};
+    std::vector<long long> xyz(n_atoms() * 3, 0);
+    std::vector<uint8_t> is_matched(n_atoms(), 0), is_fit(n_atoms(), 0);
+    Reference r;
+    for (int side = 0; side < 2; side++)
+        for (size_t a = 0; a < matched[side].size(); a++) {
+            if (matched[side][a] < 0) continue;
+            const size_t atom = side * n_rec + a;
+            for (int k = 0; k < 3; k++) xyz[3 * atom + k] = std::llrint(ref[side].xyz[3 * (size_t)matched[side][a] + k] * 1000.0);
+            is_matched[atom] = 1;
+            is_fit[atom] = fit_name(model[side]->lines[a]);
+            r.counts[side]++;
+            r.counts[3 + side] += is_fit[atom];
+        }
+    if (r.counts[3] < 3) throw Error(LD_ERR_INVALID, "fewer than 3 receptor fit atoms (matched N, CA, C, O, P) in the reference");
+    if (r.counts[4] < 1) throw Error(LD_ERR_INVALID, "no ligand fit atom (matched N, CA, C, O, P) in the reference");
+
+    // native residue pairs and interface residues, on the reference's exact integers
+    const size_t n_rec_res = rec_.res_id.size(), n_lig_res = lig_.res_id.size();
+    std::vector<uint64_t> pairs;
+    std::vector<uint8_t> interface_res[2] = {std::vector<uint8_t>(n_rec_res, 0), std::vector<uint8_t>(n_lig_res, 0)};
+    std::vector<uint32_t> lig_atoms;
+    for (size_t b = 0; b < lig_.lines.size(); b++)
+        if (is_matched[n_rec + b]) lig_atoms.push_back((uint32_t)b);
+    for (size_t a = 0; a < n_rec; a++) {
+        if (!is_matched[a]) continue;
+        const long long *p = &xyz[3 * a];
+        const uint32_t ra = rec_.res_of_atom[a];
+        for (uint32_t b : lig_atoms) {
+            const long long *q = &xyz[3 * (n_rec + b)];
+            const long long dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+            if (std::llabs(dx) > 30000 || std::llabs(dy) > 30000 || std::llabs(dz) > 30000) continue;
+            const long long d2 = dx * dx + dy * dy + dz * dz;
+            const uint32_t rb = lig_.res_of_atom[b];
+            if (d2 <= I * I) interface_res[0][ra] = interface_res[1][rb] = 1;
+            if (d2 <= C * C) pairs.push_back((uint64_t)ra << 32 | rb);
+        }
+    }
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    if (pairs.empty()) throw Error(LD_ERR_INVALID, "no native residue pair within contact_cutoff in the reference");
+    if (pairs.size() > (size_t)INT32_MAX) throw Error(LD_ERR_INVALID, "too many native residue pairs");
+    std::vector<uint8_t> native_res[2] = {std::vector<uint8_t>(n_rec_res, 0), std::vector<uint8_t>(n_lig_res, 0)};
+    for (uint64_t p : pairs) {
+        native_res[0][p >> 32] = native_res[1][(uint32_t)p] = 1;
+        r.native.push_back((uint32_t)(p >> 32));
+        r.native.push_back((uint32_t)p);
+    }
+    r.counts[2] = (uint32_t)pairs.size();
+
+    // the centre: the integer-rounded centroid of the reference's receptor fit atoms
+    long long centre[3] = {0, 0, 0};
+    for (size_t a = 0; a < n_rec; a++)
+        if (is_fit[a])
+            for (int k = 0; k < 3; k++) centre[k] += xyz[3 * a + k];
+    for (int k = 0; k < 3; k++) centre[k] = std::llrint((double)centre[k] / (double)r.counts[3]);
+
+    // used atoms in index order: fit atoms and the matched atoms of the residues of a native pair
+    std::vector<uint32_t> used_atom;
+    std::vector<int4> used_ref;
+    std::vector<int> lo[2] = {std::vector<int>(n_rec_res, 0), std::vector<int>(n_lig_res, 0)}, hi[2] = {lo[0], lo[1]};
+    RefSums sums_rec, sums_lig, sums_int;
+    for (size_t atom = 0; atom < n_atoms(); atom++) {
+        const int side = atom >= n_rec;
+        const uint32_t res = side ? lig_.res_of_atom[atom - n_rec] : rec_.res_of_atom[atom];
+        if (atom == n_rec) r.dev.n_used_rec = (int)used_atom.size();
+        if (!is_matched[atom] || !(is_fit[atom] || native_res[side][res])) continue;
+        long long c[3];
+        for (int k = 0; k < 3; k++) {
+            c[k] = xyz[3 * atom + k] - centre[k];
+            if (std::llabs(c[k]) > kAssessBound)
+                throw Error(LD_ERR_INVALID, "a reference atom is more than 2000 A from the centroid of the receptor's fit atoms");
+        }
+        const int interface_fit = is_fit[atom] && interface_res[side][res];
+        const int u = (int)used_atom.size();
+        if (native_res[side][res]) {
+            if (hi[side][res] == 0) lo[side][res] = u;
+            hi[side][res] = u + 1;
+        }
+        used_atom.push_back((uint32_t)atom);
+        used_ref.push_back(make_int4((int)c[0], (int)c[1], (int)c[2], (int)is_fit[atom] | interface_fit << 1));
+        if (is_fit[atom]) (side ? sums_lig : sums_rec).add(c);
+        if (interface_fit) sums_int.add(c);
+    }
+    if (n_rec == n_atoms()) r.dev.n_used_rec = (int)used_atom.size();
+    r.counts[5] = (uint32_t)sums_int.n;
+    if (sums_int.n < 3) throw Error(LD_ERR_INVALID, "fewer than 3 interface fit atoms within interface_cutoff in the reference");
+    if (used_atom.size() > kAssessMaxUsed) throw Error(LD_ERR_INVALID, "more than 1048576 atoms to assess");
+    std::vector<int4> native;
+    for (uint64_t p : pairs) {
+        const uint32_t i = (uint32_t)(p >> 32), j = (uint32_t)p;
+        native.push_back(make_int4(lo[0][i], hi[0][i], lo[1][j], hi[1][j]));
+    }
+
+    // what the reference contributes to every pose's superpositions, exactly
+    AssessSolve &k = r.solve;
+    auto own = [](const RefSums &s) { return assess_to_double((assess_wide)s.n * s.ss - ((assess_wide)s.s[0] * s.s[0] + (assess_wide)s.s[1] * s.s[1] + (assess_wide)s.s[2] * s.s[2])) / (double)s.n; };
+    k.n_rec = sums_rec.n, k.n_lig = sums_lig.n, k.n_int = sums_int.n;
+    for (int a = 0; a < 3; a++) k.sr_rec[a] = sums_rec.s[a], k.sr_lig[a] = sums_lig.s[a], k.sr_int[a] = sums_int.s[a];
+    k.g_rec = own(sums_rec);
+    k.g_int = own(sums_int);
+    {
+        const assess_wide nr = sums_rec.n, nl = sums_lig.n;
+        assess_wide dot = 0, rr = 0;
+        for (int a = 0; a < 3; a++) dot += (assess_wide)sums_rec.s[a] * sums_lig.s[a], rr += (assess_wide)sums_rec.s[a] * sums_rec.s[a];
+        k.g_lig = assess_to_double(nr * nr * sums_lig.ss - 2 * nr * dot + nl * rr) / ((double)sums_rec.n * (double)sums_rec.n);
+    }
+
+    r.C2 = (uint32_t)(C * C);
+    r.dev.n_used = (int)used_atom.size();
+    r.dev.n_native = (int)native.size();
+    r.dev.used_atom = upload_into(d_ref_atoms_, used_atom);
+    r.dev.used_ref = upload_into(d_ref_xyz_, used_ref);
+    r.dev.native = upload_into(d_ref_native_, native);
+    r.set = true;
+    ref_ = std::move(r);
+}
+
+void Complex::reference_counts(uint32_t *out) const {
+    if (!out) throw Error(LD_ERR_INVALID, "null argument");
+    if (!ref_.set) throw Error(LD_ERR_INVALID, "no reference set (ld_complex_set_reference)");
+    std::copy(ref_.counts, ref_.counts + 6, out);
+}
+
+void Complex::native_pairs(uint32_t *pairs) const {
+    if (!pairs) throw Error(LD_ERR_INVALID, "null argument");
+    if (!ref_.set) throw Error(LD_ERR_INVALID, "no reference set (ld_complex_set_reference)");
+    std::copy(ref_.native.begin(), ref_.native.end(), pairs);
+}
+
+void Complex::assess(size_t n, const double *poses, size_t stride, uint32_t *kept, double *lrmsd, double *irmsd) {
+    if (!ref_.set) throw Error(LD_ERR_INVALID, "no reference set (ld_complex_set_reference)");
+    if (n == 0) return;
+    check_poses(n, poses, stride);
+    const AssessDevice &d = ref_.dev;
+    // a chunk of poses a launch pair: its sums, and a workspace slot of used atoms a workgroup in flight
+    const size_t chunk = std::min(n, kAssessChunkPoses);
+    const size_t sums_bytes = chunk * kAssessWords * sizeof(long long), per_slot = (size_t)d.n_used * sizeof(int4);
+    const size_t slots = std::min(chunk, std::min<size_t>(kAssessSlots, std::max<size_t>(1, (kClusterWorkspaceBytes - sums_bytes) / per_slot)));
+    upload_poses(n, poses, stride);
+    d_ids_.reserve(n * (2 * sizeof(double) + sizeof(uint32_t)) + sizeof(int));
+    double *d_lrmsd = static_cast<double *>(d_ids_.ptr), *d_irmsd = d_lrmsd + n;
+    uint32_t *d_kept = reinterpret_cast<uint32_t *>(d_irmsd + n);
+    int *d_overflow = reinterpret_cast<int *>(d_kept + n);
+    hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), stream_), "hipMemset");
+    d_ws_.reserve(slots * per_slot + sums_bytes);
+    int4 *d_atoms = static_cast<int4 *>(d_ws_.ptr);
+    long long *d_sums = reinterpret_cast<long long *>(d_atoms + slots * d.n_used);
+    const double *d_poses = static_cast<const double *>(d_poses_.ptr);
+    hip_check(hipEventRecord(ev0_, stream_), "hipEventRecord");
+    for (size_t i0 = 0; i0 < n; i0 += chunk) {
+        const size_t m = std::min(chunk, n - i0);
+        hip_check(launch_complex_assess_sums(dev_, d, d_poses + i0 * stride, stride, m, ref_.C2, std::min(slots, m), d_atoms, d_sums,
+                                             d_overflow, stream_),
+                  "complex_assess_sums launch");
+        hip_check(launch_complex_assess_solve(ref_.solve, d_sums, m, d_kept + i0, d_lrmsd + i0, d_irmsd + i0, stream_),
+                  "complex_assess_solve launch");
+    }
+    finish_timed(d_overflow, "complex_assess", "a posed coordinate of an assessed atom is beyond +-2000 A");
+    if (kept) hip_check(hipMemcpy(kept, d_kept, n * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
+    if (lrmsd) hip_check(hipMemcpy(lrmsd, d_lrmsd, n * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy D2H");
+    if (irmsd) hip_check(hipMemcpy(irmsd, d_irmsd, n * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy D2H");
 }
 
 void Complex::write_pdb(const double *pose, const char *path) {

@@ -9,6 +9,7 @@
 
 #include "device_memory.hpp"
 #include "host/pdb_file.hpp"
+#include "kernels/assess.hpp"
 #include "kernels/cluster.hpp"
 
 namespace ld {
@@ -32,6 +33,11 @@ class Complex {
                  int32_t *cluster_of, int32_t *representatives, uint32_t *n_clusters);
     void contacts(size_t n, const double *poses, size_t stride, double cutoff, uint32_t *rec_bits, uint32_t *lig_bits);
     void write_pdb(const double *pose, const char *path);
+    // Model quality against a reference complex (lightdock_hip.h, "Model quality")
+    void set_reference(const char *ref_receptor_pdb, const char *ref_ligand_pdb, double contact_cutoff, double interface_cutoff);
+    void reference_counts(uint32_t *out) const;  // 6: matched rec, matched lig, native pairs, rec fit, lig fit, interface fit
+    void native_pairs(uint32_t *pairs) const;    // n_native x 2
+    void assess(size_t n, const double *poses, size_t stride, uint32_t *kept, double *lrmsd, double *irmsd);
     double last_kernel_ms() const { return last_kernel_ms_; }
 
    private:
@@ -49,6 +55,16 @@ class Complex {
     ComplexDevice dev_;
     const uint32_t *d_backbone_ = nullptr;
     ContactsDevice contacts_;
+    // what set_reference derived; `set` only once all of it stands
+    struct Reference {
+        bool set = false;
+        uint32_t counts[6] = {};
+        uint32_t C2 = 0;
+        std::vector<uint32_t> native;  // (receptor residue, ligand residue), sorted
+        AssessDevice dev;
+        AssessSolve solve;
+    } ref_;
+    DeviceBuffer d_ref_atoms_, d_ref_xyz_, d_ref_native_;  // behind ref_.dev: a later reference reuses them
     DeviceBuffer d_poses_, d_scores_, d_out_, d_ws_, d_ids_;
     hipStream_t stream_ = nullptr;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
