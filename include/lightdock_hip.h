@@ -313,6 +313,28 @@ int ld_complex_last_kernel_ms(const ld_complex *c, double *ms_out); /* kernels o
 /* lgd_top.py: receptor then ligand ATOM/HETATM lines as line[:30] + "%8.3f%8.3f%8.3f" + line[54:] */
 int ld_complex_write_pdb(ld_complex *c, const double *pose, const char *path);
 
+/* Clustering a ranked list: ld_complex_cluster's rule for ONE list of poses of any swarms, up to about a million,
+ * in several workgroups; what removes the models that neighbouring swarms found independently.
+ *   Order: the poses are taken by (scoring descending, index ascending).
+ *   Rule: a pose joins the FIRST representative, in creation order, for which within_cutoff holds; if none does it
+ *     becomes the next representative.
+ *   within_cutoff: rint(sqrt(S * 1e-6 / n_atoms) * 1e4) / 1e4 <= cutoff, S the sum of the squared differences of the
+ *     thousandths "%.3f" prints of the posed atoms (posing and rounding as above): ld_complex_cluster's predicate.
+ *   atoms = 0: the CA / P atoms of the whole complex, BSAS's measure; for n <= 4096 the three outputs equal
+ *     ld_complex_cluster(c, 1, n, ...)'s word for word.  atoms = 1: the ligand's CA / P atoms only, n_atoms their
+ *     count, so that the receptor does not dilute the measure.
+ *   Outputs: cluster_of in input order; representatives: input indices in creation order, -1 after the last;
+ *     n_clusters: one word.  n == 0 is LD_OK and sets *n_clusters = 0.
+ *   Equality with the sequential rule is owed wherever S < 2^53: below it the sum is exact, hence order-free.
+ * LD_ERR_INVALID, nothing written: a NaN cutoff, atoms other than 0 / 1, a non-finite scoring or pose value, a zero
+ * quaternion, no CA / P atom in the chosen set, a posed coordinate beyond an int32 of thousandths (+-2.1e6 A), a list
+ * whose device workspace, n x walked atoms x 12 B, would exceed 4 GiB (walked atoms: the chosen set, less the
+ * receptor's when atoms = 0 and the receptor has no modes: they cannot move).  The bound is checked before the list
+ * is read.  ld_complex_last_kernel_ms then reports this call from its first launch to its last, host rounds included. */
+int ld_complex_cluster_ranked(ld_complex *c, size_t n, const double *poses, size_t stride, const double *scoring,
+                              double cutoff, int atoms, int32_t *cluster_of /* n */, int32_t *representatives /* n */,
+                              uint32_t *n_clusters /* 1 */);
+
 /* Interface contacts: for every pose, which receptor and which ligand residues touch.  The primitive
  * under LightDock's lgd_filter_restraints.py and lgd_filter_membrane.py, which re-read the PDB file of
  * a model and compare a distance matrix with a cutoff; those tools are not part of the reference

@@ -147,6 +147,7 @@ def load_library():
     lib.ld_complex_num_atoms.argtypes = [vp, C.c_int]
     lib.ld_complex_coordinates.argtypes = [vp, sz, vp, sz, vp]
     lib.ld_complex_cluster.argtypes = [vp, sz, sz, vp, sz, vp, C.c_double, vp, vp, vp]
+    lib.ld_complex_cluster_ranked.argtypes = [vp, sz, vp, sz, vp, C.c_double, C.c_int, vp, vp, vp]
     lib.ld_complex_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_double)]
     lib.ld_complex_write_pdb.argtypes = [vp, vp, C.c_char_p]
     lib.ld_complex_num_residues.restype = sz
@@ -543,8 +544,8 @@ class GSO:
 
 
 class Complex:
-    """LightDock's analysis of a run (ld_complex_*): posed coordinates, BSAS clustering of whole swarms, top-model PDBs,
-    per-pose interface contacts."""
+    """LightDock's analysis of a run (ld_complex_*): posed coordinates, BSAS clustering of whole swarms and of one ranked
+    list across swarms, top-model PDBs, per-pose interface contacts."""
 
     def __init__(self, receptor_pdb, ligand_pdb, rec_nmodes=None, rec_num_anm=0, lig_nmodes=None, lig_num_anm=0):
         self.lib = load_library()
@@ -583,6 +584,24 @@ class Complex:
                "n_clusters": np.empty(ns, dtype=np.uint32)}
         _check(self.lib.ld_complex_cluster(self._h, ns, ng, _ptr(poses), poses.shape[2], _ptr(scoring), C.c_double(cutoff),
                                            _ptr(out["cluster_of"]), _ptr(out["representatives"]), _ptr(out["n_clusters"])))
+        return out
+
+    def cluster_ranked(self, poses, scoring, cutoff=4.0, atoms="complex"):
+        """One ranked list of poses of any swarms, up to about a million: poses (n, >= pose_len), scoring (n,) -> a dict
+        shaped like cluster()'s with ONE row: cluster_of (1, n) in input order, representatives (1, n) input indices in
+        creation order (-1 after the last), n_clusters (1,).  atoms: "complex", the CA / P atoms of the whole complex
+        (cluster()'s measure), or "ligand", the ligand's only (ld_complex_cluster_ranked)."""
+        poses, scoring = _f64(poses), _f64(scoring)
+        if poses.ndim != 2 or scoring.shape != poses.shape[:1]:
+            raise ValueError("poses must be (n, pose_len), scoring (n,)")
+        if atoms not in ("complex", "ligand"):
+            raise ValueError('atoms must be "complex" or "ligand"')
+        n = scoring.shape[0]
+        out = {"cluster_of": np.empty((1, n), dtype=np.int32), "representatives": np.empty((1, n), dtype=np.int32),
+               "n_clusters": np.empty(1, dtype=np.uint32)}
+        _check(self.lib.ld_complex_cluster_ranked(self._h, n, _ptr(poses), poses.shape[1], _ptr(scoring), C.c_double(cutoff),
+                                                  int(atoms == "ligand"), _ptr(out["cluster_of"]), _ptr(out["representatives"]),
+                                                  _ptr(out["n_clusters"])))
         return out
 
     def last_kernel_ms(self):

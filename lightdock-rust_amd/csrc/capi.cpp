@@ -453,6 +453,13 @@ int ld_complex_cluster(ld_complex *c, size_t n_swarms, size_t n_glowworms, const
         c->impl.cluster(n_swarms, n_glowworms, poses, stride, scoring, cutoff, cluster_of, representatives, n_clusters);
     });
 }
+int ld_complex_cluster_ranked(ld_complex *c, size_t n, const double *poses, size_t stride, const double *scoring, double cutoff,
+                              int atoms, int32_t *cluster_of, int32_t *representatives, uint32_t *n_clusters) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.cluster_ranked(n, poses, stride, scoring, cutoff, atoms, cluster_of, representatives, n_clusters);
+    });
+}
 int ld_complex_contacts(ld_complex *c, size_t n, const double *poses, size_t stride, double cutoff, uint32_t *rec_bits,
                         uint32_t *lig_bits) {
     return guarded([&] {

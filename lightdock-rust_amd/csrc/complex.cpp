@@ -201,6 +201,83 @@ void Complex::cluster(size_t n_swarms, size_t n_glowworms, const double *poses, 
     hip_check(hipMemcpy(n_clusters, d_count, n_swarms * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
 }
 
+void Complex::cluster_ranked(size_t n, const double *poses, size_t stride, const double *scoring, double cutoff, int atoms,
+                             int32_t *cluster_of, int32_t *representatives, uint32_t *n_clusters) {
+    if (std::isnan(cutoff)) throw Error(LD_ERR_INVALID, "cutoff is NaN");
+    if (atoms != 0 && atoms != 1) throw Error(LD_ERR_INVALID, "atoms must be 0 (the complex's CA / P atoms) or 1 (the ligand's)");
+    if (!n_clusters) throw Error(LD_ERR_INVALID, "null argument");
+    // the walk: the ligand's CA / P atoms first, they move most.  Without receptor modes the receptor's terms are zero
+    // and are not walked; the RMSD still counts them.
+    std::vector<uint32_t> walk;
+    for (uint32_t a : lig_.backbone) walk.push_back(a + (uint32_t)dev_.n_rec);
+    const size_t measured = atoms == 1 ? walk.size() : backbone_.size();
+    if (measured == 0)
+        throw Error(LD_ERR_INVALID, atoms == 1 ? "the ligand has no atom named CA or P" : "the complex has no atom named CA or P");
+    if (atoms == 0 && (dev_.anm_rec > 0 || walk.empty())) walk.insert(walk.end(), rec_.backbone.begin(), rec_.backbone.end());
+    // the bound comes before anything reads the list
+    const size_t per_pose = walk.size() * 3 * sizeof(int32_t);
+    if (n > kRankedWorkspaceBytes / per_pose)
+        throw Error(LD_ERR_INVALID, "the list's workspace (" + std::to_string(per_pose) + " B a pose) would exceed 4 GiB");
+    if (n == 0) {
+        *n_clusters = 0;
+        return;
+    }
+    if (!scoring || !cluster_of || !representatives) throw Error(LD_ERR_INVALID, "null argument");
+    check_poses(n, poses, stride);
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(scoring[i])) throw Error(LD_ERR_INVALID, "scoring " + std::to_string(i) + " is not finite");
+
+    // (scoring descending, index ascending); everything on the device is indexed by sorted position
+    std::vector<int32_t> order(n);
+    for (size_t i = 0; i < n; i++) order[i] = (int32_t)i;
+    std::stable_sort(order.begin(), order.end(), [scoring](int32_t a, int32_t b) { return scoring[a] > scoring[b]; });
+    const size_t len = pose_len();
+    std::vector<double> sorted(n * len);
+    for (size_t p = 0; p < n; p++) std::copy(poses + (size_t)order[p] * stride, poses + (size_t)order[p] * stride + len, &sorted[p * len]);
+
+    upload_poses(n, sorted.data(), len);
+    const size_t walk_bytes = (walk.size() * sizeof(uint32_t) + 7) / 8 * 8;
+    d_ids_.reserve(sizeof(RankedStatus) + walk_bytes + 2 * n * sizeof(int32_t));
+    RankedStatus *d_status = static_cast<RankedStatus *>(d_ids_.ptr);
+    uint32_t *d_walk = reinterpret_cast<uint32_t *>(d_status + 1);
+    RankedLaunch r;
+    r.n = (int)n;
+    r.n_walk = (int)walk.size();
+    r.status = d_status;
+    r.state = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(d_walk) + walk_bytes);
+    r.reps = r.state + n;
+    d_ranked_ws_.reserve(n * per_pose);
+    int32_t *d_ws = static_cast<int32_t *>(d_ranked_ws_.ptr);
+    hip_check(hipMemcpyAsync(d_walk, walk.data(), walk.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_), "hipMemcpy H2D walk");
+    hip_check(hipEventRecord(ev0_, stream_), "hipEventRecord");
+    hip_check(launch_ranked_begin(r, cutoff, (double)measured, stream_), "ranked_begin launch");
+    hip_check(launch_ranked_pose(dev_, static_cast<const double *>(d_poses_.ptr), len, r.n, d_walk, r.n_walk, d_ws, d_status, stream_),
+              "ranked_pose launch");
+    // a round: the pick's candidates, then the sweep behind them (sized from the cursor BEFORE the pick, which the sweep
+    // corrects from the status); the host reads the status once a round.  Every round resolves a candidate or ends the loop.
+    const char *beyond = "a posed CA / P coordinate is beyond +-2.1e6 A";
+    RankedStatus st;
+    int from = 0;
+    for (;;) {
+        hip_check(launch_ranked_pick(r, d_ws, stream_), "ranked_pick launch");
+        hip_check(launch_ranked_sweep(r, d_ws, from, stream_), "ranked_sweep launch");
+        hip_check(hipMemcpyAsync(&st, d_status, sizeof st, hipMemcpyDeviceToHost, stream_), "hipMemcpy D2H status");
+        hip_check(hipStreamSynchronize(stream_), "ranked round");
+        if (st.overflow) throw Error(LD_ERR_INVALID, beyond);
+        if (st.n_candidates == 0) break;
+        if (st.cursor <= from || st.cursor > r.n) throw Error(LD_ERR_DEVICE, "ranked clustering: the cursor did not advance");
+        from = st.cursor;
+    }
+    finish_timed(&d_status->overflow, "ranked clustering", beyond);
+    const size_t k = (size_t)st.n_clusters;
+    std::vector<int32_t> state(n), reps(k);
+    hip_check(hipMemcpy(state.data(), r.state, n * sizeof(int32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
+    hip_check(hipMemcpy(reps.data(), r.reps, k * sizeof(int32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
+    for (size_t p = 0; p < n; p++) cluster_of[order[p]] = state[p];
+    for (size_t c = 0; c < n; c++) representatives[c] = c < k ? order[reps[c]] : -1;
+    *n_clusters = (uint32_t)k;
+}
+
 void Complex::contacts(size_t n, const double *poses, size_t stride, double cutoff, uint32_t *rec_bits, uint32_t *lig_bits) {
     const long long C = cutoff_thousandths(cutoff, "cutoff must be 0.001 .. 30 A");
     if (n == 0) return;

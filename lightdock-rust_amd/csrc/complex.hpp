@@ -11,6 +11,7 @@
 #include "host/pdb_file.hpp"
 #include "kernels/assess.hpp"
 #include "kernels/cluster.hpp"
+#include "kernels/ranked.hpp"
 
 namespace ld {
 
@@ -31,6 +32,9 @@ class Complex {
     void coordinates(size_t n, const double *poses, size_t stride, double *xyz_out);
     void cluster(size_t n_swarms, size_t n_glowworms, const double *poses, size_t stride, const double *scoring, double cutoff,
                  int32_t *cluster_of, int32_t *representatives, uint32_t *n_clusters);
+    // One ranked list across swarms (lightdock_hip.h, "Clustering a ranked list")
+    void cluster_ranked(size_t n, const double *poses, size_t stride, const double *scoring, double cutoff, int atoms,
+                        int32_t *cluster_of, int32_t *representatives, uint32_t *n_clusters);
     void contacts(size_t n, const double *poses, size_t stride, double cutoff, uint32_t *rec_bits, uint32_t *lig_bits);
     void write_pdb(const double *pose, const char *path);
     // Model quality against a reference complex (lightdock_hip.h, "Model quality")
@@ -66,6 +70,7 @@ class Complex {
     } ref_;
     DeviceBuffer d_ref_atoms_, d_ref_xyz_, d_ref_native_;  // behind ref_.dev: a later reference reuses them
     DeviceBuffer d_poses_, d_scores_, d_out_, d_ws_, d_ids_;
+    DeviceBuffer d_ranked_ws_;  // cluster_ranked's resident thousandths (up to kRankedWorkspaceBytes), apart from d_ws_
     hipStream_t stream_ = nullptr;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
     double last_kernel_ms_ = 0.0;

@@ -7,7 +7,7 @@
 //                              pass one representative at a time;
 //   complex_contacts:          one workgroup a pose: which receptor and which ligand residues touch (ld_complex_contacts;
 //                              what lgd_filter_restraints.py and lgd_filter_membrane.py ask of a model's PDB file).
-// Posing and the thousandths: kernels/complex_pose.hpp, shared with kernels/assess.hip.  Workspace: the thousandths of a
+// Posing, the thousandths and the RMSD test: kernels/complex_pose.hpp, shared with kernels/assess.hip and kernels/ranked.hip.  Workspace: the thousandths of a
 // chunk of swarms, at most kClusterWorkspaceBytes (or one swarm's n_glowworms x n_backbone x 12 B if more; 1czy: 420 KB a
 // swarm); ld_complex_coordinates poses in chunks of that bound.
 #include "kernels/cluster.hpp"
@@ -55,11 +55,6 @@ __global__ void __launch_bounds__(kPoseThreads) complex_pose_thousandths(Complex
             ws[(sb * 3 + k) * G + g] = (int32_t)fmax(-2147483647.0, fmin(2147483647.0, c[k]));
         }
     }
-}
-
-// round(rmsd, 4) <= cutoff with rmsd = sqrt(S / n) in A, S in thousandths^2.  Non-decreasing in S.
-__device__ __forceinline__ bool within_cutoff(double S, double n, double cutoff) {
-    return rint(sqrt(S * 1e-6 / n) * 1e4) / 1e4 <= cutoff;
 }
 
 __global__ void __launch_bounds__(kBsasThreads) complex_bsas(const int32_t *ws, const double *scoring, int G, int n_bb,

@@ -1,5 +1,6 @@
-// complex_pose.hpp -- device code the analysis kernels share (kernels/cluster.hip, kernels/assess.hip): the posing of one
-// atom of a complex, the rounding to the thousandths "%8.3f" prints, and the 32-bit contact test on two atoms' thousandths.
+// complex_pose.hpp -- device code the analysis kernels share (kernels/cluster.hip, kernels/assess.hip, kernels/ranked.hip):
+// the posing of one atom of a complex, the rounding to the thousandths "%8.3f" prints, the clustering's RMSD test, and the
+// 32-bit contact test on two atoms' thousandths.
 // Include from a .hip file only.
 // Posing: receptor R_a + sum_m rec_ext[m] rec_mode[m][a]; ligand rotate(q, L_a + sum_m lig_ext[m] lig_mode[m][a]) + t,
 // i.e. the ligand's modes in the ligand frame -- NOT the energy's convention (src/dfire.rs:282-302).  f64, qt.rs order,
@@ -67,6 +68,11 @@ __device__ __forceinline__ double thousandths(double x) {
         if (e < 0.0) return f;
     }
     return rint(p);  // round half to even, as printf does on an exact tie
+}
+
+// round(rmsd, 4) <= cutoff with rmsd = sqrt(S / n) in A, S in thousandths^2.  Non-decreasing in S.
+__device__ __forceinline__ bool within_cutoff(double S, double n, double cutoff) {
+    return rint(sqrt(S * 1e-6 / n) * 1e4) / 1e4 <= cutoff;
 }
 
 // --- the contact test on two atoms' thousandths (int4: x, y, z, unused), for cutoffs C <= 30000 -----------------------
