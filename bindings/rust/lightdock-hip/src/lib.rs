@@ -34,6 +34,38 @@ pub struct LdScorerDesc {
     pub potential: *const f64,
 }
 
+/// `ld_energy_terms`: the terms of one pose's energy (include/lightdock_hip.h, "Energy decomposition").
+#[allow(non_camel_case_types)]
+#[derive(Clone, Copy, Default)]
+#[repr(C)]
+pub struct ld_energy_terms {
+    pub pair: [f64; 2],
+    pub score: f64,
+    pub rec_restraints: f64,
+    pub lig_restraints: f64,
+    pub membrane: f64,
+    pub energy: f64,
+    pub pairs: u32,
+    pub rec_interface: u32,
+    pub lig_interface: u32,
+    pub reserved: u32,
+}
+
+/// `ld_group_energies`: the groups of one side and where their rows go; any pointer may be null.
+#[allow(non_camel_case_types)]
+#[repr(C)]
+pub struct ld_group_energies {
+    pub group_of_atom: *const u32,
+    pub n_groups: usize,
+    pub sums: *mut f64,
+    pub pairs: *mut u32,
+    pub interface_atoms: *mut u32,
+}
+
+pub const LD_GROUP_NONE: u32 = 0xffff_ffff;
+
+// The decomposition and residue entry points (ld_scorer_decompose*, ld_model_*) are declared only: no wrapper uses them yet.
+#[allow(dead_code)]
 extern "C" {
     fn ld_init(device: c_int) -> c_int;
     fn ld_last_error() -> *const c_char;
@@ -43,6 +75,16 @@ extern "C" {
     fn ld_scorer_energy(s: *mut c_void, t: *const f64, q_wxyz: *const f64, rec_nm: *const f64, lig_nm: *const f64,
                         out: *mut f64) -> c_int;
     fn ld_scorer_energy_batch(s: *mut c_void, n: usize, poses: *const f64, stride: usize, out: *mut f64) -> c_int;
+    fn ld_scorer_decompose(s: *mut c_void, n: usize, poses: *const f64, stride: usize, terms_out: *mut ld_energy_terms,
+                           receptor: *const ld_group_energies, ligand: *const ld_group_energies) -> c_int;
+    fn ld_scorer_decompose_info(s: *const c_void, slice_poses_out: *mut usize, last_kernel_ms_out: *mut f64) -> c_int;
+    fn ld_model_from_pdb(method: c_int, pdb_path: *const c_char, active: *const *const c_char, n_active: usize,
+                         passive: *const *const c_char, n_passive: usize, nmodes: *const f64, nmodes_len: usize, num_anm: usize) -> *mut c_void;
+    fn ld_model_view(m: *const c_void, out: *mut LdMolecule) -> c_int;
+    fn ld_model_destroy(m: *mut c_void);
+    fn ld_model_num_residues(m: *const c_void) -> usize;
+    fn ld_model_residue_id(m: *const c_void, index: usize, buf: *mut c_char, buf_len: usize) -> c_int;
+    fn ld_model_residue_of_atom(m: *const c_void, out: *mut u32) -> c_int;
     fn ld_gso_create(s: *mut c_void, n_swarms: usize, n_glowworms: usize, positions: *const f64, seeds: *const u64) -> *mut c_void;
     fn ld_gso_destroy(g: *mut c_void);
     fn ld_gso_run(g: *mut c_void, steps: u32) -> c_int;

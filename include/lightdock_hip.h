@@ -115,6 +115,13 @@ ld_model *ld_model_from_pdb(int method, const char *pdb_path, const char *const 
                             size_t num_anm);
 int ld_model_view(const ld_model *m, ld_molecule *out);
 void ld_model_destroy(ld_model *m);
+/* Residue labels in the model's atom order (host-side, no GPU): a residue is a maximal run of consecutive atoms of the
+ * walk with one residue id, "<chain>.<resname>.<serial><icode>" (AtomRecord::residue_id, src/dfire.rs:139-142); indices
+ * count runs in atom order, so ld_model_residue_of_atom is ascending and covers every atom.  It is the group map
+ * ld_scorer_decompose takes for per-residue energies. */
+size_t ld_model_num_residues(const ld_model *m);
+int ld_model_residue_id(const ld_model *m, size_t index, char *buf, size_t buf_len);
+int ld_model_residue_of_atom(const ld_model *m, uint32_t *out /* n_atoms */);
 
 /* Host-side constants of the DFIRE kernel, exported for tests (DESIGN.md "bin LUT"):
  * the table bin DIST_TO_BINS[(sqrt(d2)*2-1) as usize]-1 (src/dfire.rs:49-53,336-337) of any
@@ -245,6 +252,63 @@ int ld_scorer_kernel_info(const ld_scorer *s, ld_kernel_info *out);
  * the last reset; reading also resets. */
 int ld_scorer_enable_timing(ld_scorer *s, int enable);
 int ld_scorer_pair_kernel_time(ld_scorer *s, double *total_ms_out, uint64_t *launches_out);
+
+/* ------------------------------------------------------------------------------------
+ * Energy decomposition: which terms make up a pose's energy, and which atoms or groups of atoms (residues) carry it.
+ * Its own kernels with a defined order of every sum, so a pose's results are the same bits whatever the batch, its place
+ * in it, the launch shape or the pass size.  The definition:
+ *   Posing: as the energy path, ligand atom q v q^-1 + t, then both molecules' ANM terms in ascending mode order
+ *     (src/dfire.rs:282-320, src/qt.rs:57-61); d2 = dx dx + dy dy + dz dz, left to right, unfused, dx = receptor - ligand.
+ *   Pair of receptor atom i and ligand atom j, DFIRE (src/dfire.rs:334-343): if d2 <= 225 the pair counts and contributes
+ *     v = potential[type_i * 3380 + type_j * 20 + bin], bin = DIST_TO_BINS[(sqrt(d2) * 2 - 1) as usize] - 1, which at
+ *     r = 15.0 reads past the row like the reference; the pair is interface iff sqrt(d2) * 2 - 1 <= 3.9.
+ *   DNA / PYDOCK (src/dna.rs:476-511), true f64 divisions, the reference's comparisons (a NaN stays a NaN):
+ *     d2 <= 900: e = q_i q_j / d2, e > 4/332 -> 4/332, e < -4/332 -> -4/332; the pair counts and contributes e to term 0;
+ *     d2 <= 100: p6 = powi(r_i + r_j, 6) / powi(d2, 3), k = sqrt(eps_i eps_j) (p6 p6 - 2 p6), k > 1 -> 1; k to term 1;
+ *     d2 <= 3.9 * 3.9: interface.   powi(x, 6) = x2 (x2 x2), x2 = x x;  powi(x, 3) = x x x.
+ *   Atom of either side: per term (DFIRE 1, DNA / PYDOCK 2) the f64 sum of its pairs' contributions taken sequentially in
+ *     ascending partner index from 0.0; the number of its counting pairs; whether any of its pairs is interface.
+ *   Group: the sequential sum from 0.0, in ascending atom index, of its atoms' sums, counts and flags.
+ *   Pose (ld_energy_terms): pair[k] = the RECEPTOR atoms' sums of term k added in ascending atom order from 0.0;
+ *     score = (pair[0] * 0.0157 - 4.7) * -1 (src/dfire.rs:347) or (pair[0] * 332 / 4 + pair[1]) * -1 (src/dna.rs:513-514);
+ *     rec_restraints, lig_restraints, membrane: the fractions of src/scoring.rs:21-47 over the per-atom flags (0 without
+ *     restraints / beads); energy = score + rec_restraints * score + lig_restraints * score - penalty, penalty =
+ *     999 * membrane where membrane > 0 (src/dfire.rs:349-361); pairs, rec_interface, lig_interface: counting pairs and
+ *     flagged atoms.
+ * Every pair is evaluated twice, once for each of its atoms.  Poses run in passes of at most `slice` poses
+ * (ld_scorer_decompose_info), slice = clamp(64 MiB / per-pose workspace bytes, 1, 4096); a lane owns one atom and walks the
+ * other molecule through LDS in chunks, whose size changes no sum.
+ * ---------------------------------------------------------------------------------- */
+#define LD_GROUP_NONE (0xffffffffu) /* atom belongs to no group */
+typedef struct ld_energy_terms {
+    double pair[2];        /* DFIRE: [1] is 0 */
+    double score;
+    double rec_restraints;
+    double lig_restraints;
+    double membrane;
+    double energy;
+    uint32_t pairs;
+    uint32_t rec_interface;
+    uint32_t lig_interface;
+    uint32_t reserved;     /* 0 */
+} ld_energy_terms;
+typedef struct ld_group_energies { /* one side; any pointer may be NULL */
+    const uint32_t *group_of_atom; /* n_atoms(side), values < n_groups or LD_GROUP_NONE; NULL: every atom its own group, n_groups is then taken as n_atoms(side) */
+    size_t n_groups;
+    double *sums;                  /* n x n_groups x 2 (DFIRE: [1] is 0) */
+    uint32_t *pairs;               /* n x n_groups */
+    uint32_t *interface_atoms;     /* n x n_groups */
+} ld_group_energies;
+/* Host pointers, synchronous.  poses: n rows of `stride` >= pose_len doubles.  n == 0 is LD_OK and touches nothing.  Groups
+ * need not be contiguous; an empty group yields zeros.  LD_ERR_INVALID, every output as it was: stride < pose_len, a group
+ * id >= n_groups, n_groups == 0 with a map (both also where none of that side's rows is asked for), n x n_groups x 16
+ * beyond a size_t, poses missing.  Device staging beyond the workspace: slice x n_groups x 24 B a side. */
+int ld_scorer_decompose(ld_scorer *s, size_t n, const double *poses, size_t stride,
+                        ld_energy_terms *terms_out /* n, may be NULL */,
+                        const ld_group_energies *receptor /* may be NULL */,
+                        const ld_group_energies *ligand /* may be NULL */);
+/* Either output may be NULL.  last_kernel_ms: the kernels of the last ld_scorer_decompose call, all passes (HIP events). */
+int ld_scorer_decompose_info(const ld_scorer *s, size_t *slice_poses_out, double *last_kernel_ms_out);
 
 /* ------------------------------------------------------------------------------------
  * GSO: batched over independent swarms.  Replaces GSO::new / GSO::run

@@ -54,6 +54,18 @@ class _ScorerDesc(C.Structure):
                 ("potential", C.c_void_p)]
 
 
+class _GroupEnergies(C.Structure):
+    _fields_ = [("group_of_atom", C.c_void_p), ("n_groups", C.c_size_t), ("sums", C.c_void_p), ("pairs", C.c_void_p),
+                ("interface_atoms", C.c_void_p)]
+
+
+# ld_energy_terms as a structured dtype (72 bytes, no padding)
+ENERGY_TERMS = np.dtype([("pair", np.float64, (2,)), ("score", np.float64), ("rec_restraints", np.float64),
+                         ("lig_restraints", np.float64), ("membrane", np.float64), ("energy", np.float64),
+                         ("pairs", np.uint32), ("rec_interface", np.uint32), ("lig_interface", np.uint32),
+                         ("reserved", np.uint32)])
+GROUP_NONE = 0xffffffff                # LD_GROUP_NONE
+
 _lib = None
 
 
@@ -132,6 +144,12 @@ def load_library():
     lib.ld_model_from_pdb.argtypes = [C.c_int, C.c_char_p, vp, sz, vp, sz, vp, sz, sz]
     lib.ld_model_view.argtypes = [vp, C.POINTER(_Molecule)]
     lib.ld_model_destroy.argtypes = [vp]
+    lib.ld_model_num_residues.restype = sz
+    lib.ld_model_num_residues.argtypes = [vp]
+    lib.ld_model_residue_id.argtypes = [vp, sz, C.c_char_p, sz]
+    lib.ld_model_residue_of_atom.argtypes = [vp, vp]
+    lib.ld_scorer_decompose.argtypes = [vp, sz, vp, sz, vp, C.POINTER(_GroupEnergies), C.POINTER(_GroupEnergies)]
+    lib.ld_scorer_decompose_info.argtypes = [vp, C.POINTER(sz), C.POINTER(C.c_double)]
     lib.ld_dfire_bin_lut.argtypes = [vp, vp, C.POINTER(C.c_double)]
     lib.ld_dfire_packed_lut.argtypes = [C.c_int, C.c_double, vp, C.POINTER(C.c_double)]
     lib.ld_dfire_bm_lut.argtypes = [C.c_double, C.c_double, vp, C.POINTER(C.c_double)]
@@ -204,7 +222,9 @@ def _np_from(ptr, n, ctype, dtype):
 
 def model_from_pdb(method, pdb_path, active=(), passive=(), nmodes=None, num_anm=0):
     """Host-side DockingModel::new (src/dfire.rs:115-190, src/dna.rs:249-364); no GPU involved.
-    Returns the ld_molecule fields as a dict of numpy arrays (usable with Scorer.from_arrays)."""
+    Returns the ld_molecule fields as a dict of numpy arrays (usable with Scorer.from_arrays), and the model's residues:
+    "residues", the ids ("A.SER.467") of the runs of consecutive atoms with one id, and "residue_of_atom", a group map
+    for Scorer.decompose."""
     lib = load_library()
     method = METHODS.get(method, method)
     a, na, k1 = _strings(active)
@@ -230,6 +250,13 @@ def model_from_pdb(method, pdb_path, active=(), passive=(), nmodes=None, num_anm
                 out[k] = _np_from(getattr(v, k), n, C.c_double, np.float64)
         if v.nmodes:
             out["nmodes"] = _np_from(v.nmodes, int(v.num_anm) * n * 3, C.c_double, np.float64)
+        buf = C.create_string_buffer(64)
+        out["residues"] = []
+        for i in range(lib.ld_model_num_residues(h)):
+            _check(lib.ld_model_residue_id(h, i, buf, len(buf)))
+            out["residues"].append(buf.value.decode())
+        out["residue_of_atom"] = np.zeros(n, dtype=np.uint32)
+        _check(lib.ld_model_residue_of_atom(h, _ptr(out["residue_of_atom"])))
         return out
     finally:
         lib.ld_model_destroy(h)
@@ -448,6 +475,49 @@ class Scorer:
         _check(self.lib.ld_scorer_energy_batch_device(self._h, n, C.c_void_p(d_poses), stride,
                                                       C.c_void_p(d_active) if d_active else None, C.c_void_p(d_energies),
                                                       C.c_void_p(d_pair_counts) if d_pair_counts else None))
+
+    def decompose(self, poses, rec_groups=None, lig_groups=None, atoms=False):
+        """Which terms make up each pose's energy and which groups of atoms carry it (ld_scorer_decompose; the definition
+        is in lightdock_hip.h, "Energy decomposition").  poses: (n, >= pose_len).  rec_groups / lig_groups: a group id per
+        atom of that side (GROUP_NONE: no group), e.g. model_from_pdb(...)["residue_of_atom"]; atoms=True: every atom its
+        own group on the sides without a map.  Returns {"terms": structured array (n,) of ENERGY_TERMS, "rec", "lig":
+        {"sums" (n, groups, 2), "pairs" (n, groups), "interface" (n, groups)} or None}.  Sums are raw, not in score units."""
+        poses = _f64(poses)
+        if poses.ndim != 2:
+            raise ValueError("poses must be (n, pose_len)")
+        n = poses.shape[0]
+        out = {"terms": np.zeros(n, dtype=ENERGY_TERMS), "rec": None, "lig": None}
+        structs, keep = [None, None], []
+        for side, (key, groups) in enumerate((("rec", rec_groups), ("lig", lig_groups))):
+            if groups is None and not atoms:
+                continue
+            g = _GroupEnergies()
+            if groups is None:
+                n_groups = self.num_atoms(side)
+            else:
+                gmap = np.ascontiguousarray(groups, dtype=np.uint32).ravel()
+                if gmap.size != self.num_atoms(side):
+                    raise ValueError("one group id per atom")
+                keep.append(gmap)
+                g.group_of_atom = _ptr(gmap)
+                ids = gmap[gmap != GROUP_NONE]
+                n_groups = int(ids.max()) + 1 if ids.size else 1
+            g.n_groups = n_groups
+            res = {"sums": np.zeros((n, n_groups, 2)), "pairs": np.zeros((n, n_groups), dtype=np.uint32),
+                   "interface": np.zeros((n, n_groups), dtype=np.uint32)}
+            g.sums, g.pairs, g.interface_atoms = _ptr(res["sums"]), _ptr(res["pairs"]), _ptr(res["interface"])
+            out[key] = res
+            structs[side] = g
+        _check(self.lib.ld_scorer_decompose(self._h, n, _ptr(poses), poses.shape[1], _ptr(out["terms"]),
+                                            None if structs[0] is None else C.byref(structs[0]),
+                                            None if structs[1] is None else C.byref(structs[1])))
+        return out
+
+    def decompose_info(self):
+        """{"slice": poses per pass of decompose(), "last_kernel_ms": its kernels in the last call (HIP events)}."""
+        slice_poses, ms = C.c_size_t(), C.c_double()
+        _check(self.lib.ld_scorer_decompose_info(self._h, C.byref(slice_poses), C.byref(ms)))
+        return {"slice": slice_poses.value, "last_kernel_ms": ms.value}
 
     def enable_timing(self, on=True):
         _check(self.lib.ld_scorer_enable_timing(self._h, 1 if on else 0))

@@ -156,6 +156,22 @@ int ld_model_view(const ld_model *m, ld_molecule *out) {
     });
 }
 void ld_model_destroy(ld_model *m) { delete m; }
+size_t ld_model_num_residues(const ld_model *m) { return m ? m->model.residue_ids.size() : 0; }
+int ld_model_residue_id(const ld_model *m, size_t index, char *buf, size_t buf_len) {
+    return guarded([&] {
+        if (!m || !buf) throw ld::Error(LD_ERR_INVALID, "null argument");
+        if (index >= m->model.residue_ids.size()) throw ld::Error(LD_ERR_INVALID, "residue index out of range");
+        const std::string &id = m->model.residue_ids[index];
+        if (id.size() + 1 > buf_len) throw ld::Error(LD_ERR_INVALID, "buffer too short for the residue id");
+        std::memcpy(buf, id.c_str(), id.size() + 1);
+    });
+}
+int ld_model_residue_of_atom(const ld_model *m, uint32_t *out) {
+    return guarded([&] {
+        if (!m || !out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        std::memcpy(out, m->model.residue_of_atom.data(), m->model.residue_of_atom.size() * sizeof(uint32_t));
+    });
+}
 
 int ld_dfire_bin_lut(uint8_t *lut_out, double *steps_out, double *interface_d2_out) {
     return guarded([&] {
@@ -349,6 +365,22 @@ int ld_scorer_pair_kernel_time(ld_scorer *s, double *total_ms_out, uint64_t *lau
     return guarded([&] {
         if (!s) throw ld::Error(LD_ERR_INVALID, "null scorer");
         s->impl.pair_kernel_time(total_ms_out, launches_out);
+    });
+}
+
+int ld_scorer_decompose(ld_scorer *s, size_t n, const double *poses, size_t stride, ld_energy_terms *terms_out,
+                        const ld_group_energies *receptor, const ld_group_energies *ligand) {
+    return guarded([&] {
+        if (!s) throw ld::Error(LD_ERR_INVALID, "null scorer");
+        if (n == 0) return;
+        s->decompose().run(n, poses, stride, terms_out, receptor, ligand, s->impl.stream());
+    });
+}
+int ld_scorer_decompose_info(const ld_scorer *s, size_t *slice_poses_out, double *last_kernel_ms_out) {
+    return guarded([&] {
+        if (!s) throw ld::Error(LD_ERR_INVALID, "null scorer");
+        if (slice_poses_out) *slice_poses_out = ld::Decomposer::slice_of(s->desc.view());
+        if (last_kernel_ms_out) *last_kernel_ms_out = s->decomposer ? s->decomposer->last_kernel_ms() : 0.0;
     });
 }
 

@@ -147,6 +147,8 @@ DockingModel build_docking_model(int method, const Structure &structure,
         if (a.res_name == "MMB" && a.name == "BJ") m.membrane.push_back(static_cast<uint32_t>(i));
 
         const std::string rid = a.residue_id();
+        if (m.residue_ids.empty() || m.residue_ids.back() != rid) m.residue_ids.push_back(rid);
+        m.residue_of_atom.push_back(static_cast<uint32_t>(m.residue_ids.size() - 1));
         if (std::find(active_restraints.begin(), active_restraints.end(), rid) != active_restraints.end()) {
             auto ins = group_of.emplace(rid, groups.size());
             if (ins.second) {

@@ -21,6 +21,9 @@ struct DockingModel {
     std::vector<uint32_t> restraint_atoms;
     size_t num_anm = 0;
     std::vector<double> nmodes;                  // num_anm x n x 3
+    // residues of the walk: maximal runs of consecutive atoms with one residue id (src/dfire.rs:139-142)
+    std::vector<std::string> residue_ids;
+    std::vector<uint32_t> residue_of_atom;       // n, ascending
     // DFIRE
     std::vector<uint32_t> dfire_types;           // 0..167 (src/dfire.rs:105)
     // DNA

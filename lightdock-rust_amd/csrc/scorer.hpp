@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "decompose.hpp"
 #include "device_memory.hpp"
 #include "host/error.hpp"
 #include "kernels/dfire_bm.hpp"
@@ -290,6 +291,12 @@ class Scorer {
 }  // namespace ld
 
 struct ld_scorer {
-    ld::Scorer impl;
-    explicit ld_scorer(const ld_scorer_desc &d) : impl(d) {}
+    ld::Scorer impl;                               // checks the description before anything below reads it
+    ld::DescCopy desc;                             // what the decomposer is built from, on first use
+    std::unique_ptr<ld::Decomposer> decomposer;
+    explicit ld_scorer(const ld_scorer_desc &d) : impl(d), desc(d) {}
+    ld::Decomposer &decompose() {
+        if (!decomposer) decomposer.reset(new ld::Decomposer(desc.view()));
+        return *decomposer;
+    }
 };

@@ -53,6 +53,26 @@ def load_nmodes(side, sim):
     raise FileNotFoundError("neither %s_nm.npy nor lightdock_%s.nm.npy found" % (side, side))
 
 
+def build_scorer(pkg, setup, sim, method):
+    """The scorer of a run: setup.json's restraints and ANM, the PDB files next to it, DCparams for DFIRE."""
+    method = method.lower()
+    use_anm = bool(setup["use_anm"])
+    kw = dict(use_anm=use_anm, rec_num_anm=int(setup["anm_rec"]), lig_num_anm=int(setup["anm_lig"]))
+    for side, key in (("rec", "receptor_restraints"), ("lig", "ligand_restraints")):
+        r = setup.get(key)
+        if r is not None:
+            kw[side + "_active"], kw[side + "_passive"] = r["active"], r["passive"]
+    if use_anm:
+        if kw["rec_num_anm"] > 0:
+            kw["rec_nmodes"] = load_nmodes("rec", sim)
+        if kw["lig_num_anm"] > 0:
+            kw["lig_nmodes"] = load_nmodes("lig", sim)
+    if method == "dfire":
+        kw["potential"] = pkg.load_dcparams(os.path.join(os.environ.get("LIGHTDOCK_DATA", "data"), "DCparams"))
+    return pkg.Scorer.from_pdb(method, os.path.join(sim, "lightdock_" + setup["receptor_pdb"]),
+                               os.path.join(sim, "lightdock_" + setup["ligand_pdb"]), **kw)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("setup")
@@ -73,22 +93,8 @@ def main(argv=None):
     pkg.init(local)
     setup = json.load(open(args.setup))
     sim = os.path.dirname(os.path.abspath(args.setup))
-    method = args.method.lower()
     use_anm = bool(setup["use_anm"])
-    kw = dict(use_anm=use_anm, rec_num_anm=int(setup["anm_rec"]), lig_num_anm=int(setup["anm_lig"]))
-    for side, key in (("rec", "receptor_restraints"), ("lig", "ligand_restraints")):
-        r = setup.get(key)
-        if r is not None:
-            kw[side + "_active"], kw[side + "_passive"] = r["active"], r["passive"]
-    if use_anm:
-        if kw["rec_num_anm"] > 0:
-            kw["rec_nmodes"] = load_nmodes("rec", sim)
-        if kw["lig_num_anm"] > 0:
-            kw["lig_nmodes"] = load_nmodes("lig", sim)
-    if method == "dfire":
-        kw["potential"] = pkg.load_dcparams(os.path.join(os.environ.get("LIGHTDOCK_DATA", "data"), "DCparams"))
-    scorer = pkg.Scorer.from_pdb(method, os.path.join(sim, "lightdock_" + setup["receptor_pdb"]),
-                                 os.path.join(sim, "lightdock_" + setup["ligand_pdb"]), **kw)
+    scorer = build_scorer(pkg, setup, sim, args.method)
 
     swarms = parse_swarm_list(args.swarms)
     mine = [swarms[k] for k in pkg.multi.shard(len(swarms), rank, world)]
