@@ -1112,7 +1112,7 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
     // The batch code (dfire_bm_batch.inc) reads the LUT at `cell` and a cube row at `code + a constant of the instruction`: both
     // assume S at LDS address 0 with the LUT first.  Another __shared__ object or a different placement would make it read wrong
     // codes silently: trap instead (the compiler folds the test away when the address is the 0 it assigns today).  The block also
-    // clobbers v220..v255, i.e. it needs the 256 registers of two waves per SIMD.
+    // clobbers v228..v255 (its ANM deformation block v220..v251), i.e. it needs the 256 registers of two waves per SIMD.
     static_assert(offsetof(BmShared, lut) == 0, "the LUT's cell is its LDS address");
     static_assert(kBmWaves * kBmGroupsPerCu == 8, "dfire_bm_batch.inc clobbers v220..v255: 256 VGPRs a wave = two waves per SIMD");
     if ((uint32_t)(uintptr_t)&S != 0u) __builtin_trap();

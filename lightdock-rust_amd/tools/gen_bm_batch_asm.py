@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Writes csrc/kernels/dfire_bm_batch.inc: the 64 pair slots of one batch of dfire_bm_pairs (kernels/dfire_bm.hip) as ONE
-block of gfx950 instructions, software-pipelined by hand in 8 stages of 8 slots.
+block of gfx950 instructions, software-pipelined by hand in 16 granules of 4 slots (schedule(), PRODUCT below).
 
 A slot = (ligand atom i, receptor atom j) of the block, lane = pose:
     E = (Rs_j - l2_i) + Rz_j lz_i + Ry_j ly_i + Rx_j lx_i        packed f32, two receptor atoms (a pair record) per instruction
@@ -8,20 +8,23 @@ A slot = (ligand atom i, receptor atom j) of the block, lane = pose:
     code = lut[cell]                                               ds_read_u8, the LUT sits at LDS address 0
     value = cube[row(i, j)][code]                                  ds_read_b64; the row's LDS address is an instruction constant
     acc += value                                                   v_lshl_add_u64: 64-bit fixed point, exact and order-free
-Stage h (receptor pair record g = h / 2, ligand atoms 4 (h % 2) .. + 3):  A(h) cells and LUT reads; C(h - 2) the adds of the
-table values requested one stage ago; B(h - 1) the table reads of the codes requested one stage ago.  One s_waitcnt per
-stage (LDS results return in order: when the table values of stage h - 2 are in, so are the codes of stage h - 1), instead
-of the one per add the compiler's schedule had.  Written by hand because at two waves per SIMD every instruction a wave
-issues, scalar or wait, costs it a turn.
+Granule q = one receptor pair record g against the two ligand atoms of one pair register p (q = 4 g + p): E(q), its cells and
+its four LUT reads; ONE counted s_waitcnt; the adds of granule q - 3; the table reads of granule q - 1.  LDS results return in
+order: lgkmcnt(8) leaves the table reads of granule q - 2 and the LUT reads of granule q in flight.  Until r07 the block ran in
+8 stages of 8 slots (stage_a / stage_b / stage_c below = schedule() with its defaults; kept as the microbenchmark's baseline):
+the same distances counted in slots, but reads and adds in runs of eight -- the finer grain, not a longer distance, is what
+the two waves of a SIMD gain from (profiles/r08_batch_schedule.txt).  Written by hand because at two waves per
+SIMD every instruction a wave issues, scalar or wait, costs it a turn.
 
-Temporaries are fixed registers (clobbered): v[220:235] table values, v[236:243] / v[244:251]
-cells and codes, v[252:255] the two packed E.  Operands: acc, acc1 (outputs, 64 bit: the sums over the pairs with the even / odd receptor atom of a record), Rs0..3 Rz0..3 Ry0..3 Rx0..3 (the block's receptor
+Temporaries are fixed registers (clobbered): v[228:243] two sets of 4 table values, v[244:251] two sets of 4 cells / codes,
+v[252:255] the two packed E.  Operands: acc, acc1 (outputs, 64 bit: the sums over the pairs with the even / odd receptor atom of a record), Rs0..3 Rz0..3 Ry0..3 Rx0..3 (the block's receptor
 records, wave-uniform: scalar register pairs), l2/lz/ly/lx0..3 = the values of the lane's ligand atoms (2p, 2p + 1), cube = LDS address of the wave's cube.
 """
 import os
 
 ROW = 176
-T0 = 220   # first of the block's 36 fixed temporaries (tools/microbench/gen_mfma_batch.py moves them for its three-waves-per-SIMD form)
+PRODUCT = dict(G=4, dl=1, dt=2)   # the schedule of the shipped block (schedule()'s arguments)
+T0 = 220   # first of the 36 fixed temporaries of the block in 8 stages (stage_a / stage_b / stage_c; tools/microbench/gen_mfma_batch.py moves them for its three-waves-per-SIMD form)
 
 
 def stage_a(h):
@@ -69,6 +72,140 @@ def stage_c(h):
     return out
 
 
+def quad_order(half_major=False):
+    """The batch's 16 quads (receptor pair record g, ligand pair register p) = 4 slots each, in issue order: record-major (g, then p:
+    the product's) or ligand-half-major (atoms 0-3 against the four records, then atoms 4-7)."""
+    if half_major:
+        return [(g, 2 * half + t) for half in range(2) for g in range(4) for t in range(2)]
+    return [(g, p) for g in range(4) for p in range(4)]
+
+
+def schedule(G=8, dl=1, dt=1, chains=2, half_major=False, spread=False, t0=None):
+    """The batch as a software pipeline of granules of G slots (8: a stage of the docstring above, 4: half of one).  Granule q issues
+    E(q) and the cells, the LUT reads of q, ONE counted wait, the adds of granule q - dl - dt and the table reads of granule q - dl:
+    dl / dt = the distance, in granules, from a LUT read to its table read / from a table read to its add.  chains = the number of
+    independent packed E chains (2: one quad at a time, 4: the two quads of a granule of 8 interleaved).  The arithmetic of a slot,
+    its row constant and its sum (even / odd receptor atom of the record) do not depend on any of this; schedule() with the defaults IS the
+    product's block of the docstring.  spread: the granule begins with the wait, and the adds and table reads are issued one by one
+    between the granule's E operations instead of in two runs behind them (the LDS sees a read every other instruction, not
+    runs of G; needs dl >= 2: with dl = 1 the wait would ask for the LUT reads just issued).  Temporaries, downwards from v255: 2 * chains E, dl + 1 (spread: dl) sets of G cells / codes, dt sets of G
+    table values.  LDS results return in order and lgkmcnt counts to 15 only: each wait's count is derived from the issue order
+    (the reads issued after the last one the granule needs), capped at 15, and the register hazards are checked (check_block).
+    Returns (lines, first temporary)."""
+    assert G in (4, 8) and chains in (2, 4) and (chains == 2 or G == 8)
+    quads = quad_order(half_major)
+    per = G // 4                                  # quads per granule
+    Q = 16 // per
+    c_sets = dl if spread else dl + 1            # (spread: granule q's cells are formed after the table reads of granule q - dl took theirs)
+    n_e, n_c, n_t = 2 * chains, c_sets * G, dt * 2 * G
+    if t0 is None:
+        t0 = 256 - (n_e + n_c + n_t)
+    ts0, cs0, e0 = t0, t0 + n_t, t0 + n_t + n_c
+    cells = lambda q: cs0 + G * (q % c_sets)
+    tvals = lambda q: ts0 + 2 * G * (q % dt)
+    lines, issued = [], []                        # issued: (kind, granule) of every LDS read so far
+
+    def e_ops(q):
+        out = []
+        for c0 in range(0, per, chains // 2):     # chains / 2 quads at a time
+            group = range(c0, c0 + chains // 2)
+            regs = {u: ("v[%d:%d]" % (e0 + 4 * (u - c0), e0 + 4 * (u - c0) + 1), "v[%d:%d]" % (e0 + 4 * (u - c0) + 2, e0 + 4 * (u - c0) + 3)) for u in group}
+            steps = [[], [], [], []]
+            for u in group:
+                g, p = quads[q * per + u]
+                ea, eb = regs[u]
+                # ligand atoms 2p, 2p + 1 = the two halves of the pair registers l2/lz/ly/lx[p]: op_sel broadcasts the half
+                steps[0] += ["v_pk_add_f32 %s, %%[rs%d], %%[l2%d] op_sel:[0,0] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]" % (ea, g, p),
+                             "v_pk_add_f32 %s, %%[rs%d], %%[l2%d] op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" % (eb, g, p)]
+                for s, c in enumerate("zyx"):
+                    steps[s + 1] += ["v_pk_fma_f32 %s, %%[r%s%d], %%[l%s%d], %s op_sel:[0,0,0] op_sel_hi:[1,0,1]" % (ea, c, g, c, p, ea),
+                                     "v_pk_fma_f32 %s, %%[r%s%d], %%[l%s%d], %s op_sel:[0,1,0] op_sel_hi:[1,1,1]" % (eb, c, g, c, p, eb)]
+            out += sum(steps, [])
+            for u in group:
+                out += ["v_cvt_u32_f32 v%d, v%d" % (cells(q) + 4 * u + k, e0 + 4 * (u - c0) + k) for k in range(4)]
+        return out
+
+    def add_op(qc, k):
+        # two running sums (acc: the pairs with receptor atom 2g, acc1: 2g + 1); a sum's FIRST add takes 0 as its addend
+        acc = "%[acc]" if k % 2 == 0 else "%[acc1]"
+        return "v_lshl_add_u64 %s, v[%d:%d], 0, %s" % (acc, tvals(qc) + 2 * k, tvals(qc) + 2 * k + 1, "0" if qc == 0 and k < 2 else acc)
+
+    def tbl_op(qb, k):
+        g, p = quads[qb * per + k // 4]
+        row = (2 * p + (k % 4) // 2) * 8 + 2 * g + (k % 2)
+        return "ds_read_b64 v[%d:%d], v%d offset:%%c[cube]+%d" % (tvals(qb) + 2 * k, tvals(qb) + 2 * k + 1, cells(qb) + k, row * ROW)
+
+    def wait_for(qb, qc):
+        need = [i for i, (kind, r) in enumerate(issued) if (kind == "lut" and r == qb) or (kind == "tbl" and r == qc)]
+        if need:
+            lines.append("s_waitcnt lgkmcnt(%d)" % min(15, len(issued) - 1 - max(need)))
+
+    for q in range(Q + dl + dt):
+        qb, qc = q - dl, q - dl - dt
+        if spread:
+            assert dl >= 2 and G == 4
+            wait_for(qb, qc)
+            # (add k of granule qc reads the registers that table read k of granule qb, right behind it, will write)
+            mixed = sum([([add_op(qc, k)] if 0 <= qc < Q else []) + ([tbl_op(qb, k)] if 0 <= qb < Q else []) for k in range(G)], [])
+            ops = e_ops(q) if q < Q else []
+            ev, cv = [l for l in ops if not l.startswith("v_cvt")], [l for l in ops if l.startswith("v_cvt")]
+            step = max(1, len(ev) // max(1, len(mixed))) if mixed else 0
+            while ev or mixed:
+                lines += ev[:step] if mixed else ev
+                ev = ev[step:] if mixed else []
+                if mixed:
+                    lines.append(mixed.pop(0))
+            lines += cv
+            if 0 <= qb < Q:
+                issued += [("tbl", qb)] * G
+            if q < Q:
+                lines += ["ds_read_u8 v%d, v%d" % (cells(q) + k, cells(q) + k) for k in range(G)]
+                issued += [("lut", q)] * G
+            continue
+        if q < Q:
+            lines += e_ops(q)
+            lines += ["ds_read_u8 v%d, v%d" % (cells(q) + k, cells(q) + k) for k in range(G)]
+            issued += [("lut", q)] * G
+        wait_for(qb, qc)
+        if 0 <= qc < Q:
+            lines += [add_op(qc, k) for k in range(G)]
+        if 0 <= qb < Q:
+            lines += [tbl_op(qb, k) for k in range(G)]
+            issued += [("tbl", qb)] * G
+    check_block(lines)
+    return lines, t0
+
+
+def check_block(lines):
+    """Replays a block's issue order against its waits: no instruction may read, or write, a register that an LDS read still in flight
+    will write (in flight = issued and not yet behind a wait's count; LDS results return in order), every slot's table value is
+    added exactly once, and no wait asks for a count lgkmcnt cannot hold."""
+    import re
+    def regs(text):
+        out = set()
+        for a, b in re.findall(r"v\[(\d+):(\d+)\]", text):
+            out |= set(range(int(a), int(b) + 1))
+        return out | set(int(r) for r in re.findall(r"\bv(\d+)\b", text))
+    flight = []                                   # destination registers of the reads in flight, oldest first
+    rows, added = [], 0
+    for l in lines:
+        if l.startswith("s_waitcnt"):
+            n = int(re.search(r"lgkmcnt\((\d+)\)", l).group(1))
+            assert 0 <= n <= 15, l
+            flight = flight[len(flight) - n:] if n < len(flight) else flight
+            continue
+        ops = l.split(None, 1)[1]
+        dst = regs(ops.split(", ")[0])
+        busy = set().union(*flight) if flight else set()
+        assert not (regs(ops) & busy), "register of a read in flight touched: " + l
+        if l.startswith("ds_read"):
+            flight.append(dst)
+            if l.startswith("ds_read_b64"):
+                rows.append(int(l.rsplit("+", 1)[1]) // ROW)
+        added += l.startswith("v_lshl_add_u64")
+    assert not flight and sorted(rows) == list(range(64)) and added == 64
+
+
 def pose_block():
     """Two of the lane's 8 ligand atoms posed at a time: l = A x + t' (the affine map of bm_apply, same operations and nesting,
     so the culling kernel's boxes and the exact path's re-evaluation see the same bits), and |l|^2.  Operands: A0xy = {r00, r01},
@@ -106,7 +243,7 @@ def flex_block():
     """The deformation of one subtile's 8 atoms for the lane's pose (src/dfire.rs:288-320): D[pc] = sum_k amplitude_k x mode_k of the
     atoms (2p, 2p + 1)'s coordinate c, pc = 3 p + c -- twelve packed sums of ten terms.  The subtile's modes lie in LDS in this
     order (BmModel: ((pc * 10 + k) * 2 + atom of the pair) floats), sixty 16-byte broadcast reads of two modes each; EIGHT are
-    kept in flight in the fixed registers v[220:251] (the batch's temporaries, free here), every wait counted.  (As C++ the
+    kept in flight in the fixed registers v[220:251] (the batch's temporaries and eight below them, free here), every wait counted.  (As C++ the
     compiler, out of registers, issued each read, waited for it and only then multiplied: 120 LDS round trips a batch, and
     the ANM form ran at 6.4 us a batch against the rigid form's 2.4.)  The first term is a product, the others fused
     multiply-adds in mode order: bm_recheck repeats exactly this.  Operands: D0..D11 (outputs), A0..A4 (the molecule's
@@ -165,16 +302,7 @@ def dma_block():
 
 
 def main():
-    lines = []
-    for h in range(10):
-        if h < 8:
-            lines += stage_a(h)
-        if h >= 1:
-            lines.append("s_waitcnt lgkmcnt(%d)" % (8 if h < 8 else 0))
-        if h >= 2:
-            lines += stage_c(h - 2)
-        if 1 <= h <= 8:
-            lines += stage_b(h - 1)
+    lines, t0 = schedule(**PRODUCT)
     body = " \\\n".join('    "%s\\n\\t"' % l for l in lines)
     def operands(r_constraint):
         ops = []
@@ -189,7 +317,7 @@ def main():
             ops += ['[%s%d] "v"(%s[%d])' % (name, p, arr, p) for p in range(4)]
         return ops
     ops_in = operands("s")
-    clobbers = ", ".join('"v%d"' % r for r in range(220, 256))
+    clobbers = ", ".join('"v%d"' % r for r in range(t0, 256))
     here = os.path.dirname(os.path.abspath(__file__))
     path = os.path.join(here, "..", "csrc", "kernels", "dfire_bm_batch.inc")
     with open(path, "w") as f:

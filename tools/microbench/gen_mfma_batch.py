@@ -26,6 +26,34 @@ TS = 220          # v[220:235]: table values
 CS = 236          # v[236:251]: cells / codes, two sets of 8
 
 
+# r08 (the batch schedule at two waves per SIMD): (macro tag, description, prod.schedule arguments)
+SCHEDULES = [
+    ("BASE", "8 stages of 8 again, from schedule()", dict()),
+    ("A", "(a) four E chains", dict(chains=4)),
+    ("B", "(b) LUT reads two stages ahead", dict(dl=2)),
+    ("C", "(c) two sets of table values", dict(dt=2)),
+    ("D", "(d) ligand-half-major order", dict(half_major=True)),
+    ("AC", "(a)+(c)", dict(chains=4, dt=2)),
+    ("BC", "(b)+(c)", dict(dl=2, dt=2)),
+    ("ABC", "(a)+(b)+(c)", dict(chains=4, dl=2, dt=2)),
+    ("ACD", "(a)+(c)+(d)", dict(chains=4, dt=2, half_major=True)),
+    ("G4_11", "granules of 4 slots, distances 1/1", dict(G=4)),
+    ("G4_12", "granules of 4 slots, distances 1/2", dict(G=4, dt=2)),
+    ("G4_22", "granules of 4 slots, distances 2/2", dict(G=4, dl=2, dt=2)),
+    ("G4_23", "granules of 4 slots, distances 2/3", dict(G=4, dl=2, dt=3)),
+    ("G4_33", "granules of 4 slots, distances 3/3", dict(G=4, dl=3, dt=3)),
+    ("G4_13", "granules of 4 slots, distances 1/3", dict(G=4, dt=3)),
+    ("S4_21", "granules of 4, reads spread, distances 2/1", dict(G=4, dl=2, dt=1, spread=True)),
+    ("S4_22", "granules of 4, reads spread, distances 2/2", dict(G=4, dl=2, dt=2, spread=True)),
+    ("S4_23", "granules of 4, reads spread, distances 2/3", dict(G=4, dl=2, dt=3, spread=True)),
+    ("S4_32", "granules of 4, reads spread, distances 3/2", dict(G=4, dl=3, dt=2, spread=True)),
+    ("S4_33", "granules of 4, reads spread, distances 3/3", dict(G=4, dl=3, dt=3, spread=True)),
+    ("S4_42", "granules of 4, reads spread, distances 4/2", dict(G=4, dl=4, dt=2, spread=True)),
+    ("G4_23D", "granules of 4 slots, 2/3, (d)", dict(G=4, dl=2, dt=3, half_major=True)),
+]
+NOLDS_TOO = ("A",)
+
+
 def rows_of(h):
     """slot k of stage h -> (ligand atom i, receptor atom j): ligand atoms 2 (h % 4) + (k / 4), receptor atoms 4 (h / 4) + k % 4"""
     return [((2 * (h % 4) + k // 4), 4 * (h // 4) + k % 4) for k in range(8)]
@@ -100,7 +128,7 @@ def main():
     path = os.path.join(HERE, "mfma_batch_gen.inc")
     with open(path, "w") as f:
         f.write("// GENERATED by tools/microbench/gen_mfma_batch.py -- do not edit.\n")
-        # the product's block, verbatim
+        # the block in 8 stages of 8 slots (the product's until r07), verbatim
         lines = []
         for h in range(10):
             if h < 8:
@@ -162,6 +190,19 @@ def main():
         mins.append('[cube] "n"(CUBE)')
         clob = ['"v%d"' % r for r in range(D0, 252)]
         write_macro(f, "MB_BATCH_MFMA", mfma_lines(), outs, mins, clob)
+        # r08: schedules of the product's 64 slots (prod.schedule: granule, LUT -> table and table -> add distances, E chains, quad
+        # order); the same slots, rows and sums as MB_BATCH_VALU -- the host compares every form's sums with its.  "_NOLDS": timing only.
+        forms = []
+        for tag, text, kw in SCHEDULES:
+            sl, t0 = prod.schedule(**kw)
+            clob_s = ['"v%d"' % r for r in range(t0, 256)]
+            write_macro(f, "MB_S_" + tag, sl, outs, ins, clob_s)
+            forms.append((len(forms) + 10, "MB_S_" + tag, "%s [%d regs]" % (text, 256 - t0), 1))
+            if tag in NOLDS_TOO:
+                write_macro(f, "MB_S_%s_NOLDS" % tag, [l for l in fix_waits(no_lut(sl)) if not l.startswith("ds_read_b64")], outs, ins, clob_s)
+                forms.append((len(forms) + 10, "MB_S_%s_NOLDS" % tag, text + ", no LDS read at all", 0))
+        f.write("// X(form number, macro, description, sums comparable with the product's)\n#define MB_SCHED_FORMS(X) \\\n")
+        f.write(" \\\n".join('    X(%d, %s, "%s", %d)' % fm for fm in forms) + "\n")
         write_macro(f, "MB_BATCH_MFMA_ONLY", mfma_lines(mfma_only=True), outs, mins, clob)
         write_macro(f, "MB_BATCH_REST_ONLY", mfma_lines(valu_only=True), outs, mins, clob)
     print("wrote", path)

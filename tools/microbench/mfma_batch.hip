@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "mfma_batch_gen.inc"
@@ -54,7 +55,11 @@ __device__ __forceinline__ void batch(unsigned long long &acc0, unsigned long lo
         MB_BATCH_VALU_NOLUT_B32;
     } else if (FORM == 7) {
         MB_BATCH_VALU_NOLDS;
-    } else {
+    }
+#define MB_X(id, M, name, cmp) else if (FORM == id) { M; }
+    MB_SCHED_FORMS(MB_X)
+#undef MB_X
+    else {
         float NL2[8], LZ1[8], LY1[8], LX1[8];
 #pragma unroll
         for (int p = 0; p < 4; p++) {
@@ -234,8 +239,78 @@ static double time_form(const char *name, Args A, int groups, std::vector<unsign
     return us_batch;
 }
 
+// ---- r08: the batch's schedules (gen_mfma_batch.py: SCHEDULES) against the product's block, interleaved over rounds in ONE process:
+// usage: mfma_batch sched [batches per wave] [rounds].  Every form's sums must equal the product's.  ("The product's block" here and
+// above = MB_BATCH_VALU, the block in 8 stages of 8 slots that shipped until r07; what ships since is the form G4_12 of the list.)
+struct Timing { double us, ghz; };
+template <int FORM>
+static Timing time_once(Args A, int groups, std::vector<unsigned long long> *sums) {
+    hipEvent_t e0, e1;
+    CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
+    CHECK(hipMemset(A.stamps, 0, 16));
+    CHECK(hipEventRecord(e0));
+    hipLaunchKernelGGL(run<FORM>, dim3(groups), dim3(kWaves * 64), 0, 0, A);
+    CHECK(hipEventRecord(e1)); CHECK(hipEventSynchronize(e1));
+    float ms; CHECK(hipEventElapsedTime(&ms, e0, e1));
+    CHECK(hipEventDestroy(e0)); CHECK(hipEventDestroy(e1));
+    unsigned long long h[2]; CHECK(hipMemcpy(h, A.stamps, 16, hipMemcpyDeviceToHost));
+    if (sums) {
+        sums->resize((size_t)groups * kWaves * 64);
+        CHECK(hipMemcpy(sums->data(), A.out, sums->size() * 8, hipMemcpyDeviceToHost));
+    }
+    return Timing{ms * 1e3 / A.batches, h[1] ? (double)h[0] / ((double)h[1] * 10.0) : 0.0};
+}
+struct SchedForm { const char *name; int compare; Timing (*fn)(Args, int, std::vector<unsigned long long> *); };
+static int run_schedules(Args A, int groups, int rounds) {
+    const SchedForm forms[] = {
+        {"product's block", 1, time_once<0>},
+        {"product's, no LDS read at all", 0, time_once<7>},
+#define MB_X(id, M, name, cmp) {name, cmp, time_once<id>},
+        MB_SCHED_FORMS(MB_X)
+#undef MB_X
+        {"product's block, again (last of the round)", 1, time_once<0>},
+    };
+    const int n = (int)(sizeof(forms) / sizeof(forms[0]));
+    std::vector<unsigned long long> ref, got;
+    std::vector<std::vector<Timing>> t(n);
+    int bad = 0;
+    Args W = A; W.batches = 200; W.stamps = A.stamps;
+    for (int f = 0; f < n; f++) forms[f].fn(W, groups, nullptr);   // code objects loaded, every form warm
+    for (int r = 0; r < rounds; r++)
+        for (int f = 0; f < n; f++) {
+            const bool cmp = r == 0 && forms[f].compare;
+            t[f].push_back(forms[f].fn(A, groups, cmp ? (f == 0 ? &ref : &got) : nullptr));
+            if (cmp && f > 0) {
+                size_t differ = 0;
+                for (size_t i = 0; i < ref.size(); i++) differ += ref[i] != got[i];
+                if (differ) { std::printf("!! %s: sums differ from the product's in %zu of %zu lanes\n", forms[f].name, differ, ref.size()); bad++; }
+            }
+        }
+    std::printf("# %d rounds, every form once per round in this order; us = per batch of a wave, two waves a SIMD; cycles = us x the held shader clock\n", rounds);
+    std::printf("%-48s %9s %9s %9s %9s %9s %9s\n", "form", "us mean", "us min", "us max", "GHz mean", "cycles", "vs product");
+    double base = 0.0;
+    for (int f = 0; f < n; f++) {
+        double su = 0, sg = 0, sc = 0, lo = 1e30, hi = 0;
+        for (const Timing &x : t[f]) { su += x.us; sg += x.ghz; sc += x.us * 1e3 * x.ghz; lo = std::fmin(lo, x.us); hi = std::fmax(hi, x.us); }
+        su /= rounds; sg /= rounds; sc /= rounds;
+        if (f == 0) base = su;
+        std::printf("%-48s %9.4f %9.4f %9.4f %9.3f %9.0f %+8.2f %%\n", forms[f].name, su, lo, hi, sg, sc, 100.0 * (su / base - 1.0));
+    }
+    for (int r = 0; r < rounds; r++) {
+        std::printf("# round %d us:", r);
+        for (int f = 0; f < n; f++) std::printf(" %.4f", t[f][r].us);
+        std::printf("\n");
+    }
+    std::printf("%s\n", bad ? "SUMS DIFFER" : "every comparable form's sums equal the product's, lane for lane");
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
+    const bool sched = argc > 1 && std::string(argv[1]) == "sched";
+    if (sched) { argc--; argv++; }
     const int batches = argc > 1 ? std::atoi(argv[1]) : 2000;
+    const int rounds = sched && argc > 2 ? std::atoi(argv[2]) : 5;
+    if (sched) argc = 1;   // (the distance range: the default, 30 % of the slots inside the cutoff)
     const double near_a = argc > 2 ? std::atof(argv[2]) : 10.0, far_a = argc > 3 ? std::atof(argv[3]) : 26.0;   // the subtiles' distance range, A
     hipDeviceProp_t prop; CHECK(hipGetDeviceProperties(&prop, 0));
     const int groups = prop.multiProcessorCount * 2;
@@ -278,6 +353,10 @@ int main(int argc, char **argv) {
     CHECK(hipMalloc(&d_maps, maps.size() * 4)); CHECK(hipMemcpy(d_maps, maps.data(), maps.size() * 4, hipMemcpyHostToDevice));
     CHECK(hipMalloc(&d_out, (size_t)groups * kWaves * 64 * 8)); CHECK(hipMalloc(&d_st, 16));
     A.lut = d_lut; A.rows = d_rows; A.rec = d_rec; A.maps = d_maps; A.n_maps = n_maps; A.batches = batches; A.out = d_out; A.stamps = d_st;
+    if (sched) {
+        std::printf("# %d workgroups of %d waves (2 per CU: 2 waves per SIMD), %d batches per wave\n", groups, kWaves, batches);
+        return run_schedules(A, groups, rounds);
+    }
     std::vector<unsigned long long> s_valu, s_mfma;
     {   // the share of pair slots inside the cutoff (host replay of a sample of the poses)
         size_t in = 0, all = 0;
