@@ -6,52 +6,24 @@ lgd_rank.py, lgd_top.py), with the posing and clustering of every swarm in ONE l
 Reads swarm_<i>/gso_<step>.out and writes swarm_<i>/cluster.repr, rank_by_scoring.list and top/top_<k>.pdb.
 Path rules as launch.py.  No per-glowworm PDB files are written.
 """
-import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
 try:
-    from .launch import load_nmodes, parse_swarm_list
+    from .run_dir import argument_parser, build_complex, open_run, ranking, read_gso, swarm_list
 except ImportError:  # run as a script
-    from launch import load_nmodes, parse_swarm_list
+    from run_dir import argument_parser, build_complex, open_run, ranking, read_gso, swarm_list
 
 RANK_HEADER = ("Swarm  Glowworm   Coordinates                                             RecID  LigID  Luciferin  Neigh   VR"
                "     RMSD    PDB             Clashes  Scoring\n")
-COLUMNS = (("rec_id", int), ("lig_id", int), ("luciferin", float), ("neighbors", int), ("vision_range", float), ("scoring", float))
-
-
-def read_gso(path):
-    """gso_<step>.out -> (poses (G, columns), dict of the per-glowworm columns)."""
-    poses, cols = [], {k: [] for k, _ in COLUMNS}
-    for line in open(path):
-        if line.startswith("("):
-            inner, rest = line[1:].split(")", 1)
-            poses.append([float(v) for v in inner.split(",")])
-            for (k, kind), v in zip(COLUMNS, rest.split()):
-                cols[k].append(kind(v))
-    return np.array(poses), {k: np.array(v) for k, v in cols.items()}
 
 
 def cluster_repr_lines(cluster_of, representatives, n_clusters, scoring):
     """lgd_cluster_bsas.py's cluster.repr of one swarm."""
     sizes = np.bincount(cluster_of, minlength=n_clusters)
     return ["%d:%d:%8.5f:%d:lightdock_%d.pdb\n" % (c, sizes[c], scoring[r], r, r) for c, r in enumerate(representatives[:n_clusters])]
-
-
-def ranking(swarms, step, base="."):
-    """lgd_rank.py: the representatives of every swarm (swarm, then cluster order) from cluster.repr, sorted by scoring,
-    highest first (stable).  Entries: (swarm, glowworm, pose row, columns)."""
-    entries = []
-    for s in swarms:
-        d = os.path.join(base, "swarm_%d" % s)
-        poses, cols = read_gso(os.path.join(d, "gso_%d.out" % step))
-        for line in filter(str.strip, open(os.path.join(d, "cluster.repr"))):
-            g = int(line.split(":")[3])
-            entries.append((s, g, poses[g], {k: v[g] for k, v in cols.items()}))
-    return sorted(entries, key=lambda e: e[3]["scoring"], reverse=True)
 
 
 def rank_by_scoring_text(entries):
@@ -67,28 +39,15 @@ def printed_pose(pose):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("setup")
-    ap.add_argument("step", type=int)
-    ap.add_argument("--swarms", default=None, help="e.g. 0-9 or 0,3,7 (default: every swarm of setup.json)")
+    ap = argument_parser(every=False)
     ap.add_argument("--top", type=int, default=10, help="number of top_<k>.pdb files")
     ap.add_argument("--cutoff", type=float, default=4.0, help="BSAS RMSD cutoff (A)")
     args = ap.parse_args(argv)
 
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import __graft_entry__ as ge
-    pkg = ge.package()
-    pkg.init(-1)
-    setup = json.load(open(args.setup))
-    sim = os.path.dirname(os.path.abspath(args.setup))
-    kw = {}
-    for side in ("rec", "lig"):
-        kw[side + "_num_anm"] = n = int(setup["anm_" + side]) if setup["use_anm"] else 0
-        if n > 0:
-            kw[side + "_nmodes"] = load_nmodes(side, sim)
-    cx = pkg.Complex(os.path.join(sim, "lightdock_" + setup["receptor_pdb"]), os.path.join(sim, "lightdock_" + setup["ligand_pdb"]), **kw)
+    pkg, setup, sim = open_run(args.setup)
+    cx = build_complex(pkg, setup, sim)
 
-    swarms = parse_swarm_list(args.swarms) if args.swarms else list(range(int(setup["swarms"])))
+    swarms = swarm_list(args.swarms, setup)
     runs = [read_gso(os.path.join("swarm_%d" % s, "gso_%d.out" % args.step)) for s in swarms]
     if len({p.shape for p, _ in runs}) != 1 or runs[0][0].shape[1] < cx.pose_len:
         raise ValueError("every gso_%d.out must hold as many glowworms, of at least %d columns" % (args.step, cx.pose_len))

@@ -4,7 +4,7 @@ with ALL candidates in ONE ld_scorer_decompose call on the GPU (include/lightdoc
     cd run_dir && python lightdock-rust_amd/decompose.py <setup.json> <step> <dfire|dna|pydock> [--swarms 0-9] [--all] [--top N]
 
 The scorer is built as launch.py builds it (setup.json's restraints and ANM, DCparams for DFIRE).  Candidates as filter.py:
-the entries analyse.ranking() forms from swarm_<i>/cluster.repr and gso_<step>.out, or with --all every glowworm of every
+the entries run_dir.ranking() forms from swarm_<i>/cluster.repr and gso_<step>.out, or with --all every glowworm of every
 selected swarm by scoring; --top N keeps the first N.  Each is decomposed at the full-precision pose of its gso file.
 
   decomposition/terms.list      per candidate: swarm, glowworm, the gso file's scoring, energy, score, the pair terms (DFIRE:
@@ -19,21 +19,15 @@ selected swarm by scoring; --top N keeps the first N.  Each is decomposed at the
 Residues are those of the scoring model's atom walk (ld_model_residue_of_atom).  The library returns raw sums; the scaling
 to score units is the plain functions below.  Path rules as launch.py.
 """
-import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
 try:
-    from .analyse import ranking
-    from .filter import all_glowworms
-    from .launch import build_scorer, parse_swarm_list
+    from .run_dir import argument_parser, build_scorer, candidates, open_run, pose_matrix, swarm_list
 except ImportError:  # run as a script
-    from analyse import ranking
-    from filter import all_glowworms
-    from launch import build_scorer, parse_swarm_list
+    from run_dir import argument_parser, build_scorer, candidates, open_run, pose_matrix, swarm_list
 
 MEMBRANE_PENALTY_SCORE = 999.0   # src/constants.rs
 # energies are printed with 17 significant digits: the lists hold the doubles the library returned
@@ -91,33 +85,21 @@ def parse_list(text):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("setup")
-    ap.add_argument("step", type=int)
+    ap = argument_parser()
     ap.add_argument("method")
-    ap.add_argument("--swarms", default=None, help="e.g. 0-9 or 0,3,7 (default: every swarm of setup.json)")
-    ap.add_argument("--all", action="store_true", help="every glowworm, not only the ranked cluster representatives")
     ap.add_argument("--top", type=int, default=None, help="only the first N candidates")
     args = ap.parse_args(argv)
 
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import __graft_entry__ as ge
-    pkg = ge.package()
-    pkg.init(-1)
-    setup = json.load(open(args.setup))
-    sim = os.path.dirname(os.path.abspath(args.setup))
+    pkg, setup, sim = open_run(args.setup)
     method = args.method.lower()
     dfire = method == "dfire"
     scorer = build_scorer(pkg, setup, sim, method)
     models = [pkg.model_from_pdb(method, os.path.join(sim, "lightdock_" + setup[key])) for key in ("receptor_pdb", "ligand_pdb")]
 
-    swarms = parse_swarm_list(args.swarms) if args.swarms else list(range(int(setup["swarms"])))
-    entries = all_glowworms(swarms, args.step) if args.all else ranking(swarms, args.step)
+    entries = candidates(swarm_list(args.swarms, setup), args.step, args.all)
     if args.top is not None:
         entries = entries[:max(0, args.top)]
-    if any(len(e[2]) < scorer.pose_len for e in entries):
-        raise ValueError("gso_%d.out must hold poses of at least %d columns" % (args.step, scorer.pose_len))
-    poses = np.array([e[2][:scorer.pose_len] for e in entries]).reshape(len(entries), scorer.pose_len)
+    poses = pose_matrix(entries, args.step, scorer.pose_len)
     out = scorer.decompose(poses, rec_groups=models[0]["residue_of_atom"], lig_groups=models[1]["residue_of_atom"])
 
     os.makedirs("decomposition", exist_ok=True)

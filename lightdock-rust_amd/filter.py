@@ -5,7 +5,7 @@ ld_complex_contacts call on the GPU.
     cd run_dir && python lightdock-rust_amd/filter.py <setup.json> <step> [--swarms 0-9] [--all] [--restraints FILE]
                                                        [--cutoff 5.0] [--fnat 0.4] [--max-beads N] [--write-pdb]
 
-Candidates: the entries of rank_by_scoring.list as analyse.ranking() forms them from swarm_<i>/cluster.repr and
+Candidates: the entries of rank_by_scoring.list as run_dir.ranking() forms them from swarm_<i>/cluster.repr and
 gso_<step>.out (the full-precision pose of the gso file); with --all every glowworm of every selected swarm, by scoring,
 highest first, ties in (swarm, glowworm) order.  Per candidate: `rec` / `lig` = the fraction of the receptor's / ligand's
 restraint residues (active + passive; blocked ones are ignored) in contact with the other molecule, -1 for a side without
@@ -14,19 +14,15 @@ rec >= fnat and lig >= fnat and beads <= N.  Writes filtered/rank_filtered.list 
 filtered/swarm_<s>_<g>.pdb.  The contact rule is this project's (include/lightdock_hip.h, "Interface contacts"), modelled on
 LightDock's tools; its files are not claimed to equal theirs byte for byte.  Path rules as launch.py.
 """
-import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
 try:
-    from .analyse import ranking, read_gso
-    from .launch import load_nmodes, parse_swarm_list
+    from .run_dir import all_glowworms, argument_parser, build_complex, candidates, open_run, pose_matrix, swarm_list  # noqa: F401
 except ImportError:  # run as a script
-    from analyse import ranking, read_gso
-    from launch import load_nmodes, parse_swarm_list
+    from run_dir import all_glowworms, argument_parser, build_complex, candidates, open_run, pose_matrix, swarm_list  # noqa: F401
 
 FILTER_HEADER = "Swarm  Glowworm     Scoring      Rec      Lig   Beads\n"
 BEAD_RESIDUE = "MMB"   # the reference's membrane beads (src/dfire.rs:107)
@@ -90,26 +86,13 @@ def keep_mask(rec, lig, beads, fnat, max_beads=None):
     return keep if max_beads is None else keep & (beads <= max_beads)
 
 
-def all_glowworms(swarms, step, base="."):
-    """Every glowworm of every swarm as analyse.ranking() entries, by scoring, highest first, ties in (swarm, glowworm) order."""
-    entries = []
-    for s in swarms:
-        poses, cols = read_gso(os.path.join(base, "swarm_%d" % s, "gso_%d.out" % step))
-        entries += [(s, g, poses[g], {k: v[g] for k, v in cols.items()}) for g in range(len(poses))]
-    return sorted(entries, key=lambda e: (-e[3]["scoring"], e[0], e[1]))
-
-
 def rank_filtered_text(entries, rec, lig, beads, keep):
     return FILTER_HEADER + "".join("%5d %9d %11.5f %8.3f %8.3f %7d\n" % (e[0], e[1], e[3]["scoring"], rec[i], lig[i], beads[i])
                                    for i, e in enumerate(entries) if keep[i])
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("setup")
-    ap.add_argument("step", type=int)
-    ap.add_argument("--swarms", default=None, help="e.g. 0-9 or 0,3,7 (default: every swarm of setup.json)")
-    ap.add_argument("--all", action="store_true", help="every glowworm, not only the ranked cluster representatives")
+    ap = argument_parser()
     ap.add_argument("--restraints", default=None, help="a LightDock restraints list instead of setup.json's restraints")
     ap.add_argument("--cutoff", type=float, default=5.0, help="contact distance (A)")
     ap.add_argument("--fnat", type=float, default=0.4, help="least fraction of restraint residues in contact, per side")
@@ -117,29 +100,16 @@ def main(argv=None):
     ap.add_argument("--write-pdb", action="store_true", help="filtered/swarm_<s>_<g>.pdb of every kept model")
     args = ap.parse_args(argv)
 
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    import __graft_entry__ as ge
-    pkg = ge.package()
-    pkg.init(-1)
-    setup = json.load(open(args.setup))
-    sim = os.path.dirname(os.path.abspath(args.setup))
-    kw = {}
-    for side in ("rec", "lig"):
-        kw[side + "_num_anm"] = n = int(setup["anm_" + side]) if setup["use_anm"] else 0
-        if n > 0:
-            kw[side + "_nmodes"] = load_nmodes(side, sim)
-    cx = pkg.Complex(os.path.join(sim, "lightdock_" + setup["receptor_pdb"]), os.path.join(sim, "lightdock_" + setup["ligand_pdb"]), **kw)
+    pkg, setup, sim = open_run(args.setup)
+    cx = build_complex(pkg, setup, sim)
 
     wanted = parse_restraints_list(open(args.restraints).read()) if args.restraints else setup_restraints(setup)
     residues = {"rec": cx.residues(0), "lig": cx.residues(1)}
     columns = {"rec": restraint_columns(wanted["rec"], residues["rec"], "receptor"),
                "lig": restraint_columns(wanted["lig"], residues["lig"], "ligand")}
 
-    swarms = parse_swarm_list(args.swarms) if args.swarms else list(range(int(setup["swarms"])))
-    entries = all_glowworms(swarms, args.step) if args.all else ranking(swarms, args.step)
-    if any(len(e[2]) < cx.pose_len for e in entries):
-        raise ValueError("gso_%d.out must hold poses of at least %d columns" % (args.step, cx.pose_len))
-    poses = np.array([e[2][:cx.pose_len] for e in entries]).reshape(len(entries), cx.pose_len)
+    entries = candidates(swarm_list(args.swarms, setup), args.step, args.all)
+    poses = pose_matrix(entries, args.step, cx.pose_len)
     contact = cx.contacts(poses, args.cutoff)
     rec, lig = fractions(contact["rec"], columns["rec"]), fractions(contact["lig"], columns["lig"])
     beads = bead_counts(contact["rec"], residues["rec"])

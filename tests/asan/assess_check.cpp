@@ -9,17 +9,9 @@
 #include <string>
 #include <vector>
 
+#define CHECK_PROGRAM "assess_check"
+#include "check.hpp"
 #include "kernels/assess.hpp"
-#include "lightdock_hip.h"
-
-static int failures = 0;
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "assess_check: %s failed at line %d (%s)\n", #cond, __LINE__, ld_last_error()); \
-            failures++;                                                                                          \
-        }                                                                                                        \
-    } while (0)
 
 struct Point {
     long long x, y, z;
@@ -106,19 +98,8 @@ static void numerics() {
     CHECK(i < 1e-6 && std::fabs(l - std::sqrt(0.5)) < 1e-6);   // sqrt((0 + 1) / 2)
 }
 
-static void put(const std::string &path, const std::string &text) {
-    std::FILE *f = std::fopen(path.c_str(), "wb");
-    if (f) {
-        std::fwrite(text.data(), 1, text.size(), f);
-        std::fclose(f);
-    }
-}
-
-static std::string atom_line(int serial, const char *name, const char *res, char chain, int seq, double x, double y, double z) {
-    char buf[128];
-    std::snprintf(buf, sizeof buf, "ATOM  %5d %-4s %3s %c%4d    %8.3f%8.3f%8.3f  1.00  0.00\n", serial, name, res, chain, seq, x, y, z);
-    return buf;
-}
+// The columns of a record after its coordinates: occupancy, B-factor, the line end.
+static const char *const kRest = "  1.00  0.00\n";
 
 static void through_the_abi(const std::string &golden, const std::string &scratch) {
     const std::string rec = golden + "/1ppe/lightdock_1ppe_e.pdb", lig = golden + "/1ppe/lightdock_1ppe_i.pdb";
@@ -190,15 +171,15 @@ static void through_the_abi(const std::string &golden, const std::string &scratc
     ld_complex_destroy(c);
 
     // hand-made complexes: the least a reference may have, and one atom less
-    const std::string r3 = atom_line(1, "N", "GLY", 'A', 1, 0, 0, 0) + atom_line(2, "CA", "GLY", 'A', 1, 1.5, 0, 0) +
-                           atom_line(3, "C", "GLY", 'A', 1, 1.5, 1.5, 0) + atom_line(4, "CB", "GLY", 'A', 1, 0, 1.5, 1.5);
-    const std::string l1 = atom_line(1, "P", "DT", 'B', 1, 3.0, 4.0, 0) + atom_line(2, "OP1", "DT", 'B', 1, 9.0, 9.0, 9.0);
+    const std::string r3 = atom_line(1, "N", "GLY", 'A', 1, 0, 0, 0, kRest) + atom_line(2, "CA", "GLY", 'A', 1, 1.5, 0, 0, kRest) +
+                           atom_line(3, "C", "GLY", 'A', 1, 1.5, 1.5, 0, kRest) + atom_line(4, "CB", "GLY", 'A', 1, 0, 1.5, 1.5, kRest);
+    const std::string l1 = atom_line(1, "P", "DT", 'B', 1, 3.0, 4.0, 0, kRest) + atom_line(2, "OP1", "DT", 'B', 1, 9.0, 9.0, 9.0, kRest);
     put(scratch + "/r3.pdb", r3);
     put(scratch + "/l1.pdb", l1);
-    put(scratch + "/r2.pdb", r3.substr(0, r3.find("ATOM", 100)) + atom_line(4, "CB", "GLY", 'A', 1, 0, 1.5, 1.5));   // N, CA and the CB
-    put(scratch + "/l0.pdb", atom_line(2, "OP1", "DT", 'B', 1, 3.0, 4.0, 0));
-    put(scratch + "/lfar.pdb", atom_line(1, "P", "DT", 'B', 1, 3.0, 4.0, 40.0));
-    put(scratch + "/lvery_far.pdb", atom_line(1, "P", "DT", 'B', 1, 3.0, 4.0, 2100.0));
+    put(scratch + "/r2.pdb", r3.substr(0, r3.find("ATOM", 100)) + atom_line(4, "CB", "GLY", 'A', 1, 0, 1.5, 1.5, kRest));   // N, CA and the CB
+    put(scratch + "/l0.pdb", atom_line(2, "OP1", "DT", 'B', 1, 3.0, 4.0, 0, kRest));
+    put(scratch + "/lfar.pdb", atom_line(1, "P", "DT", 'B', 1, 3.0, 4.0, 40.0, kRest));
+    put(scratch + "/lvery_far.pdb", atom_line(1, "P", "DT", 'B', 1, 3.0, 4.0, 2100.0, kRest));
     ld_complex *t = ld_complex_create((scratch + "/r3.pdb").c_str(), (scratch + "/l1.pdb").c_str(), nullptr, 0, 0, nullptr, 0, 0);
     CHECK(t != nullptr);
     if (!t) return;

@@ -13,16 +13,8 @@
 #include <string>
 #include <vector>
 
-#include "lightdock_hip.h"
-
-static int failures = 0;
-#define CHECK(cond)                                                                                                 \
-    do {                                                                                                            \
-        if (!(cond)) {                                                                                              \
-            std::fprintf(stderr, "decompose_check: %s failed at line %d (%s)\n", #cond, __LINE__, ld_last_error()); \
-            failures++;                                                                                             \
-        }                                                                                                           \
-    } while (0)
+#define CHECK_PROGRAM "decompose_check"
+#include "check.hpp"
 
 static uint64_t seed = 88172645463325252ull;
 static double uniform() {   // [0, 1)

@@ -12,17 +12,9 @@
 #include <string>
 #include <vector>
 
+#define CHECK_PROGRAM "host_check"
+#include "check.hpp"
 #include "kernels/cluster.hpp"   // the analysis section sizes its inputs from the constants; every call goes through the C ABI
-#include "lightdock_hip.h"
-
-static int failures = 0;
-#define CHECK(cond)                                                              \
-    do {                                                                         \
-        if (!(cond)) {                                                           \
-            std::fprintf(stderr, "host_check: %s failed at line %d (%s)\n", #cond, __LINE__, ld_last_error()); \
-            failures++;                                                          \
-        }                                                                        \
-    } while (0)
 
 extern "C" size_t ld_stub_device_allocations(void);   // tests/asan/hip_stub.cpp
 extern "C" size_t ld_stub_device_allocations_of(size_t bytes);
@@ -57,19 +49,6 @@ static int cli(std::vector<std::string> args) {
 }
 
 // ---- the analysis half (complex.cpp, host/pdb_file.cpp; ld_complex_*) ---------------------------------------------------------
-static void put(const std::string &path, const std::string &text) {
-    FILE *f = std::fopen(path.c_str(), "wb");
-    std::fwrite(text.data(), 1, text.size(), f);
-    std::fclose(f);
-}
-
-// An ATOM record of exactly 54 columns.
-static std::string atom_line(int serial, const char *name, const char *res, int res_seq, double x, double y, double z) {
-    char buf[96];
-    std::snprintf(buf, sizeof buf, "ATOM  %5d %-4s %3s A%4d    %8.3f%8.3f%8.3f", serial, name, res, res_seq, x, y, z);
-    return buf;
-}
-
 static std::vector<double> identity_poses(size_t n, size_t stride) {
     std::vector<double> poses(n * stride, 0.0);
     for (size_t i = 0; i < n; i++) poses[i * stride + 3] = 1.0;
@@ -223,7 +202,7 @@ static void analysis(const std::string &rec1, const std::string &lig1, const std
     ld_complex_destroy(c);
 
     {   // files and modes a handle is refused for
-        const std::string bad = scratch + "/bad_complex.pdb", good = atom_line(1, " CA", "ALA", 1, 1.0, 2.0, 3.0);
+        const std::string bad = scratch + "/bad_complex.pdb", good = atom_line(1, " CA", "ALA", 'A', 1, 1.0, 2.0, 3.0);
         CHECK(good.size() == 54);
         CHECK(refused_create(scratch + "/missing.pdb", lig1, nullptr, 0, 0, "cannot open PDB file"));
         CHECK(refused_create(rec1, scratch + "/missing.pdb", nullptr, 0, 0, "cannot open PDB file"));
@@ -247,7 +226,7 @@ static void analysis(const std::string &rec1, const std::string &lig1, const std
     }
     {   // "\r\n" line ends, records of exactly 54 columns, records that are not atoms: one line out per record in, no '\r'
         std::string text = "REMARK a file from elsewhere\r\n";
-        for (int a = 0; a < 7; a++) text += atom_line(a + 1, a % 2 ? " CA" : " N", "GLY", 1 + a / 2, a, 2.0 * a, -a) + "\r\n";
+        for (int a = 0; a < 7; a++) text += atom_line(a + 1, a % 2 ? " CA" : " N", "GLY", 'A', 1 + a / 2, a, 2.0 * a, -a) + "\r\n";
         text += "TER\r\nEND\r\n";
         const std::string crlf = scratch + "/crlf.pdb", model = scratch + "/crlf_model.pdb";
         put(crlf, text);
@@ -266,8 +245,8 @@ static void analysis(const std::string &rec1, const std::string &lig1, const std
         const int n_rec = 1800, n_lig = 12;
         CHECK((size_t)(n_rec + n_lig + (n_lig + ld::kResGroup - 1) / ld::kResGroup) * 24 > ld::kMaxBoxLdsBytes);
         std::string rec, lig;
-        for (int a = 0; a < n_rec; a++) rec += atom_line(a + 1, " CA", "ALA", a + 1, a % 30, (a / 30) % 30, a / 900) + "\n";
-        for (int a = 0; a < n_lig; a++) lig += atom_line(a + 1, " P", "  A", a + 1, 40.0 + a, 0.0, 0.0) + "\n";
+        for (int a = 0; a < n_rec; a++) rec += atom_line(a + 1, " CA", "ALA", 'A', a + 1, a % 30, (a / 30) % 30, a / 900) + "\n";
+        for (int a = 0; a < n_lig; a++) lig += atom_line(a + 1, " P", "  A", 'A', a + 1, 40.0 + a, 0.0, 0.0) + "\n";
         put(scratch + "/wide_rec.pdb", rec);
         put(scratch + "/wide_lig.pdb", lig);
         ld_complex *w = ld_complex_create((scratch + "/wide_rec.pdb").c_str(), (scratch + "/wide_lig.pdb").c_str(), nullptr, 0, 0, nullptr, 0, 0);

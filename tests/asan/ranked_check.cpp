@@ -14,18 +14,10 @@
 #include <string>
 #include <vector>
 
+#define CHECK_PROGRAM "ranked_check"
+#include "check.hpp"
 #include "kernels/ranked.hpp"
-#include "lightdock_hip.h"
 #include "ranked_host.hpp"
-
-static int failures = 0;
-#define CHECK(cond)                                                                                              \
-    do {                                                                                                         \
-        if (!(cond)) {                                                                                           \
-            std::fprintf(stderr, "ranked_check: %s failed at line %d (%s)\n", #cond, __LINE__, ld_last_error()); \
-            failures++;                                                                                          \
-        }                                                                                                        \
-    } while (0)
 
 struct Side {
     std::vector<double> xyz;
@@ -49,14 +41,6 @@ static Side read_side(const std::string &path, bool keep_backbone = true) {
         s.text += line + "\n";
     }
     return s;
-}
-
-static void put(const std::string &path, const std::string &text) {
-    std::FILE *f = std::fopen(path.c_str(), "wb");
-    if (f) {
-        std::fwrite(text.data(), 1, text.size(), f);
-        std::fclose(f);
-    }
 }
 
 struct Result {

@@ -2,6 +2,7 @@
 reference's 1czy products, and a numpy restatement of LightDock's analysis rules (the checker the GPU tests use)."""
 import importlib.util
 import os
+import sys
 
 import numpy as np
 
@@ -9,16 +10,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CZY = os.path.join(ROOT, "tests", "golden", "1czy")
 
 
-def analyse_module():
-    spec = importlib.util.spec_from_file_location("ld_analyse", os.path.join(ROOT, "lightdock-rust_amd", "analyse.py"))
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "lightdock-rust_amd"))
+def tool_module(name):
+    """lightdock-rust_amd/<name>.py as the module lightdock_rust_amd.<name>.  Its directory is on sys.path while it loads:
+    a tool imports run_dir relative to the package where that is loaded, and by file name where it is not."""
+    tools = os.path.join(ROOT, "lightdock-rust_amd")
+    spec = importlib.util.spec_from_file_location("lightdock_rust_amd." + name, os.path.join(tools, name + ".py"))
+    sys.path.insert(0, tools)
     try:
         mod = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(mod)
     finally:
         sys.path.pop(0)
     return mod
+
+
+def analyse_module():
+    return tool_module("analyse")
 
 
 # ---- numpy restatement of LightDock's analysis rules ------------------------------------------------------------

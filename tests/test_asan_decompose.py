@@ -16,7 +16,7 @@ from test_asan import ENV, clean
 
 @pytest.mark.timeout(900)
 def test_decompose_host_side_under_asan_ubsan():
-    r = subprocess.run(["make", "-C", os.path.join(ROOT, "lightdock-rust_amd"), "asan-decompose"], capture_output=True, text=True)
+    r = subprocess.run(["make", "-C", os.path.join(ROOT, "lightdock-rust_amd"), "-j8", "asan-decompose"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     exe = os.path.join(ROOT, "lightdock-rust_amd", "build", "asan", "decompose_check")
     r = subprocess.run([exe], capture_output=True, text=True, env=ENV)

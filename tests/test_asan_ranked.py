@@ -15,7 +15,7 @@ from test_asan import ENV, clean
 
 @pytest.mark.timeout(900)
 def test_ranked_host_side_under_asan_ubsan(tmp_path):
-    r = subprocess.run(["make", "-C", os.path.join(ROOT, "lightdock-rust_amd"), "asan-ranked"], capture_output=True, text=True)
+    r = subprocess.run(["make", "-C", os.path.join(ROOT, "lightdock-rust_amd"), "-j8", "asan-ranked"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     exe = os.path.join(ROOT, "lightdock-rust_amd", "build", "asan", "ranked_check")
     r = subprocess.run([exe, GOLDEN, str(tmp_path)], capture_output=True, text=True, env=ENV)

@@ -5,14 +5,12 @@ characteristic quartic (Newton in `decimal` at 60 digits), a numpy SVD Kabsch fo
 answer is known, pinned on the counts of the fixtures, and assess.py's arithmetic and text."""
 import decimal
 import functools
-import importlib.util
 import os
-import sys
 
 import numpy as np
 import pytest
 
-from test_analysis_cpu import CZY, ROOT, analyse_module, restated_pdb
+from test_analysis_cpu import CZY, ROOT, analyse_module, restated_pdb, tool_module
 from test_contacts_cpu import GOLDEN, ContactsRestated, atom_contacts, thousandths
 
 FIT_NAMES = ("N", "CA", "C", "O", "P")
@@ -20,14 +18,7 @@ EPS = 2.0 ** -52
 
 
 def assess_module():
-    spec = importlib.util.spec_from_file_location("ld_assess", os.path.join(ROOT, "lightdock-rust_amd", "assess.py"))
-    sys.path.insert(0, os.path.join(ROOT, "lightdock-rust_amd"))
-    try:
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-    finally:
-        sys.path.pop(0)
-    return mod
+    return tool_module("assess")
 
 
 # ---- the restatement --------------------------------------------------------------------------------------------

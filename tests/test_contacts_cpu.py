@@ -1,27 +1,18 @@
 """Interface contacts (ld_complex_contacts, lightdock-rust_amd/filter.py) on the CPU: an int64 numpy
 restatement of the rule in include/lightdock_hip.h (the checker the GPU tests use), pinned on counts of the committed runs,
 and filter.py's file logic on hand-made arrays."""
-import importlib.util
 import os
-import sys
 
 import numpy as np
 import pytest
 
-from test_analysis_cpu import CZY, ROOT, Restated, analyse_module
+from test_analysis_cpu import CZY, ROOT, Restated, analyse_module, tool_module
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def filter_module():
-    spec = importlib.util.spec_from_file_location("ld_filter", os.path.join(ROOT, "lightdock-rust_amd", "filter.py"))
-    sys.path.insert(0, os.path.join(ROOT, "lightdock-rust_amd"))
-    try:
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-    finally:
-        sys.path.pop(0)
-    return mod
+    return tool_module("filter")
 
 
 # ---- the restatement --------------------------------------------------------------------------------------------
@@ -207,15 +198,20 @@ def test_restraint_columns_and_fractions():
     assert list(fl.keep_mask(lig, lig, beads, 0.4, max_beads=0)) == [False, True, True]
 
 
-def test_ordering_ties_and_the_text_of_rank_filtered_list(tmp_path):
-    fl = filter_module()
+def two_swarm_run(base):
+    """gso_5.out of swarms 0 and 3, three glowworms each, with ties in scoring inside a swarm and across the two."""
     header = "#Coordinates  RecID  LigID  Luciferin  Neighbor's number  Vision Range  Scoring\n"
     scores = {0: [1.5, 7.25, 1.5], 3: [7.25, -2.0, 1.5]}
     for s, sc in scores.items():
-        os.makedirs(tmp_path / ("swarm_%d" % s))
-        with open(tmp_path / ("swarm_%d" % s) / "gso_5.out", "w") as f:
+        os.makedirs(base / ("swarm_%d" % s))
+        with open(base / ("swarm_%d" % s) / "gso_5.out", "w") as f:
             f.write(header + "".join("(%d.0, %d.5, 0.0, 1.0, 0.0, 0.0, 0.0)    0    0   1.00000000  0 0.200 %.8f\n" % (s, g, v)
                                      for g, v in enumerate(sc)))
+
+
+def test_ordering_ties_and_the_text_of_rank_filtered_list(tmp_path):
+    fl = filter_module()
+    two_swarm_run(tmp_path)
     entries = fl.all_glowworms([3, 0], 5, base=str(tmp_path))
     assert [(e[0], e[1]) for e in entries] == [(0, 1), (3, 0), (0, 0), (0, 2), (3, 2), (3, 1)]
     assert list(entries[1][2]) == [3.0, 0.5, 0.0, 1.0, 0.0, 0.0, 0.0]

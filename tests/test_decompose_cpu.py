@@ -2,7 +2,6 @@
 model builder (ld_model_num_residues / ld_model_residue_id / ld_model_residue_of_atom), the constants the Python binding
 mirrors from the header, the layout of ld_energy_terms / ld_group_energies in the binding and in the Rust crate, and
 decompose.py's scaling to score units and its two list formats on made-up arrays.  No GPU."""
-import importlib.util
 import os
 import re
 
@@ -11,15 +10,13 @@ import pytest
 
 from conftest import GOLDEN, ROOT
 import test_rust_binding as rb
+from test_analysis_cpu import tool_module
 
 HEADER = os.path.join(ROOT, "include", "lightdock_hip.h")
 
 
 def tool():
-    spec = importlib.util.spec_from_file_location("lightdock_rust_amd.decompose", os.path.join(ROOT, "lightdock-rust_amd", "decompose.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+    return tool_module("decompose")
 
 
 def file_residue_ids(path):

@@ -1,24 +1,15 @@
 """Clustering of one ranked list across swarms (ld_complex_cluster_ranked, lightdock-rust_amd/cluster_run.py, DESIGN §5
 K3e) on the CPU: the script's candidate gathering and its two text formats on the committed 1czy run, and an int64 numpy
 restatement of the rule (the checker the GPU tests use), held against Restated.bsas of tests/test_analysis_cpu.py."""
-import importlib.util
 import os
-import sys
 
 import numpy as np
 
-from test_analysis_cpu import CZY, ROOT, Restated, analyse_module, czy_restated
+from test_analysis_cpu import CZY, ROOT, Restated, analyse_module, czy_restated, tool_module
 
 
 def cluster_run_module():
-    spec = importlib.util.spec_from_file_location("ld_cluster_run", os.path.join(ROOT, "lightdock-rust_amd", "cluster_run.py"))
-    sys.path.insert(0, os.path.join(ROOT, "lightdock-rust_amd"))
-    try:
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-    finally:
-        sys.path.pop(0)
-    return mod
+    return tool_module("cluster_run")
 
 
 # ---- int64 numpy restatement of the rule ------------------------------------------------------------------------------
