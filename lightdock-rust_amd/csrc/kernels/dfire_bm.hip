@@ -869,10 +869,36 @@ __device__ __forceinline__ unsigned long long bm_pair_item(uint32_t row, int la,
     return (unsigned long long)row | (unsigned long long)la << 32 | (unsigned long long)ra << 48;
 }
 
-__device__ __forceinline__ void bm_exact_pairs(BmArgs *T, unsigned long long *queue, uint32_t n_pairs, int lane) {
+// DEBUG: a drain's timers and counters (columns 14-26 of a wave's LIGHTDOCK_BM_DEBUG line; 100 MHz ticks).  The DEBUG instantiation WAITS at the end of
+// every phase of a trip (vmcnt(0)) so that the phase's round trip is the phase's time: what it measures is the chain, one link
+// at a time -- the production instantiation carries neither the timers nor the waits.
+struct BmDrainDebug {
+    unsigned long long t_items = 0;     // the release fence and the items' read-back
+    unsigned long long t_rows = 0;      // the rows' loads, issue to arrival
+    unsigned long long t_arith = 0;     // the pairs' arithmetic (and the flags' atomics issued)
+    unsigned long long t_table = 0;     // the table reads, issue to arrival (and the flags' atomics acknowledged)
+    unsigned long long t_atomics = 0;   // the sums' atomics issued; the closing fence
+    unsigned long long t_first = 0;     // of all five: every drain's FIRST trip (the code may have left the instruction cache)
+    unsigned long long drains = 0, trips = 0, pairs = 0, max_trips = 0;   // pairs: evaluated (real atoms); max_trips: the longest drain
+    unsigned long long t_recheck = 0, rounds = 0, block_items = 0;         // bm_recheck: its time, its rounds of 64 items, its items
+};
+
+template <bool DEBUG, bool ANM>
+__device__ __forceinline__ void bm_exact_pairs(BmArgs *T, unsigned long long *queue, uint32_t n_pairs, int lane, BmDrainDebug &dbg) {
 #ifdef LD_BM_DIAG_NO_EXACT   // (diagnostic builds: timing only, wrong sums -- the kernel without its exact path)
     return;
 #endif
+    auto now = [] { return DEBUG ? __builtin_amdgcn_s_memrealtime() : 0ull; };
+    auto arrived = [] { if (DEBUG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
+    unsigned long long dbg_t = now(), dbg_trips = 0;
+    const unsigned long long dbg_first0 = dbg_t;
+    auto lap = [&](unsigned long long &phase) {
+        if (DEBUG) {
+            const unsigned long long t = now();
+            phase += t - dbg_t;
+            dbg_t = t;
+        }
+    };
     // the wave reads back what it pushed itself: its stores are complete (through the write-through L1, in the XCD's L2), and
     // the loads below go past the L1.  (An agent-scope release here writes the whole L2 back, on every drain of every wave:
     // the launch took twice as long.)
@@ -893,6 +919,8 @@ __device__ __forceinline__ void bm_exact_pairs(BmArgs *T, unsigned long long *qu
             act[u] = k < n_pairs;
             item[u] = act[u] ? __hip_atomic_load(queue + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;   // (past the L1)
         }
+        arrived();
+        lap(dbg.t_items);
 #pragma unroll
         for (int u = 0; u < U; u++) {
             la[u] = (int)((item[u] >> 32) & 0xffffu);
@@ -915,6 +943,12 @@ __device__ __forceinline__ void bm_exact_pairs(BmArgs *T, unsigned long long *qu
             lq[u][0] = lrow[0]; lq[u][1] = lrow[1];
             rq[u][0] = rrow[0]; rq[u][1] = rrow[1];
         }
+        if (DEBUG) {
+#pragma unroll
+            for (int u = 0; u < U; u++) dbg.pairs += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(act[u]));
+        }
+        arrived();
+        lap(dbg.t_rows);
         double pr[U][7], lc[U][3], rc[U][3];
         uint32_t lterm[U], rterm[U];
         int32_t rslot[U], lslot[U];
@@ -944,7 +978,7 @@ __device__ __forceinline__ void bm_exact_pairs(BmArgs *T, unsigned long long *qu
             const Quat r = qmul(qmul(q, Quat{0.0, lc[u][0], lc[u][1], lc[u][2]}), qinverse(q));
             double px = r.x + pr[u][0], py = r.y + pr[u][1], pz = r.z + pr[u][2];
             double rx = rc[u][0], ry = rc[u][1], rz = rc[u][2];
-            if (T->amp != nullptr) {   // molecules that flex: src/dfire.rs:288-320, the operations of pose_ligand_atom and exact_pair (dfire_device.hpp)
+            if (ANM && T->amp != nullptr) {   // molecules that flex (the rigid kernels carry none of this): src/dfire.rs:288-320, the operations of pose_ligand_atom and exact_pair (dfire_device.hpp)
                 // (an atom's modes and a row's amplitudes in 16-byte pieces of contiguous memory: mode by mode out of the [mode][xyz][atom]
                 // arrays a pair was 60 scattered 8-byte loads, and the ANM form's waves spent a fifth of their time here)
                 const v2d *amps = reinterpret_cast<const v2d *>(T->amp_exact + row[u] * (2 * kBmMaxModes));
@@ -977,9 +1011,12 @@ __device__ __forceinline__ void bm_exact_pairs(BmArgs *T, unsigned long long *qu
             inside[u] = true;
             slot_at[u] = (lterm[u] + rterm[u] + tiled_bin_term(bin)) / 8u;
         }
+        lap(dbg.t_arith);
         double value[U];
 #pragma unroll
         for (int u = 0; u < U; u++) value[u] = ex0.table[slot_at[u]];   // (slot 0 for the pairs that read nothing: a valid address)
+        arrived();
+        lap(dbg.t_table);
 #pragma unroll
         for (int u = 0; u < U; u++) {
             if (!inside[u]) continue;
@@ -991,8 +1028,18 @@ __device__ __forceinline__ void bm_exact_pairs(BmArgs *T, unsigned long long *qu
             asm volatile("" :: "v"(fix));
 #endif
         }
+        if (DEBUG) {
+            lap(dbg.t_atomics);
+            if (dbg_trips++ == 0) dbg.t_first += dbg_t - dbg_first0;
+        }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // the list is read before it is written again
+    if (DEBUG) {
+        lap(dbg.t_atomics);
+        dbg.drains++;
+        dbg.trips += dbg_trips;
+        dbg.max_trips = dbg_trips > dbg.max_trips ? dbg_trips : dbg.max_trips;
+    }
 }
 
 __device__ __forceinline__ uint32_t bm_cell(float Rs, float Rz, float Ry, float Rx, float l2, float lz, float ly, float lx) {
@@ -1007,36 +1054,42 @@ __device__ __forceinline__ uint32_t bm_cell(float Rs, float Rz, float Ry, float 
 }
 
 // (entry, block) items with several flagged pairs -> the list of pairs.  An item = entry of the pass | ligand subtile of the tile
-// << 32 | receptor subtile of the tile << 35: like a pair item it needs nothing of the job it came from, so the wave collects
-// 64 of them before it spends a call and 64 pair loops on them.
-__device__ __forceinline__ unsigned long long bm_block_item(size_t entry, int a, int b) {
-    return (unsigned long long)entry | (unsigned long long)a << 32 | (unsigned long long)b << 35;
+// << 32 | receptor subtile of the tile << 35 | the entry's row of the pass << 38 (18 bits; read back from the entry list it was
+// one more dependent round trip in front of every round's loads): like a pair item it needs nothing of the job it came from,
+// so the wave collects 64 of them before it spends a call and 64 pair loops on them.
+static_assert(kBmMaxPassPoses <= (size_t)1 << 26, "a block item keeps the row of the pass in its upper 26 bits");
+__device__ __forceinline__ unsigned long long bm_block_item(size_t entry, int a, int b, uint32_t row) {
+    return (unsigned long long)entry | (unsigned long long)a << 32 | (unsigned long long)b << 35 | (unsigned long long)row << 38;
 }
-__device__ __forceinline__ uint32_t bm_recheck(BmArgs *T, const unsigned char *lut, const unsigned long long *blocks, uint32_t n_blocks,
-                                            unsigned long long *queue, uint32_t n_pairs, int lane) {
+template <bool DEBUG, bool ANM>
+__device__ __forceinline__ uint32_t bm_recheck(BmArgs *T, const unsigned char *lut, const unsigned long long *blocks, uint32_t &n_blocks,
+                                            unsigned long long *queue, uint32_t n_pairs, int lane, BmDrainDebug &dbg) {
+    const unsigned long long dbg_t = DEBUG ? __builtin_amdgcn_s_memrealtime() : 0ull;
+    if (DEBUG) dbg.block_items += n_blocks;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     constexpr float seed = (float)kBmCellZero + 0.5f;
     const int n_rt = T->m.rec_n_tiles;
-    for (uint32_t base = 0; base < n_blocks; base += 64) {
-    if (n_pairs > (uint32_t)kBmQueuePairs - 4096u - (uint32_t)(8 * kBmPartEntries)) {   // room for 64 x 64 more, and still for a job's pushes
-        bm_exact_pairs(T, queue, n_pairs, lane);
-        n_pairs = 0;
-    }
+    // As many items, 64 at a time off the list's END, as the list of pairs has room for -- 64 x 64 more, and still a job's
+    // pushes: for the rest (n_blocks: what is left) the wave comes back once the drain site has emptied the list of pairs (an
+    // empty list has room: every call takes items).  The order in which pairs are listed is free: integer sums, ORed flags.
+    while (n_blocks != 0u && n_pairs <= (uint32_t)kBmQueuePairs - 4096u - (uint32_t)(8 * kBmPartEntries)) {
+    const uint32_t base = (n_blocks - 1u) & ~63u;
+    if (DEBUG) dbg.rounds++;
     const bool act = base + (uint32_t)lane < n_blocks;
     const unsigned long long item = act ? __hip_atomic_load(blocks + base + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-    const size_t entry = (size_t)(item & 0xffffffffull);
+    const uint32_t entry = (uint32_t)item;
     const int a = (int)((item >> 32) & 7u), b = (int)((item >> 35) & 7u);
-    const size_t tp = entry / T->cap;
+    const uint32_t tp = entry / (uint32_t)T->cap;   // (entries of a pass are 32-bit numbers: 32-bit divisions)
     const int lt = (int)(tp / (unsigned)n_rt), RT = (int)(tp % (unsigned)n_rt), ls = lt * 8 + a;
     // the lane's pose and block, as the batch saw them
-    const uint32_t row = act ? T->ent_row[entry] : 0u;   // (an idle lane's entry 0 may never have been written)
+    const uint32_t row = (uint32_t)(item >> 38);   // (an idle lane: row 0)
     const float4 *ap = reinterpret_cast<const float4 *>(T->rt) + (size_t)row * 3;
     const float4 a0 = ap[0], a1 = ap[1], a2 = ap[2];
     const TiledBox box = T->m.rec_sub[(size_t)RT * 8 + b];
     const float cbx = 0.5f * (box.lox + box.hix), cby = 0.5f * (box.loy + box.hiy), cbz = 0.5f * (box.loz + box.hiz);
     const Affine A{a0.x, a0.y, a0.z, a0.w - cbx, a1.x, a1.y, a1.z, a1.w - cby, a2.x, a2.y, a2.z, a2.w - cbz};
     // ANM: the pose's amplitudes, and the deformation of an atom as the batch forms it (LD_BM_FLEX_ASM)
-    const bool anm = T->amp != nullptr;
+    const bool anm = ANM && T->amp != nullptr;   // (false at compile time in the rigid kernels)
     float amp_rec[kBmMaxModes], amp_lig[kBmMaxModes];
     bool wild = false;
 #pragma unroll
@@ -1072,9 +1125,18 @@ __device__ __forceinline__ uint32_t bm_recheck(BmArgs *T, const unsigned char *l
     }
     const float *rec = reinterpret_cast<const float *>(T->m.rec_pairs + (size_t)RT * 32 + b * 4);   // 4 records: x0 x1 y0 y1 z0 z1 . .
     // (in a block with tracked atoms the slots of bins 0 and 1 held markers too)
-    const uint32_t near_code = T->m.lig_sub_tracked[ls] != 0 || T->m.rec_sub_tracked[RT * 8 + b] != 0 ? bm_code_of_bin(1) : 0xffffffffu;
+    const int near_code = T->m.lig_sub_tracked[ls] != 0 || T->m.rec_sub_tracked[RT * 8 + b] != 0 ? (int)bm_code_of_bin(1) : -1;
+    // The lane's 64 cells first, its hits as ONE 64-bit mask (bit ^ 15 = receptor atom of the subtile * 8 + ligand atom); then a
+    // scan over the lanes' counts places every lane's run in the list, and the lanes write their pairs side by side.  (A ballot,
+    // a count and a masked store per CELL -- the list in cell order -- were thirty instructions and an LDS round trip for
+    // each of a round's 64 cells: three quarters of bm_recheck's instructions.  The list's order is free.)  A hit is the SIGN
+    // of an integer -- code = flagged: (code ^ flagged) - 1 < 0; code <= near_code: code - near_code - 1 < 0 (codes are bytes;
+    // near_code -1: never) -- so that sixteen cells' tests in flight hold no sixteen lane masks in scalar registers.
+    const uint32_t wild_sign = wild ? 0x80000000u : 0u;   // (a wild pose: every pair, the exact path decides)
+    unsigned long long hits = 0ull;
 #pragma unroll 1
     for (int q = 0; q < 4; q++) {
+        uint32_t hits_q = 0u;   // receptor atoms 2 q and 2 q + 1
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             float x = rec[q * 8 + h] - cbx, y = rec[q * 8 + 2 + h] - cby, z = rec[q * 8 + 4 + h] - cbz;
@@ -1090,16 +1152,37 @@ __device__ __forceinline__ uint32_t bm_recheck(BmArgs *T, const unsigned char *l
             for (int i = 0; i < 8; i++) {
                 const uint32_t cell = bm_cell(Rs, Rz, Ry, Rx, l2[i], lz[i], ly[i], lx[i]);
                 const uint32_t code = lut[cell];
-                const bool hit = act && (wild || code == kBmFlagged || (near_code != 0xffffffffu && code <= near_code));   // (a wild pose: every pair, the exact path decides)
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-                if (hit) {
-                    const uint32_t at = n_pairs + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    queue[at] = bm_pair_item(row, ls * 8 + i, RT * 64 + b * 8 + 2 * q + h);
-                }
-                n_pairs += (uint32_t)__popcll(m);
+                const uint32_t sign = ((code ^ kBmFlagged) - 1u) | (code - (uint32_t)near_code - 1u) | wild_sign;
+                hits_q = hits_q << 1 | sign >> 31;   // (the first cell ends in bit 15)
             }
         }
+        hits |= (unsigned long long)hits_q << (16 * q);
     }
+    if (!act) hits = 0ull;
+    const uint32_t mine = (uint32_t)__popcll(hits);
+    // inclusive scan over the lanes, in the vector unit alone (DPP: rows of 16 lanes shifted by 1, 2, 4, 8 -- a lane without a
+    // source adds 0 --, then lane 15 of rows 0 and 2 into rows 1 and 3, then lane 31 into rows 2 and 3)
+    uint32_t upto = mine;
+    upto += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)upto, 0x111, 0xf, 0xf, false);   // row_shr:1
+    upto += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)upto, 0x112, 0xf, 0xf, false);   // row_shr:2
+    upto += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)upto, 0x114, 0xf, 0xf, false);   // row_shr:4
+    upto += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)upto, 0x118, 0xf, 0xf, false);   // row_shr:8
+    upto += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)upto, 0x142, 0xa, 0xf, false);   // row_bcast:15, rows 1 and 3
+    upto += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)upto, 0x143, 0xc, 0xf, false);   // row_bcast:31, rows 2 and 3
+    uint32_t at = n_pairs + upto - mine;
+    n_pairs += (uint32_t)__builtin_amdgcn_readlane((int)upto, 63);
+    while (__builtin_amdgcn_ballot_w64(hits != 0ull) != 0ull) {   // (as many trips as the lane with the most hits has)
+        if (hits != 0ull) {
+            const int k = __builtin_ctzll(hits) ^ 15;
+            hits &= hits - 1ull;
+            queue[at++] = bm_pair_item(row, ls * 8 + (k & 7), RT * 64 + b * 8 + (k >> 3));
+        }
+    }
+    n_blocks = base;
+    }
+    if (DEBUG) {
+        dbg.block_items -= n_blocks;   // (what is left comes back)
+        dbg.t_recheck += __builtin_amdgcn_s_memrealtime() - dbg_t;
     }
     return n_pairs;
 }
@@ -1126,7 +1209,7 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
     }
     BmWaveSharedT<ANM> &WS = S.w[wave];
     __syncthreads();
-    const uint32_t n_jobs = T->job_count[3];
+    uint32_t n_jobs = T->job_count[3];   // (not 0: see above; set to 0 behind the last job)
     unsigned long long *queue = T->queue + ((size_t)blockIdx.x * kBmWaves + wave) * kBmQueueCap;   // the wave's flagged pairs
     unsigned long long *queue_blocks = queue + kBmQueuePairs;                                        // (entry, block) items with several
     uint32_t queued = 0, queued_blocks = 0;   // wave-uniform: flagged pairs listed; (entry, block) items listed
@@ -1136,6 +1219,7 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
     // block set-up: the rows' copy issued; the item list formed; the first loads' chain; a block's first batch's wait
     unsigned long long dbg_t_dma = 0, dbg_t_compact = 0, dbg_t_compact_read = 0, dbg_t_chain = 0, dbg_t_wait = 0, dbg_blocks = 0;
     auto now = [] { return DEBUG ? __builtin_amdgcn_s_memrealtime() : 0ull; };
+    BmDrainDebug dbg_drain;   // the drains' own timers and counters
 
     // A wave's FIRST job is its own number in the launch -- no draw: the 2048 waves of a launch all start at once, and their 2048
     // returning atomics on one counter (device scope: resolved behind the XCDs' L2s) queued for ~20 us before the first job's
@@ -1143,6 +1227,30 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
     const uint32_t n_waves = gridDim.x * (uint32_t)kBmWaves;
     bool first_job = true;
     for (;;) {
+        // The exact path, between two jobs only -- the kernel's ONE copy of bm_recheck and bm_exact_pairs (each at its own place
+        // behind a job, inside bm_recheck and behind the loop, the copies were two thirds of the kernel's instructions): no call
+        // inside the block and batch loops (the compiler keeps what lives across a call site in scratch for the whole job), and
+        // the lists have room for everything one job can push.  The pairs a few hundred at a time: often enough that the other
+        // waves' batches hide its memory latencies -- everything at the wave's end was a 230 us tail of the whole launch -- and
+        // seldom enough that the calls do not count.  (A kernel of its own for the lists, after this one, took 120 us for what
+        // costs the waves 45 us each here: measured.)  The (entry, block) items from 64 on, and behind the last job whatever is
+        // there: bm_recheck lists their pairs for as long as the list has room, the pairs are drained, and it goes on.
+        const bool last = n_jobs == 0u;   // no job left: one more pass, for whatever the lists still hold
+        if (queued >= (uint32_t)kBmDrainAt || queued_blocks >= 64u || (last && (queued | queued_blocks) != 0u)) {
+            const unsigned long long td = now();
+            // (the launch arguments through a pointer opaque to the compiler: what the exact path reads of them is loaded here,
+            // not ahead of the job loop and kept in scalar registers, or spilled, for the wave's whole life)
+            BmArgs *Tx = T;
+            asm volatile("" : "+s"(Tx));
+            auto blocks_due = [&] { return queued_blocks >= 64u || (last && queued_blocks != 0u); };
+            do {   // (again while bm_recheck has left items, whole rounds of 64, behind: the list of pairs ran out of room)
+                if (blocks_due()) queued = bm_recheck<DEBUG, ANM>(Tx, S.lut, queue_blocks, queued_blocks, queue, queued, lane, dbg_drain);
+                if (queued != 0u) bm_exact_pairs<DEBUG, ANM>(Tx, queue, queued, lane, dbg_drain);
+                queued = 0;
+            } while (blocks_due());
+            if (DEBUG) dbg_t_drain += now() - td;
+        }
+        if (last) break;
         const unsigned long long dbg_tj = now();
         uint32_t job = blockIdx.x * (uint32_t)kBmWaves + (uint32_t)wave;
         if (!first_job) {
@@ -1150,7 +1258,10 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
             job = (uint32_t)__builtin_amdgcn_readfirstlane((int)job) + n_waves;
         }
         first_job = false;
-        if (job >= n_jobs) break;
+        if (job >= n_jobs) {
+            n_jobs = 0u;
+            continue;
+        }
         job = T->job_order[job];   // longest first (dfire_bm_order)
         // (the job's record as dfire_bm_census wrote it: one load; its pieces one by one -- the (tile pair, part) pair, then the tile
         // pair's entry count -- were two more dependent round trips per job)
@@ -1591,7 +1702,7 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
                 if (__builtin_expect(m2 != 0ull, 0)) {
                     if (several) {   // (a lane has one flagged pair or several, never both: one slot serves both lists -- queue_blocks = queue + kBmQueuePairs)
                         pending_push = (uint32_t)kBmQueuePairs + queued_blocks + __builtin_amdgcn_mbcnt_hi((uint32_t)(m2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m2, 0u));
-                        pending_push_item = bm_block_item(row_base_entry + el, a, b);
+                        pending_push_item = bm_block_item(row_base_entry + el, a, b, cur_row);
                     }
                     queued_blocks += (uint32_t)__popcll(m2);
                 }
@@ -1662,47 +1773,28 @@ __global__ __launch_bounds__(kBmWaves * 64, kBmGroupsPerCu) void dfire_bm_pairs(
             }
             flush_pending();   // (the next block's first loads read what this block's last batch wrote)
         }
-        // The exact path, at the job's end only: no call inside the block and batch loops (the compiler keeps what lives across
-        // a call site in scratch for the whole job), and the lists have room for everything one job can push.
-        if (queued_blocks >= 64u) {
-            const unsigned long long td = now();
-            queued = bm_recheck(T, S.lut, queue_blocks, queued_blocks, queue, queued, lane);
-            queued_blocks = 0;
-            if (DEBUG) dbg_t_drain += now() - td;
-        }
-        // (a few hundred pairs at a time: often enough that the other waves' batches hide its memory latencies -- everything at
-        // the wave's end was a 230 us tail of the whole launch -- and seldom enough that the calls do not count.  A kernel of
-        // its own for the lists, after this one, took 120 us for what costs the waves 45 us each here: measured.)
-        if (queued >= (uint32_t)kBmDrainAt) {
-            const unsigned long long td = now();
-            bm_exact_pairs(T, queue, queued, lane);
-            queued = 0;
-            if (DEBUG) dbg_t_drain += now() - td;
-        }
-    }
-    {
-        const unsigned long long td = now();
-        if (queued_blocks) queued = bm_recheck(T, S.lut, queue_blocks, queued_blocks, queue, queued, lane);
-        if (queued) bm_exact_pairs(T, queue, queued, lane);
-        if (DEBUG) dbg_t_drain += now() - td;
+        // (the exact path for what this job listed: at the loop's head)
     }
 #ifndef LD_BM_DIAG_CULL_TIMES
     if (DEBUG && T->debug != nullptr && lane == 0) {
         unsigned long long *d = T->debug + ((size_t)blockIdx.x * kBmWaves + wave) * kBmDebugWords;
+        // (the record keeps its 14 words: words 2 to 13 -- counts and tick sums far below 2^32 -- hold in their UPPER halves the
+        // drains' twelve values, which the host writes out as columns 14 to 26 of a wave's line: bm_debug_columns, dfire_bm.hpp)
+        auto both = [](unsigned long long low, unsigned long long high) { return (low & 0xffffffffull) | high << 32; };
         d[0] = dbg_t0;
         d[1] = __builtin_amdgcn_s_memrealtime();
-        d[2] = dbg_jobs;
-        d[3] = dbg_batches;
-        d[4] = dbg_t_batch;
-        d[5] = dbg_t_drain;
-        d[6] = dbg_t_block;
-        d[7] = dbg_t_scan;
-        d[8] = dbg_t_dma;
-        d[9] = dbg_t_compact;
-        d[10] = dbg_t_chain;
-        d[11] = dbg_t_wait;
-        d[12] = dbg_blocks;
-        d[13] = dbg_t_compact_read;
+        d[2] = both(dbg_jobs, dbg_drain.t_items);
+        d[3] = both(dbg_batches, dbg_drain.t_rows);
+        d[4] = both(dbg_t_batch, dbg_drain.t_arith);
+        d[5] = both(dbg_t_drain, dbg_drain.t_table);
+        d[6] = both(dbg_t_block, dbg_drain.t_atomics);
+        d[7] = both(dbg_t_scan, dbg_drain.t_first);
+        d[8] = both(dbg_t_dma, dbg_drain.drains);
+        d[9] = both(dbg_t_compact, dbg_drain.trips);
+        d[10] = both(dbg_t_chain, dbg_drain.pairs);
+        d[11] = both(dbg_t_wait, dbg_drain.t_recheck);
+        d[12] = both(dbg_blocks, dbg_drain.block_items);
+        d[13] = both(dbg_t_compact_read, dbg_drain.rounds << 8 | (dbg_drain.max_trips & 0xffull));
     }
 #endif
 }

@@ -77,6 +77,21 @@ constexpr int kBmMarkerShift = 51;           // a lane keeps two sums of 32 pair
 constexpr int kBmJobRows = 8;                // a job = (tile pair, part of its entries, ligand subtile a): the blocks (a, 0..7); one partial sum per (entry, a)
 constexpr int kBmPartEntries = 1792;         // entries of a tile pair in one job: what a wave's share of the LDS holds at 3 bytes an entry (the block bits, the item list)
 constexpr int kBmDebugWords = 14;          // words of a wave's record in the LIGHTDOCK_BM_DEBUG buffer (dfire_bm_pairs' phase timers)
+constexpr int kBmDebugColumns = 27;        // columns of a wave's line in the LIGHTDOCK_BM_DEBUG file: bm_debug_columns
+// A wave's record -> its line.  Words 0 and 1 are times of day (64 bits); words 2 to 13 hold a phase's count or tick sum in
+// their lower half (columns 2 to 13) and one of the exact-path drains' values in their upper half: columns 14 to 19 the trips'
+// phases and the first trips (ticks), 20 drains, 21 trips, 22 pairs evaluated, 23 the longest drain's trips, 24 bm_recheck's
+// ticks, 25 its rounds, 26 its items.
+inline void bm_debug_columns(const unsigned long long *record, unsigned long long *columns) {
+    columns[0] = record[0];
+    columns[1] = record[1];
+    for (int k = 2; k < kBmDebugWords; k++) columns[k] = record[k] & 0xffffffffull;
+    for (int k = 0; k < 9; k++) columns[14 + k] = record[2 + k] >> 32;   // t_items .. pairs
+    columns[23] = (record[13] >> 32) & 0xffull;
+    columns[24] = record[11] >> 32;
+    columns[25] = record[13] >> 40;
+    columns[26] = record[12] >> 32;
+}
 constexpr int kBmEntryMask = 0x7ff;          // an entry's number in its part
 constexpr int kBmPassQuantum = 1024;         // poses per pass: a multiple of this
 constexpr int kBmOpsFloats = 36;             // BmModel::rec_ops: Rs[4][2], Rz[4][2], Ry[4][2], Rx[4][2], cx, cy, cz, 0

@@ -1397,8 +1397,11 @@ void BlockMajorPath::run(size_t n, const double *d_poses, size_t stride, const u
         std::vector<unsigned long long> h(s.waves * kBmDebugWords);
         hip_check(hipMemcpy(h.data(), t.debug, h.size() * 8, hipMemcpyDeviceToHost), "D2H debug");
         if (FILE *f = std::fopen(dbg, "w")) {
-            for (size_t i = 0; i < h.size(); i += kBmDebugWords)
-                for (int k = 0; k < kBmDebugWords; k++) std::fprintf(f, k + 1 < kBmDebugWords ? "%llu " : "%llu\n", h[i + (size_t)k]);
+            for (size_t i = 0; i < h.size(); i += kBmDebugWords) {
+                unsigned long long line[kBmDebugColumns];
+                bm_debug_columns(h.data() + i, line);
+                for (int k = 0; k < kBmDebugColumns; k++) std::fprintf(f, k + 1 < kBmDebugColumns ? "%llu " : "%llu\n", line[k]);
+            }
             std::fclose(f);
         }
     }

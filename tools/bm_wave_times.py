@@ -21,6 +21,16 @@ if d.shape[1] >= 14:   # the block set-up split (words 8-13): the rows' copy iss
     us = lambda k: (d[:, k] / 100).mean()
     print("block set-ups per wave mean %.1f (%.2f us each): rows' copy issued %.1f us, item list %.1f us (its reads' round trip %.1f us), first loads' chain %.1f us per wave; first batches' wait for rows and loads %.1f us per wave (%.2f us per block)" % (
         d[:, 12].mean(), d[:, 6].sum() / 100 / blocks, us(8), us(9), us(13), us(10), us(11), d[:, 11].sum() / 100 / blocks))
+if d.shape[1] >= 24:   # the drains' split (columns 14-23; the DEBUG kernel waits at the end of every phase, so a phase's time is its round trip)
+    us = lambda k: (d[:, k] / 100).mean()
+    drains, trips = np.maximum(d[:, 20].sum(), 1), np.maximum(d[:, 21].sum(), 1)
+    print("drains per wave mean %.1f, trips %.1f (longest drain %d trips), pairs evaluated %.0f per wave (%d in all); %.2f us per trip: fence + items %.1f us, the rows' wait %.1f us, arithmetic %.1f us, the table wait %.1f us, atomics + closing fence %.1f us per wave; rechecks and the rest of the drain timer %.1f us; a drain's first trip %.2f us, a later trip %.2f us" % (
+        d[:, 20].mean(), d[:, 21].mean(), d[:, 23].max(), d[:, 22].mean(), d[:, 22].sum(), d[:, 14:19].sum() / 100 / trips, us(14), us(15), us(16), us(17), us(18),
+        (d[:, 5] / 100).mean() - (d[:, 14:19].sum(1) / 100).mean(), d[:, 19].sum() / 100 / drains,
+        (d[:, 14:19].sum() - d[:, 19].sum()) / 100 / np.maximum(trips - drains, 1)))
+if d.shape[1] >= 27:   # bm_recheck (columns 24-26): the blocks with several flagged pairs, their pairs found again
+    print("bm_recheck: %.1f us per wave in %.1f rounds of 64 (entry, block) items at most (%.2f us a round), %.0f items per wave" % (
+        (d[:, 24] / 100).mean(), d[:, 25].mean(), d[:, 24].sum() / 100 / np.maximum(d[:, 25].sum(), 1), d[:, 26].mean()))
 late = end > np.percentile(end, 90)
 print("slowest 10%% of waves: batches %.0f, batch time %.0f us, drain time %.0f us, jobs %.1f" % (batches[late].mean(), (d[late, 4] / 100).mean(), (d[late, 5] / 100).mean(), jobs[late].mean()))
 per_cu = batches.reshape(-1, 8).sum(1)
