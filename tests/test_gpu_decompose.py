@@ -15,29 +15,14 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, case_kwargs, case_positions
+from dna_reference import IFACE2, N_POSES, posed, synthetic, synthetic_poses
 from test_gpu_parity import REL_TOL, bm_err, rel_err
 
 pytestmark = pytest.mark.gpu
 
-IFACE2 = 3.9 * 3.9    # INTERFACE_CUTOFF2, src/constants.rs:15
-
-
 # ---------------------------------------------------------------------------------------------------------------------
 # the restatement
 # ---------------------------------------------------------------------------------------------------------------------
-def posed(orc, mol, row, ligand, ext):
-    """One molecule at one pose: q v q^-1 + t for the ligand, then ANM in ascending mode order (src/dfire.rs:282-320)."""
-    xyz = np.array(mol["coordinates"], dtype=np.float64).reshape(-1, 3)
-    if ligand:
-        xyz = np.stack([orc.q_rotate(row[3:7], v) for v in xyz]) + row[:3]
-    modes = mol.get("modes")
-    if modes is not None:
-        xyz = xyz.copy()
-        for k in range(modes.shape[0]):
-            xyz += modes[k] * ext[k]
-    return xyz
-
-
 def dfire_bin(d2):
     """DIST_TO_BINS[(sqrt(d2) * 2 - 1) as usize] - 1 (src/dfire.rs:49-53,336-337) for d2 <= 225: half-angstrom bins up to
     8 A, then one-angstrom bins; `as usize` saturates a negative d to 0; r = 15.0 gives bin 20, past the row."""
@@ -130,33 +115,8 @@ def check_terms_exact(t, want, where):
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. synthetic molecules: the lane, workgroup and LDS-chunk edges; the cutoffs hit exactly; NaN
 # ---------------------------------------------------------------------------------------------------------------------
-N_POSES = 37
 PARTNER_CHUNK = 512     # kDecomposeChunk of csrc/kernels/decompose.hpp (tests/test_decompose_cpu.py holds the two together)
 SHAPES = [(1, 1), (63, 65), (64, 64), (257, 255), (300, PARTNER_CHUNK + 1)]
-
-
-def synthetic(n_rec, n_lig, seed):
-    rng = np.random.default_rng(seed)
-
-    def mol(n):
-        xyz = rng.random((n, 3)) * 30.0
-        xyz[0] = 0.0        # atom 0 of both molecules at the origin: a pose's translation IS their distance vector
-        return {"coordinates": xyz, "dfire_types": rng.integers(0, 168, n).astype(np.uint32), "ele_charges": rng.random(n) - 0.5,
-                "vdw_charges": 0.01 + 0.2 * rng.random(n), "vdw_radii": 1.0 + rng.random(n)}
-    return mol(n_rec), mol(n_lig)
-
-
-def synthetic_poses(seed):
-    """37 rows of pose_len + 3 columns.  0: d2 = 225 exactly between the two atoms 0 (identity rotation); 1: 500 A away;
-    2: the two atoms 0 coincide (DNA: NaN); 3, 4, 5: d2 = 900, 100 and 3.9 * 3.9 exactly; the rest random, quaternions
-    not normalised."""
-    rng = np.random.default_rng(seed)
-    poses = np.full((N_POSES, 10), np.nan)
-    poses[:, :3] = rng.random((N_POSES, 3)) * 20.0 - 10.0
-    poses[:, 3:7] = rng.random((N_POSES, 4)) - 0.5
-    for p, t in enumerate([(9.0, 12.0, 0.0), (500.0, 0.0, 0.0), (0.0, 0.0, 0.0), (18.0, 24.0, 0.0), (6.0, 8.0, 0.0), (3.9, 0.0, 0.0)]):
-        poses[p, :7] = t + (1.0, 0.0, 0.0, 0.0)
-    return poses
 
 
 @pytest.fixture(scope="module")
