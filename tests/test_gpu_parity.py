@@ -782,7 +782,9 @@ def _k2_env(monkeypatch, shape):
 
 def test_gso_odd_sizes(pkg, scorers, orc, monkeypatch):
     """1 glowworm (never has a neighbour), 3 glowworms, swarms around the 256 glowworms up to which K2 keeps a bit per candidate
-    for the roulette, more glowworms than threads in a workgroup (1030 > 1024), a swarm whose LDS snapshot exceeds 64 KiB (2048: exactly 64 KiB for the thread-per-glowworm
+    for the roulette, a swarm of more glowworms than a workgroup has threads (1030 > 1024: one swarm is split over 17 workgroups with
+    shares of 61, so no thread here takes a second glowworm -- shares larger than a workgroup are tests/test_gpu_gso_shapes.py's), a
+    swarm whose LDS snapshot exceeds 64 KiB (2048: exactly 64 KiB for the thread-per-glowworm
     kernel, 96 KiB for the phased one; 2100): same as the oracle, in BOTH shapes of K2 (src/swarm.rs:72-126; the launch picks
     one by size, gso_step.hip, LIGHTDOCK_GSO_K2 forces one), and the two shapes' states bit for bit the same."""
     hip, cpu = scorers("1ppe")
