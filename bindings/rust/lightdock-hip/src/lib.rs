@@ -90,6 +90,13 @@ extern "C" {
     fn ld_gso_run(g: *mut c_void, steps: u32) -> c_int;
     fn ld_gso_save(g: *mut c_void, swarm: usize, step: u32, dir: *const c_char) -> c_int;
     fn ld_gso_save_many(g: *mut c_void, n: usize, swarms: *const usize, dirs: *const *const c_char, step: u32) -> c_int;
+    // Normal modes (include/lightdock_hip.h, "Normal modes"): what src/bin/lightdock-rust.rs:216-254 reads as rec_nm.npy / lig_nm.npy
+    pub fn ld_anm_nodes(pdb_path: *const c_char, node_atom_out: *mut u32, n_residues_out: *mut usize) -> c_int;
+    pub fn ld_anm_modes_xyz(node_xyz: *const f64, n_nodes: usize, n_modes: usize, cutoff: f64, node_modes_out: *mut f64,
+                            eigenvalues_out: *mut f64) -> c_int;
+    pub fn ld_anm_modes(pdb_path: *const c_char, n_modes: usize, cutoff: f64, rmsd: f64, modes_out: *mut f64,
+                        eigenvalues_out: *mut f64) -> c_int;
+    pub fn ld_anm_last_kernel_ms(ms_out: *mut f64) -> c_int;
 }
 
 fn last_error() -> String {

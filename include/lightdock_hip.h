@@ -36,7 +36,8 @@ typedef enum ld_status {
     LD_ERR_UNSUPPORTED = -2, /* residue/atom/method the scoring function does not know */
     LD_ERR_IO = -3,          /* file missing / unreadable / malformed */
     LD_ERR_DEVICE = -4,      /* HIP error or no gfx950 device */
-    LD_ERR_NOMEM = -5
+    LD_ERR_NOMEM = -5,
+    LD_ERR_INTERNAL = -6     /* an iteration of the library's own did not end within its bound */
 } ld_status;
 
 /* src/scoring.rs:5-9 `enum Method` */
@@ -475,6 +476,48 @@ int ld_complex_native_pairs(const ld_complex *c, uint32_t *pairs /* n_native x 2
 /* Any output may be NULL; n == 0 is LD_OK.  ld_complex_last_kernel_ms then reports this call's kernels. */
 int ld_complex_assess(ld_complex *c, size_t n, const double *poses, size_t stride,
                       uint32_t *kept /* n */, double *lrmsd /* n */, double *irmsd /* n */);
+
+/* ------------------------------------------------------------------------------------
+ * Normal modes: the rec_nm.npy / lig_nm.npy a run with `use_anm: true` reads
+ * (src/bin/lightdock-rust.rs:216-254 is the consumer; the reference tree cannot produce them,
+ * lightdock3_setup.py asks ProDy).  The rule is ProDy's anisotropic network model on one node per
+ * residue, extended to all atoms as LightDock does; it reproduces the mode files under
+ * tests/golden up to each mode's sign.
+ *   Atoms and residues: the ATOM / HETATM records in file order; residues as under "Interface
+ *     contacts" above.
+ *   Node of a residue: its first atom named CA, else its first atom named C4'.  A residue with
+ *     neither is refused (LD_ERR_INVALID, the residue id in ld_last_error()).
+ *   Hessian, 3m x 3m for m nodes, spring constant 1: for i != j with 0 < d^2 <= cutoff^2 the
+ *     off-diagonal 3 x 3 block is -d d^T / d^2, d = x_j - x_i; a diagonal block is minus the sum of
+ *     its row's off-diagonal blocks, j ascending.
+ *   Modes: eigenpairs ascending; the six smallest are rigid-body motions; the modes are the 7th to
+ *     the (6 + n_modes)-th.  Sign: the component of largest magnitude of the node eigenvector (the
+ *     lowest index on a tie) is positive (ProDy's sign is LAPACK's accident).
+ *   Extension: every atom takes its residue's node vector; each mode is then divided by its
+ *     Euclidean norm over all atoms x 3.
+ *   Amplitude (this library's own option, the expectation form of ProDy's sampleModes scale; only
+ *     the DIRECTION of a mode is claimed to equal a setup made with anm_rec_rmsd / anm_seed): with
+ *     rmsd > 0 mode k is further multiplied by rmsd sqrt(atoms) / sqrt(sum_j 1 / lambda_j) /
+ *     sqrt(lambda_k), j over the n_modes modes.
+ *   Solver: parallel one-sided Jacobi on the device, f64, to |a_p . a_q| <= 2^-50 |a_p| |a_q| for
+ *     every column pair; all sums in a fixed order, so the same input gives the same bits.
+ * LD_ERR_INVALID, nothing written: a null argument, n_modes == 0 or > 128, more than 4096 nodes,
+ * 3m < 6 + n_modes, a cutoff that is not positive and finite, a negative or non-finite rmsd, a
+ * non-finite coordinate, a seventh eigenvalue below 1e-6 (a floppy, collinear or disconnected
+ * network).  LD_ERR_INTERNAL, nothing written: no convergence within 40 sweeps.  A file that
+ * cannot be read is LD_ERR_IO.  Device memory: two matrices of (3m)^2 doubles for the call.
+ * ---------------------------------------------------------------------------------- */
+/* Host only.  node_atom_out: n_residues record indices (file order), or NULL to ask for the count alone. */
+int ld_anm_nodes(const char *pdb_path, uint32_t *node_atom_out /* n_residues or NULL */, size_t *n_residues_out);
+/* The core on raw coordinates; the modes of the nodes themselves, each of norm 1. */
+int ld_anm_modes_xyz(const double *node_xyz /* n_nodes x 3 */, size_t n_nodes, size_t n_modes, double cutoff /* 15.0 */,
+                     double *node_modes_out /* n_modes x n_nodes x 3 */, double *eigenvalues_out /* n_modes or NULL */);
+/* From a PDB file to what rec_nm.npy holds.  rmsd == 0: unit modes. */
+int ld_anm_modes(const char *pdb_path, size_t n_modes, double cutoff /* 15.0 */, double rmsd /* 0.0 */,
+                 double *modes_out /* n_modes x atoms x 3, file order */, double *eigenvalues_out /* n_modes or NULL */);
+/* The device work of this thread's last ld_anm_modes / ld_anm_modes_xyz that reached the device (HIP events, from the
+ * first launch to the last, the host's reads of the sweeps' convergence word included). */
+int ld_anm_last_kernel_ms(double *ms_out);
 
 /* ------------------------------------------------------------------------------------
  * The reference command line (src/bin/lightdock-rust.rs:77-333) as a function:

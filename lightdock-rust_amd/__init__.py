@@ -177,6 +177,10 @@ def load_library():
     lib.ld_complex_reference_counts.argtypes = [vp, vp]
     lib.ld_complex_native_pairs.argtypes = [vp, vp]
     lib.ld_complex_assess.argtypes = [vp, sz, vp, sz, vp, vp, vp]
+    lib.ld_anm_nodes.argtypes = [C.c_char_p, vp, C.POINTER(sz)]
+    lib.ld_anm_modes_xyz.argtypes = [vp, sz, sz, C.c_double, vp, vp]
+    lib.ld_anm_modes.argtypes = [C.c_char_p, sz, C.c_double, C.c_double, vp, vp]
+    lib.ld_anm_last_kernel_ms.argtypes = [dp]
     _lib = lib
     return lib
 
@@ -751,6 +755,51 @@ class Complex:
         n_native = self.reference_counts()["native_pairs"]
         _check(self.lib.ld_complex_assess(self._h, n, _ptr(poses), poses.shape[1], _ptr(kept), _ptr(lrmsd), _ptr(irmsd)))
         return {"kept": kept, "fnat": kept / float(n_native), "lrmsd": lrmsd, "irmsd": irmsd}
+
+
+ANM_CUTOFF = 15.0
+
+
+def anm_nodes(pdb_path):
+    """The node atom of every residue of a PDB file (ld_anm_nodes; lightdock_hip.h, "Normal modes"): indices into the
+    file's ATOM / HETATM records, one a residue, in file order.  Host only."""
+    lib = load_library()
+    n = C.c_size_t()
+    _check(lib.ld_anm_nodes(os.fsencode(pdb_path), None, C.byref(n)))
+    out = np.zeros(n.value, dtype=np.uint32)
+    _check(lib.ld_anm_nodes(os.fsencode(pdb_path), _ptr(out), C.byref(n)))
+    return out
+
+
+def anm_modes_xyz(node_xyz, n_modes, cutoff=ANM_CUTOFF):
+    """(eigenvalues (k,), unit modes (k, nodes, 3)) of an anisotropic network on raw node coordinates (ld_anm_modes_xyz)."""
+    xyz = _f64(node_xyz).reshape(-1, 3)
+    k = max(0, int(n_modes))
+    modes, eig = np.zeros((k, xyz.shape[0], 3)), np.zeros(k)
+    _check(load_library().ld_anm_modes_xyz(_ptr(xyz), xyz.shape[0], k, C.c_double(cutoff), _ptr(modes), _ptr(eig)))
+    return eig, modes
+
+
+def anm_modes(pdb_path, n_modes, cutoff=ANM_CUTOFF, rmsd=0.0):
+    """(eigenvalues (k,), modes (k, atoms, 3) in file order) of a PDB file: what lightdock_rec.nm.npy holds (ld_anm_modes).
+    rmsd = 0: every mode of norm 1; rmsd > 0: the library's amplitude rule."""
+    lib = load_library()
+    try:
+        with open(pdb_path, errors="replace") as f:
+            atoms = sum(1 for line in f if line.startswith("ATOM  ") or line.startswith("HETATM"))
+    except OSError:   # the library says why (LD_ERR_IO) before it writes anything
+        atoms = 0
+    k = max(0, int(n_modes))
+    modes, eig = np.zeros((k, atoms, 3)), np.zeros(k)
+    _check(lib.ld_anm_modes(os.fsencode(pdb_path), k, C.c_double(cutoff), C.c_double(rmsd), _ptr(modes), _ptr(eig)))
+    return eig, modes
+
+
+def anm_last_kernel_ms():
+    """The device work of this thread's last anm_modes / anm_modes_xyz, in ms (HIP events)."""
+    ms = C.c_double()
+    _check(load_library().ld_anm_last_kernel_ms(C.byref(ms)))
+    return ms.value
 
 
 def cli_main(argv):

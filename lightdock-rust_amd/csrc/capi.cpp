@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "anm.hpp"
 #include "complex.hpp"
 #include "gso.hpp"
 #include "host/cli.hpp"
@@ -534,6 +535,43 @@ int ld_complex_write_pdb(ld_complex *c, const double *pose, const char *path) {
     return guarded([&] {
         if (!c) throw ld::Error(LD_ERR_INVALID, "null argument");
         c->impl.write_pdb(pose, path);
+    });
+}
+
+int ld_anm_nodes(const char *pdb_path, uint32_t *node_atom_out, size_t *n_residues_out) {
+    return guarded([&] {
+        if (!pdb_path || !n_residues_out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        const std::vector<uint32_t> node = ld::anm_node_atoms(ld::read_pdb_file_order(pdb_path));
+        *n_residues_out = node.size();
+        if (node_atom_out) std::memcpy(node_atom_out, node.data(), node.size() * sizeof(uint32_t));
+    });
+}
+int ld_anm_modes_xyz(const double *node_xyz, size_t n_nodes, size_t n_modes, double cutoff, double *node_modes_out,
+                     double *eigenvalues_out) {
+    return guarded([&] {
+        if (!node_xyz || !node_modes_out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        const ld::AnmResult r = ld::anm_solve(node_xyz, n_nodes, n_modes, cutoff, nullptr, n_nodes, 0.0);
+        std::memcpy(node_modes_out, r.modes.data(), r.modes.size() * sizeof(double));
+        if (eigenvalues_out) std::memcpy(eigenvalues_out, r.eigenvalues.data(), r.eigenvalues.size() * sizeof(double));
+    });
+}
+int ld_anm_modes(const char *pdb_path, size_t n_modes, double cutoff, double rmsd, double *modes_out, double *eigenvalues_out) {
+    return guarded([&] {
+        if (!pdb_path || !modes_out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        const ld::PdbFile pdb = ld::read_pdb_file_order(pdb_path);
+        const std::vector<uint32_t> node = ld::anm_node_atoms(pdb);
+        std::vector<double> xyz(3 * node.size());
+        for (size_t r = 0; r < node.size(); r++)
+            for (int c = 0; c < 3; c++) xyz[3 * r + c] = pdb.xyz[3 * (size_t)node[r] + c];
+        const ld::AnmResult r = ld::anm_solve(xyz.data(), node.size(), n_modes, cutoff, pdb.res_of_atom.data(), pdb.res_of_atom.size(), rmsd);
+        std::memcpy(modes_out, r.modes.data(), r.modes.size() * sizeof(double));
+        if (eigenvalues_out) std::memcpy(eigenvalues_out, r.eigenvalues.data(), r.eigenvalues.size() * sizeof(double));
+    });
+}
+int ld_anm_last_kernel_ms(double *ms_out) {
+    return guarded([&] {
+        if (!ms_out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        *ms_out = ld::anm_last_kernel_ms();
     });
 }
 
