@@ -64,6 +64,15 @@ pub struct ld_group_energies {
 
 pub const LD_GROUP_NONE: u32 = 0xffff_ffff;
 
+/// `ld_complex`: the opaque handle of the analysis half of a run (include/lightdock_hip.h, "Analysis of a finished run").
+#[allow(non_camel_case_types)]
+#[repr(C)]
+pub struct ld_complex {
+    _private: [u8; 0],
+}
+
+pub const LD_SASA_POINTS: usize = 128;
+
 // The decomposition and residue entry points (ld_scorer_decompose*, ld_model_*) are declared only: no wrapper uses them yet.
 #[allow(dead_code)]
 extern "C" {
@@ -97,6 +106,16 @@ extern "C" {
     pub fn ld_anm_modes(pdb_path: *const c_char, n_modes: usize, cutoff: f64, rmsd: f64, modes_out: *mut f64,
                         eigenvalues_out: *mut f64) -> c_int;
     pub fn ld_anm_last_kernel_ms(ms_out: *mut f64) -> c_int;
+    // Solvent-accessible surface (include/lightdock_hip.h, "Solvent-accessible surface"): Shrake-Rupley on integer thousandths
+    pub fn ld_complex_create(receptor_pdb: *const c_char, ligand_pdb: *const c_char, rec_nmodes: *const f64, rec_nmodes_len: usize,
+                             rec_num_anm: usize, lig_nmodes: *const f64, lig_nmodes_len: usize, lig_num_anm: usize) -> *mut ld_complex;
+    pub fn ld_complex_destroy(c: *mut ld_complex);
+    pub fn ld_complex_pose_len(c: *const ld_complex) -> usize;
+    pub fn ld_complex_num_atoms(c: *const ld_complex, side: c_int) -> usize;
+    pub fn ld_sasa_directions(out: *mut i32) -> c_int;
+    pub fn ld_complex_sasa_radii(c: *const ld_complex, side: c_int, radii_out: *mut u32) -> c_int;
+    pub fn ld_complex_sasa(c: *mut ld_complex, n: usize, poses: *const f64, stride: usize, probe: f64, sums: *mut u64,
+                           free_counts: *mut u8, bound_counts: *mut u8) -> c_int;
 }
 
 fn last_error() -> String {

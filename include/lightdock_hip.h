@@ -477,6 +477,44 @@ int ld_complex_native_pairs(const ld_complex *c, uint32_t *pairs /* n_native x 2
 int ld_complex_assess(ld_complex *c, size_t n, const double *poses, size_t stride,
                       uint32_t *kept /* n */, double *lrmsd /* n */, double *irmsd /* n */);
 
+/* Solvent-accessible surface: for every pose, the surface of each molecule alone and in the complex, and so the area
+ * the interface buries, per pose and per atom.  No tool of the reference tree computes a surface; the rule is this
+ * library's own: Shrake-Rupley on integers, in thousandths of an angstrom as "%8.3f" prints a coordinate.
+ *   Atoms that take part: every ATOM / HETATM record of the two files, in file order, except element H or D and
+ *     residues named MMB (membrane beads).  An excluded atom neither has a surface nor covers anyone's.  The element is
+ *     columns 77-78, trimmed and upper-cased; if the record is too short for them or the field is blank, the first
+ *     alphabetic character of columns 13-16.
+ *   Radii in thousandths: C 1700, N 1550, O 1520, F 1470, P 1800, S 1800, CL 1750, SE 1900, BR 1850, I 1980, any other
+ *     element 1800; an atom that takes no part reports 0.
+ *   Probe: 0 <= probe <= 2.0 A, p = llrint(1000 * probe); the expanded radius of atom a is E_a = R_a + p.
+ *   Directions: LD_SASA_POINTS golden-spiral directions as a fixed integer table (ld_sasa_directions),
+ *     U[k] = rint(2^20 * (r cos(k g), r sin(k g), z)), z = 1 - (2k + 1) / 128, r = sqrt(1 - z^2), g = pi (3 - sqrt 5).
+ *     No component is within 1e-3 of a rounding tie.
+ *   Points: point k of atom a lies at c_a + ((E_a * U[k] + 2^19) >> 20), the product in 64 bits, the shift arithmetic,
+ *     per component.  c_a is the posed atom (posing as above: the ligand's modes in the ligand frame) as the integer
+ *     thousandths "%8.3f" prints, so the surface of a pose is that of the file ld_complex_write_pdb writes for it.
+ *   Burial: point q of atom a is buried by atom b (b != a, b taking part) iff |q - c_b|^2 < E_b^2, strictly, in exact
+ *     integers.
+ *   Counts per atom: free_a, the points of a not buried by any atom of a's OWN molecule; bound_a, those not buried by
+ *     any atom of either molecule.  bound_a <= free_a <= 128; both are 0 for an atom that takes no part.
+ *   Sums per pose, four uint64 in this order: sum free_a E_a^2 and sum bound_a E_a^2 over the receptor, then the same
+ *     two over the ligand.  An area in A^2 is sum * 4 pi / (128e6); the area a model buries is
+ *     (s0 - s1 + s2 - s3) * 4 pi / (128e6).
+ *   The directions are fixed in the run's frame and rounding follows posing, so the ligand's free counts change with
+ *     the pose even without modes.  Every result is the same bits whatever the batch.
+ * LD_ERR_INVALID, nothing written: a probe that is negative, above 2.0 or not finite; non-finite poses, a zero
+ * quaternion, stride < pose_len; a posed coordinate of an atom that takes part beyond +-1.0e6 A; a complex in which no
+ * atom of a side takes part; a side other than 0 / 1.  Device workspace: one slot of 36 B an atom that takes part per
+ * workgroup in flight, at most 1024 slots and 256 MiB (or one slot); per-atom counts are produced in chunks of poses
+ * within 256 MiB. */
+#define LD_SASA_POINTS (128)
+int ld_sasa_directions(int32_t *out /* LD_SASA_POINTS x 3 */); /* host only */
+int ld_complex_sasa_radii(const ld_complex *c, int side, uint32_t *radii_out /* n_atoms of that side, thousandths */); /* host only */
+/* Any output may be NULL; n == 0 is LD_OK.  ld_complex_last_kernel_ms then reports this call's device work. */
+int ld_complex_sasa(ld_complex *c, size_t n, const double *poses, size_t stride, double probe /* 1.4 */,
+                    uint64_t *sums /* n x 4 */, uint8_t *free_counts /* n x (n_rec + n_lig), receptor first, file order */,
+                    uint8_t *bound_counts /* as free_counts */);
+
 /* ------------------------------------------------------------------------------------
  * Normal modes: the rec_nm.npy / lig_nm.npy a run with `use_anm: true` reads
  * (src/bin/lightdock-rust.rs:216-254 is the consumer; the reference tree cannot produce them,

@@ -173,6 +173,9 @@ def load_library():
     lib.ld_complex_residue_id.argtypes = [vp, C.c_int, sz, C.c_char_p, sz]
     lib.ld_complex_residue_of_atom.argtypes = [vp, C.c_int, vp]
     lib.ld_complex_contacts.argtypes = [vp, sz, vp, sz, C.c_double, vp, vp]
+    lib.ld_sasa_directions.argtypes = [vp]
+    lib.ld_complex_sasa_radii.argtypes = [vp, C.c_int, vp]
+    lib.ld_complex_sasa.argtypes = [vp, sz, vp, sz, C.c_double, vp, vp, vp]
     lib.ld_complex_set_reference.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_double, C.c_double]
     lib.ld_complex_reference_counts.argtypes = [vp, vp]
     lib.ld_complex_native_pairs.argtypes = [vp, vp]
@@ -619,7 +622,7 @@ class GSO:
 
 class Complex:
     """LightDock's analysis of a run (ld_complex_*): posed coordinates, BSAS clustering of whole swarms and of one ranked
-    list across swarms, top-model PDBs, per-pose interface contacts."""
+    list across swarms, top-model PDBs, per-pose interface contacts, solvent-accessible and buried surface."""
 
     def __init__(self, receptor_pdb, ligand_pdb, rec_nmodes=None, rec_num_anm=0, lig_nmodes=None, lig_num_anm=0):
         self.lib = load_library()
@@ -721,6 +724,30 @@ class Complex:
             out[k] = bits[:, :self.num_residues(side)].astype(bool)
         return out
 
+    def sasa_radii(self, side):
+        """The radius of every atom of a side (0 receptor, 1 ligand) in thousandths of an A, 0 for an atom that takes no
+        part in the surface: a hydrogen, a deuterium, a membrane bead (ld_complex_sasa_radii)."""
+        out = np.zeros(self.num_atoms(side) if side in (0, 1) else 0, dtype=np.uint32)
+        _check(self.lib.ld_complex_sasa_radii(self._h, side, _ptr(out)))
+        return out
+
+    def sasa(self, poses, probe=1.4, atoms=False):
+        """(n, >= pose_len) poses -> {"sums": (n, 4) uint64}: the weighted point counts sum count x E^2 of the receptor
+        alone, the receptor in the complex, the ligand alone, the ligand in the complex (ld_complex_sasa; lightdock_hip.h,
+        "Solvent-accessible surface"); sasa_area() turns them into A^2.  atoms=True adds "free" and "bound", (n, receptor
+        + ligand atoms) uint8: the exposed points, of 128, of every atom in its own molecule and in the complex."""
+        poses = _f64(poses)
+        if poses.ndim != 2:
+            raise ValueError("poses must be (n, pose_len)")
+        n = poses.shape[0]
+        out = {"sums": np.zeros((n, 4), dtype=np.uint64)}
+        if atoms:
+            n_atoms = self.num_atoms(0) + self.num_atoms(1)
+            out["free"], out["bound"] = np.zeros((n, n_atoms), dtype=np.uint8), np.zeros((n, n_atoms), dtype=np.uint8)
+        _check(self.lib.ld_complex_sasa(self._h, n, _ptr(poses), poses.shape[1], C.c_double(probe), _ptr(out["sums"]),
+                                        _ptr(out.get("free")), _ptr(out.get("bound"))))
+        return out
+
     def write_pdb(self, pose, path):
         pose = _f64(pose).ravel()
         if pose.size != self.pose_len:
@@ -755,6 +782,22 @@ class Complex:
         n_native = self.reference_counts()["native_pairs"]
         _check(self.lib.ld_complex_assess(self._h, n, _ptr(poses), poses.shape[1], _ptr(kept), _ptr(lrmsd), _ptr(irmsd)))
         return {"kept": kept, "fnat": kept / float(n_native), "lrmsd": lrmsd, "irmsd": irmsd}
+
+
+SASA_POINTS = 128
+
+
+def sasa_directions():
+    """The (128, 3) int32 table of the surface rule: rint(2^20 x golden-spiral unit vector) (ld_sasa_directions)."""
+    out = np.zeros((SASA_POINTS, 3), dtype=np.int32)
+    _check(load_library().ld_sasa_directions(_ptr(out)))
+    return out
+
+
+def sasa_area(weighted):
+    """Weighted point counts (count x E^2 in thousandths^2: sasa()'s sums, their differences, an atom's count times its
+    squared expanded radius) -> A^2: x 4 pi / (128 x 10^6)."""
+    return np.asarray(weighted, dtype=np.float64) * (4.0 * np.pi / (SASA_POINTS * 1e6))
 
 
 ANM_CUTOFF = 15.0

@@ -500,6 +500,25 @@ int ld_complex_contacts(ld_complex *c, size_t n, const double *poses, size_t str
         c->impl.contacts(n, poses, stride, cutoff, rec_bits, lig_bits);
     });
 }
+int ld_sasa_directions(int32_t *out) {
+    return guarded([&] {
+        if (!out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        std::memcpy(out, ld::kSasaDirections, sizeof ld::kSasaDirections);
+    });
+}
+int ld_complex_sasa_radii(const ld_complex *c, int side, uint32_t *radii_out) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.sasa_radii(side, radii_out);
+    });
+}
+int ld_complex_sasa(ld_complex *c, size_t n, const double *poses, size_t stride, double probe, uint64_t *sums, uint8_t *free_counts,
+                    uint8_t *bound_counts) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.sasa(n, poses, stride, probe, sums, free_counts, bound_counts);
+    });
+}
 int ld_complex_set_reference(ld_complex *c, const char *ref_receptor_pdb, const char *ref_ligand_pdb, double contact_cutoff,
                              double interface_cutoff) {
     return guarded([&] {

@@ -3,6 +3,7 @@
 #include "complex.hpp"
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -28,6 +29,27 @@ long long cutoff_thousandths(double cutoff, const char *message) {
 }
 
 }  // namespace
+
+uint32_t sasa_radius(const char *line, size_t len) {
+    static const struct {
+        const char *element;
+        uint32_t radius;
+    } table[] = {{"C", 1700}, {"N", 1550}, {"O", 1520}, {"F", 1470}, {"P", 1800}, {"S", 1800}, {"CL", 1750}, {"SE", 1900}, {"BR", 1850}, {"I", 1980}};
+    std::string element;
+    if (len >= 78)
+        for (size_t k = 76; k < 78; k++)
+            if (line[k] != ' ') element.push_back((char)std::toupper((unsigned char)line[k]));
+    if (element.empty())
+        for (size_t k = 12; k < 16 && element.empty(); k++)
+            if (std::isalpha((unsigned char)line[k])) element.push_back((char)std::toupper((unsigned char)line[k]));
+    size_t b = 17, e = 20;  // the residue name, blanks trimmed
+    while (b < e && line[b] == ' ') b++;
+    while (e > b && line[e - 1] == ' ') e--;
+    if (element == "H" || element == "D" || std::string(line + b, e - b) == "MMB") return 0;
+    for (const auto &row : table)
+        if (element == row.element) return row.radius;
+    return 1800;
+}
 
 Complex::Complex(const char *receptor_pdb, const char *ligand_pdb, const double *rec_nmodes, size_t rec_nmodes_len,
                  size_t rec_num_anm, const double *lig_nmodes, size_t lig_nmodes_len, size_t lig_num_anm)
@@ -72,6 +94,24 @@ Complex::Complex(const char *receptor_pdb, const char *ligand_pdb, const double 
         for (uint32_t r : lig_.res_of_atom) res_of_atom.push_back(r + (uint32_t)k.n_rec_res);
         k.res_of_atom = arena_.upload(res_of_atom);
         k.boxes_in_lds = k.box_bytes() <= kMaxBoxLdsBytes;
+        // the atoms that take part in the surface, the receptor's first
+        std::vector<uint32_t> part_atom, part_radius;
+        const PdbFile *files[2] = {&rec_, &lig_};
+        for (int side = 0; side < 2; side++) {
+            for (size_t a = 0; a < files[side]->lines.size(); a++) {
+                const uint32_t r = sasa_radius(files[side]->lines[a].data(), files[side]->lines[a].size());
+                sasa_radius_[side].push_back(r);
+                if (r == 0) continue;
+                part_atom.push_back((uint32_t)(side * rec_.lines.size() + a));
+                part_radius.push_back(r);
+                sasa_r_max_ = std::max(sasa_r_max_, (int)r);
+            }
+            if (side == 0) sasa_.n_part_rec = (int)part_atom.size();
+        }
+        sasa_.n_atoms = k.n_atoms;
+        sasa_.n_part = (int)part_atom.size();
+        sasa_.part_atom = arena_.upload(part_atom);
+        sasa_.part_radius = arena_.upload(part_radius);
     } catch (...) {
         destroy();  // no destructor runs for a constructor that throws
         throw;
@@ -303,6 +343,58 @@ void Complex::contacts(size_t n, const double *poses, size_t stride, double cuto
     finish_timed(d_overflow, "complex_contacts", "a posed coordinate is beyond +-1.0e6 A");
     if (rec_bits) hip_check(hipMemcpy(rec_bits, d_rec, n * rw * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
     if (lig_bits) hip_check(hipMemcpy(lig_bits, d_lig, n * lw * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
+}
+
+// --- the solvent-accessible surface (lightdock_hip.h, "Solvent-accessible surface"; kernels/sasa.hpp) ------------------
+
+void Complex::sasa_radii(int side, uint32_t *radii_out) const {
+    side_file(side);
+    if (!radii_out) throw Error(LD_ERR_INVALID, "null argument");
+    std::copy(sasa_radius_[side].begin(), sasa_radius_[side].end(), radii_out);
+}
+
+void Complex::sasa(size_t n, const double *poses, size_t stride, double probe, uint64_t *sums, uint8_t *free_counts,
+                   uint8_t *bound_counts) {
+    if (!(probe >= 0.0 && probe <= 2.0)) throw Error(LD_ERR_INVALID, "probe must be 0 .. 2.0 A");
+    if (sasa_.n_part_rec == 0 || sasa_.n_part == sasa_.n_part_rec)
+        throw Error(LD_ERR_INVALID, "no atom of a side takes part in the surface (all hydrogens or membrane beads)");
+    if (n == 0) return;
+    check_poses(n, poses, stride);
+    SasaDevice d = sasa_;
+    d.probe = (int)std::llrint(1000.0 * probe);
+    d.e_max = sasa_r_max_ + d.probe;
+    const bool atoms = free_counts || bound_counts;
+    const size_t n_all = n_atoms(), per_slot = sasa_slot_bytes(d.n_part);
+    const size_t slots = std::min(n, std::min<size_t>(kSasaSlots, std::max<size_t>(1, kClusterWorkspaceBytes / per_slot)));
+    // per-atom counts leave in chunks of poses; nothing reaches the caller before the overflow flag is known
+    const size_t chunk = atoms ? std::min(n, std::max<size_t>(1, kClusterWorkspaceBytes / (2 * n_all))) : n;
+    const size_t counts_bytes = atoms ? (chunk * n_all + 15) / 16 * 16 : 0;
+    std::vector<uint8_t> h_free(atoms ? n * n_all : 0), h_bound(atoms ? n * n_all : 0);
+    upload_poses(n, poses, stride);
+    d_ids_.reserve(n * 4 * sizeof(uint64_t) + 16 + 2 * counts_bytes);
+    unsigned long long *d_sums = static_cast<unsigned long long *>(d_ids_.ptr);
+    int *d_overflow = reinterpret_cast<int *>(d_sums + n * 4);
+    uint8_t *d_free = atoms ? reinterpret_cast<uint8_t *>(d_sums + n * 4) + 16 : nullptr;
+    uint8_t *d_bound = atoms ? d_free + counts_bytes : nullptr;
+    hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), stream_), "hipMemset");
+    d_ws_.reserve(slots * per_slot);
+    const double *d_poses = static_cast<const double *>(d_poses_.ptr);
+    hip_check(hipEventRecord(ev0_, stream_), "hipEventRecord");
+    for (size_t i0 = 0; i0 < n; i0 += chunk) {
+        const size_t m = std::min(chunk, n - i0);
+        if (atoms) hip_check(hipMemsetAsync(d_free, 0, 2 * counts_bytes, stream_), "hipMemset");  // atoms that take no part stay 0
+        hip_check(launch_complex_sasa(dev_, d, d_poses + i0 * stride, stride, m, std::min(slots, m), d_ws_.ptr, d_sums + i0 * 4, d_free,
+                                      d_bound, d_overflow, stream_),
+                  "complex_sasa launch");
+        if (atoms) {
+            hip_check(hipMemcpyAsync(h_free.data() + i0 * n_all, d_free, m * n_all, hipMemcpyDeviceToHost, stream_), "hipMemcpy D2H");
+            hip_check(hipMemcpyAsync(h_bound.data() + i0 * n_all, d_bound, m * n_all, hipMemcpyDeviceToHost, stream_), "hipMemcpy D2H");
+        }
+    }
+    finish_timed(d_overflow, "complex_sasa", "a posed coordinate is beyond +-1.0e6 A");
+    if (sums) hip_check(hipMemcpy(sums, d_sums, n * 4 * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
+    if (free_counts) std::copy(h_free.begin(), h_free.end(), free_counts);
+    if (bound_counts) std::copy(h_bound.begin(), h_bound.end(), bound_counts);
 }
 
 // --- model quality against a reference complex (lightdock_hip.h, "Model quality"; kernels/assess.hpp) ------------------

@@ -12,6 +12,7 @@
 #include "kernels/assess.hpp"
 #include "kernels/cluster.hpp"
 #include "kernels/ranked.hpp"
+#include "kernels/sasa.hpp"
 
 namespace ld {
 
@@ -37,6 +38,9 @@ class Complex {
                         int32_t *cluster_of, int32_t *representatives, uint32_t *n_clusters);
     void contacts(size_t n, const double *poses, size_t stride, double cutoff, uint32_t *rec_bits, uint32_t *lig_bits);
     void write_pdb(const double *pose, const char *path);
+    // Solvent-accessible surface (lightdock_hip.h, "Solvent-accessible surface")
+    void sasa_radii(int side, uint32_t *radii_out) const;  // thousandths, 0 for an atom that takes no part
+    void sasa(size_t n, const double *poses, size_t stride, double probe, uint64_t *sums, uint8_t *free_counts, uint8_t *bound_counts);
     // Model quality against a reference complex (lightdock_hip.h, "Model quality")
     void set_reference(const char *ref_receptor_pdb, const char *ref_ligand_pdb, double contact_cutoff, double interface_cutoff);
     void reference_counts(uint32_t *out) const;  // 6: matched rec, matched lig, native pairs, rec fit, lig fit, interface fit
@@ -59,6 +63,9 @@ class Complex {
     ComplexDevice dev_;
     const uint32_t *d_backbone_ = nullptr;
     ContactsDevice contacts_;
+    SasaDevice sasa_;                       // probe and e_max are set per call
+    std::vector<uint32_t> sasa_radius_[2];  // every atom of a side, 0 for one that takes no part
+    int sasa_r_max_ = 0;
     // what set_reference derived; `set` only once all of it stands
     struct Reference {
         bool set = false;

@@ -1,4 +1,4 @@
-// complex_pose.hpp -- device code the analysis kernels share (kernels/cluster.hip, kernels/assess.hip, kernels/ranked.hip):
+// complex_pose.hpp -- device code the analysis kernels share (kernels/cluster.hip, kernels/assess.hip, kernels/ranked.hip, kernels/sasa.hip):
 // the posing of one atom of a complex, the rounding to the thousandths "%8.3f" prints, the clustering's RMSD test, and the
 // 32-bit contact test on two atoms' thousandths.
 // Include from a .hip file only.
