@@ -106,6 +106,17 @@ extern "C" {
     pub fn ld_anm_modes(pdb_path: *const c_char, n_modes: usize, cutoff: f64, rmsd: f64, modes_out: *mut f64,
                         eigenvalues_out: *mut f64) -> c_int;
     pub fn ld_anm_last_kernel_ms(ms_out: *mut f64) -> c_int;
+    pub fn ld_swarm_diameter2(xyz: *const i32, n: usize, d2_out: *mut u64) -> c_int;
+    pub fn ld_swarm_shell(atoms: *const i32, bead: *const u8, n: usize, spacing: i32, nodes_out: *mut i32, cap: usize,
+                          count_out: *mut usize, lattice_nodes_out: *mut u64) -> c_int;
+    pub fn ld_swarm_centres(points: *const i32, n: usize, max_centres: usize, cover: i32, index_out: *mut u32, gap2_out: *mut u64,
+                            n_out: *mut usize) -> c_int;
+    pub fn ld_initial_poses(seed: u64, glowworms: usize, swarm: usize, first: usize, n: usize, centre: *const f64, radius: f64,
+                            rec_points: *const f64, n_rec: usize, lig_points: *const f64, n_lig: usize, anm_rec: usize,
+                            anm_lig: usize, rows_out: *mut f64, draws_out: *mut u64) -> c_int;
+    pub fn ld_prepare_pdb(in_path: *const c_char, out_path: *const c_char, keep_flags: c_int, atoms_out: *mut usize,
+                          centre_out: *mut f64) -> c_int;
+    pub fn ld_setup_last_kernel_ms(ms_out: *mut f64) -> c_int;
     // Solvent-accessible surface (include/lightdock_hip.h, "Solvent-accessible surface"): Shrake-Rupley on integer thousandths
     pub fn ld_complex_create(receptor_pdb: *const c_char, ligand_pdb: *const c_char, rec_nmodes: *const f64, rec_nmodes_len: usize,
                              rec_num_anm: usize, lig_nmodes: *const f64, lig_nmodes_len: usize, lig_num_anm: usize) -> *mut ld_complex;

@@ -558,6 +558,84 @@ int ld_anm_modes(const char *pdb_path, size_t n_modes, double cutoff /* 15.0 */,
 int ld_anm_last_kernel_ms(double *ms_out);
 
 /* ------------------------------------------------------------------------------------
+ * Preparing a run: the swarm centres and the start poses lightdock3_setup.py computes, so that a
+ * run starts from its two PDB files alone (lightdock-rust_amd/prepare.py).  LightDock's own
+ * placement (ProDy's surface selection, scipy's kmeans2) cannot be reproduced and is not claimed;
+ * the rule is this library's own, modelled on it.  Every decision that picks a centre is exact
+ * integer arithmetic on int32 thousandths of an angstrom, as "%8.3f" prints a coordinate of the
+ * cleaned, centred files; |x| <= 2 000 000 or the call is refused.
+ *   1. Distance D = isqrt(max_{i,j} |l_i - l_j|^2) / 4, floor both times, over the ligand's atoms
+ *      with a radius > 0 under "Solvent-accessible surface" (ld_swarm_diameter2 gives the maximum).
+ *   2. Shell candidates (ld_swarm_shell).  An atom b has a centre c_b and an extent E_b: R_b + D for
+ *      a receptor atom with R_b > 0, 2000 + D for a bead (a residue named MMB), which is flagged.
+ *      Lattice nodes are p = (i h, j h, k h), h the spacing; per axis i runs from
+ *      floor((min_b c_b - E_max - h) / h) to ceil((max_b c_b + E_max + h) / h).  A node is a candidate
+ *      iff |p - c_b|^2 >= E_b^2 for EVERY atom and bead and |p - c_b|^2 < (E_b + h)^2 for SOME atom
+ *      that is no bead: beads keep centres out of the membrane and attract none.  Candidates are
+ *      numbered in lexicographic (x, y, z) order.
+ *   3. Centres (ld_swarm_centres): farthest-point sampling.  The first centre is the candidate of
+ *      largest |p|^2; each next one is the candidate, not chosen yet, whose smallest squared distance to
+ *      the chosen ones (its gap^2) is largest; ties go to the lowest index.  Sampling ends after
+ *      max_centres, when every candidate is chosen, and, with cover > 0, before a centre (the first
+ *      excepted) whose gap^2 <= cover^2.
+ *   4. Restraint filter (prepare.py, host): with restraint residues on the receptor a centre is kept
+ *      iff it is among the swarms_per_restraint nearest (squared distance on thousandths, ties by
+ *      centre index) to some restraint residue's CA, else P, else first atom; the kept centres are
+ *      renumbered in ascending order.
+ *   5. Poses (ld_initial_poses, host).  Stream: ld_stdrng_key(seed); u64 number k is words 2 (k % 8),
+ *      2 (k % 8) + 1 of ChaCha block k / 8.  Glowworm g of swarm s of a run of G glowworms reads the
+ *      draws ((s G + g) << 16) + j, j = 0, 1, ..: a row depends on (seed, s, g) alone.
+ *      u = (bits >> 11) 2^-53, v = 2 u - 1.  In this order:
+ *        translation: triples (v1, v2, v3) until (v1^2 + v2^2) + v3^2 <= 1; t = centre + radius v.
+ *        rotation, unless both sides have restraint points (Marsaglia): pairs until r1 = x1^2 + y1^2
+ *          < 1, pairs until 0 < r2 = x2^2 + y2^2 < 1; q = (x1, y1, x2 s, y2 s), s = sqrt((1 - r1) / r2).
+ *        rotation with restraint points on both sides: one draw picks the receptor's, floor(u n_rec),
+ *          the next the ligand's; q is the shortest arc taking a = unit(l) to b = unit(r - t), l in the
+ *          centred ligand frame: q = normalise(1 + a.b, a x b); when 1 + a.b < 1e-12, half a turn about
+ *          a x e, e the coordinate axis of a's smallest absolute component (the lowest on a tie); a zero
+ *          l or r - t gives the identity.
+ *        mode extents: anm_rec + anm_lig standard normals by the polar method: pairs until 0 < s =
+ *          v1^2 + v2^2 < 1, each giving v1 f, v2 f, f = sqrt(-2 ln s / s); a left-over one is discarded.
+ *      Sums of squares add left to right, no operation is fused.
+ *   Cleaned files (ld_prepare_pdb, host): the ATOM / HETATM records in file order; element H or D
+ *      (the surface rule's element test), atoms named OXT and residues HOH / WAT are dropped unless
+ *      kept by flag, MMB is kept; with t the thousandths llrint(1000 x) of the n kept atoms and S their
+ *      sum per axis, a coordinate becomes floor((2 (t n - S) + n) / (2 n)), printed "%8.3f".
+ * LD_ERR_INVALID, every output as it was: a null argument; a coordinate beyond +-2 000 000; no
+ * atoms, an extent outside 1 .. 4 000 000, a spacing outside 1 .. 1 000 000; a lattice of more than
+ * 2^28 nodes or more than 2^22 candidates (the message names the spacing); a cap below the count
+ * (count_out then holds the count, which is all that is written); more than 2^22 points, max_centres
+ * == 0, a negative cover; more than 2^20 atoms for the diameter.  Device memory for the call only.
+ * ---------------------------------------------------------------------------------- */
+int ld_swarm_diameter2(const int32_t *xyz /* n x 3 */, size_t n, uint64_t *d2_out);
+/* nodes_out NULL: the count alone.  lattice_nodes_out (or NULL): the nodes tested. */
+int ld_swarm_shell(const int32_t *atoms /* n x 4: x y z E */, const uint8_t *bead /* n flags, or NULL: none */, size_t n,
+                   int32_t spacing /* 2000 */, int32_t *nodes_out /* cap x 3 or NULL */, size_t cap, size_t *count_out,
+                   uint64_t *lattice_nodes_out);
+/* index_out, gap2_out: min(max_centres, n) entries; gap2_out[k] is the value centre k was picked at, |p|^2 for the
+ * first, its gap^2 for the others (non-increasing from the second).  n == 0 is LD_OK with *n_out = 0. */
+int ld_swarm_centres(const int32_t *points /* n x 3 */, size_t n, size_t max_centres, int32_t cover /* 0: no cover rule */,
+                     uint32_t *index_out, uint64_t *gap2_out, size_t *n_out);
+/* Host only.  Rows first .. first + n - 1 of swarm `swarm`; rows_out: n x (7 + anm_rec + anm_lig); draws_out: the u64
+ * draws each row consumed, or NULL.  LD_ERR_INVALID, nothing written: rows that are no glowworms of the run, more than
+ * 2^24 swarms or glowworms or 4096 modes a side, a negative radius, a non-finite value. */
+int ld_initial_poses(uint64_t seed, size_t glowworms, size_t swarm, size_t first, size_t n, const double centre[3],
+                     double radius /* 10.0 */, const double *rec_points /* n_rec x 3 or NULL */, size_t n_rec,
+                     const double *lig_points /* n_lig x 3 or NULL */, size_t n_lig, size_t anm_rec, size_t anm_lig,
+                     double *rows_out, uint64_t *draws_out);
+/* Host only.  keep_flags: 1 hydrogens, 2 OXT, 4 waters.  LD_ERR_IO: a file that cannot be read or written, a record
+ * shorter than 54 columns; LD_ERR_INVALID: no atom kept, a centred coordinate that "%8.3f" cannot hold.  The output file
+ * is written only when every record has passed. */
+#define LD_KEEP_HYDROGENS (1)
+#define LD_KEEP_OXT (2)
+#define LD_KEEP_WATERS (4)
+int ld_prepare_pdb(const char *in_path, const char *out_path, int keep_flags, size_t *atoms_out /* or NULL */,
+                   double centre_out[3] /* the mean subtracted, A; or NULL */);
+/* The device work of this thread's last ld_swarm_diameter2 / ld_swarm_shell / ld_swarm_centres that reached the device
+ * (HIP events; for the centres from the first step's launch to the last, the host's reads of the stop word included). */
+int ld_setup_last_kernel_ms(double *ms_out);
+
+/* ------------------------------------------------------------------------------------
  * The reference command line (src/bin/lightdock-rust.rs:77-333) as a function:
  *   argv = { prog, setup.json, initial_positions_N.dat, steps, dfire|dna|pydock }
  * Same stdout lines, same files, same "usage errors return 0" behaviour.

@@ -184,6 +184,12 @@ def load_library():
     lib.ld_anm_modes_xyz.argtypes = [vp, sz, sz, C.c_double, vp, vp]
     lib.ld_anm_modes.argtypes = [C.c_char_p, sz, C.c_double, C.c_double, vp, vp]
     lib.ld_anm_last_kernel_ms.argtypes = [dp]
+    lib.ld_swarm_diameter2.argtypes = [vp, sz, C.POINTER(C.c_uint64)]
+    lib.ld_swarm_shell.argtypes = [vp, vp, sz, C.c_int32, vp, sz, C.POINTER(sz), C.POINTER(C.c_uint64)]
+    lib.ld_swarm_centres.argtypes = [vp, sz, sz, C.c_int32, vp, vp, C.POINTER(sz)]
+    lib.ld_initial_poses.argtypes = [C.c_uint64, sz, sz, sz, sz, vp, C.c_double, vp, sz, vp, sz, sz, sz, vp, vp]
+    lib.ld_prepare_pdb.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(sz), vp]
+    lib.ld_setup_last_kernel_ms.argtypes = [dp]
     _lib = lib
     return lib
 
@@ -842,6 +848,81 @@ def anm_last_kernel_ms():
     """The device work of this thread's last anm_modes / anm_modes_xyz, in ms (HIP events)."""
     ms = C.c_double()
     _check(load_library().ld_anm_last_kernel_ms(C.byref(ms)))
+    return ms.value
+
+
+KEEP_HYDROGENS, KEEP_OXT, KEEP_WATERS = 1, 2, 4
+
+
+def _i32(a, columns):
+    return np.ascontiguousarray(a, dtype=np.int32).reshape(-1, columns)
+
+
+def swarm_diameter2(xyz):
+    """max |x_i - x_j|^2 of (n, 3) int32 thousandths, exact (ld_swarm_diameter2; lightdock_hip.h, "Preparing a run")."""
+    xyz = _i32(xyz, 3)
+    out = C.c_uint64()
+    _check(load_library().ld_swarm_diameter2(_ptr(xyz), xyz.shape[0], C.byref(out)))
+    return out.value
+
+
+def swarm_shell_count(atoms, bead=None, spacing=2000):
+    """(candidates, lattice nodes) of ld_swarm_shell's count-only call."""
+    atoms = _i32(atoms, 4)
+    flags = None if bead is None else np.ascontiguousarray(bead, dtype=np.uint8)
+    count, nodes = C.c_size_t(), C.c_uint64()
+    _check(load_library().ld_swarm_shell(_ptr(atoms), _ptr(flags), atoms.shape[0], int(spacing), None, 0, C.byref(count), C.byref(nodes)))
+    return count.value, nodes.value
+
+
+def swarm_shell(atoms, bead=None, spacing=2000, lattice_nodes=False):
+    """The shell candidates of (n, 4) int32 atoms x y z E, `bead` flagging those that attract no node: (count, 3) int32 in
+    lexicographic order (ld_swarm_shell, the count-only call and then the filling one).  lattice_nodes=True: (candidates,
+    the number of lattice nodes tested)."""
+    atoms = _i32(atoms, 4)
+    flags = None if bead is None else np.ascontiguousarray(bead, dtype=np.uint8)
+    count, nodes = swarm_shell_count(atoms, flags, spacing)
+    out = np.zeros((count, 3), dtype=np.int32)
+    got = C.c_size_t()
+    _check(load_library().ld_swarm_shell(_ptr(atoms), _ptr(flags), atoms.shape[0], int(spacing), _ptr(out), count, C.byref(got), None))
+    return (out[:got.value], nodes) if lattice_nodes else out[:got.value]
+
+
+def swarm_centres(points, max_centres, cover=0):
+    """Farthest-point sampling of (n, 3) int32 points: (indices uint32, gap2 uint64) in the order picked (ld_swarm_centres)."""
+    points = _i32(points, 3)
+    room = max(1, min(int(max_centres), points.shape[0]))
+    index, gap2, n = np.zeros(room, dtype=np.uint32), np.zeros(room, dtype=np.uint64), C.c_size_t()
+    _check(load_library().ld_swarm_centres(_ptr(points), points.shape[0], int(max_centres), int(cover), _ptr(index), _ptr(gap2), C.byref(n)))
+    return index[:n.value], gap2[:n.value]
+
+
+def initial_poses(seed, glowworms, swarm, centre, first=0, n=None, radius=10.0, rec_points=None, lig_points=None, anm_rec=0,
+                  anm_lig=0):
+    """(rows (n, 7 + anm_rec + anm_lig), draws (n,) uint64) of glowworms first .. first + n - 1 of one swarm
+    (ld_initial_poses; host only)."""
+    n = glowworms - first if n is None else n
+    centre = _f64(centre).reshape(3)
+    rec = np.zeros((0, 3)) if rec_points is None else _f64(rec_points).reshape(-1, 3)
+    lig = np.zeros((0, 3)) if lig_points is None else _f64(lig_points).reshape(-1, 3)
+    rows, draws = np.zeros((max(0, n), 7 + anm_rec + anm_lig)), np.zeros(max(0, n), dtype=np.uint64)
+    _check(load_library().ld_initial_poses(seed, glowworms, swarm, first, n, _ptr(centre), C.c_double(radius), _ptr(rec), rec.shape[0],
+                                           _ptr(lig), lig.shape[0], anm_rec, anm_lig, _ptr(rows), _ptr(draws)))
+    return rows, draws
+
+
+def prepare_pdb(in_path, out_path, keep_h=False, keep_oxt=False, keep_waters=False):
+    """Writes the cleaned, centred copy of a PDB file; (atoms written, the mean subtracted in A) (ld_prepare_pdb; host only)."""
+    flags = (KEEP_HYDROGENS if keep_h else 0) | (KEEP_OXT if keep_oxt else 0) | (KEEP_WATERS if keep_waters else 0)
+    atoms, centre = C.c_size_t(), np.zeros(3)
+    _check(load_library().ld_prepare_pdb(os.fsencode(in_path), os.fsencode(out_path), flags, C.byref(atoms), _ptr(centre)))
+    return atoms.value, centre
+
+
+def setup_last_kernel_ms():
+    """The device work of this thread's last swarm_diameter2 / swarm_shell / swarm_centres call, in ms (HIP events)."""
+    ms = C.c_double()
+    _check(load_library().ld_setup_last_kernel_ms(C.byref(ms)))
     return ms.value
 
 

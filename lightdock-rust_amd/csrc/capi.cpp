@@ -17,9 +17,12 @@
 #include "host/cli.hpp"
 #include "host/docking_model.hpp"
 #include "host/error.hpp"
+#include "host/initial_poses.hpp"
 #include "host/io.hpp"
+#include "host/prepare_pdb.hpp"
 #include "host/spatial_order.hpp"
 #include "lightdock_hip.h"
+#include "prepare.hpp"
 #include "scorer.hpp"
 
 namespace {
@@ -591,6 +594,73 @@ int ld_anm_last_kernel_ms(double *ms_out) {
     return guarded([&] {
         if (!ms_out) throw ld::Error(LD_ERR_INVALID, "null argument");
         *ms_out = ld::anm_last_kernel_ms();
+    });
+}
+
+int ld_swarm_diameter2(const int32_t *xyz, size_t n, uint64_t *d2_out) {
+    return guarded([&] {
+        if (!xyz || !d2_out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        *d2_out = ld::swarm_diameter2(xyz, n);
+    });
+}
+int ld_swarm_shell(const int32_t *atoms, const uint8_t *bead, size_t n, int32_t spacing, int32_t *nodes_out, size_t cap,
+                   size_t *count_out, uint64_t *lattice_nodes_out) {
+    return guarded([&] {
+        if (!atoms || !count_out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        const ld::SwarmShell shell = ld::swarm_shell(atoms, bead, n, spacing);
+        const size_t count = shell.candidates.size() / 3;
+        *count_out = count;
+        if (nodes_out && cap < count)
+            throw ld::Error(LD_ERR_INVALID, "room for " + std::to_string(cap) + " candidates, the shell has " + std::to_string(count));
+        if (lattice_nodes_out) *lattice_nodes_out = shell.nodes;
+        if (nodes_out && count) std::memcpy(nodes_out, shell.candidates.data(), shell.candidates.size() * sizeof(int32_t));
+    });
+}
+int ld_swarm_centres(const int32_t *points, size_t n, size_t max_centres, int32_t cover, uint32_t *index_out, uint64_t *gap2_out,
+                     size_t *n_out) {
+    return guarded([&] {
+        if ((!points && n) || !index_out || !gap2_out || !n_out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        const ld::SwarmCentres c = ld::swarm_centres(points, n, max_centres, cover);
+        if (!c.index.empty()) {
+            std::memcpy(index_out, c.index.data(), c.index.size() * sizeof(uint32_t));
+            std::memcpy(gap2_out, c.gap2.data(), c.gap2.size() * sizeof(uint64_t));
+        }
+        *n_out = c.index.size();
+    });
+}
+int ld_initial_poses(uint64_t seed, size_t glowworms, size_t swarm, size_t first, size_t n, const double centre[3], double radius,
+                     const double *rec_points, size_t n_rec, const double *lig_points, size_t n_lig, size_t anm_rec, size_t anm_lig,
+                     double *rows_out, uint64_t *draws_out) {
+    return guarded([&] {
+        if (!centre || (n && !rows_out)) throw ld::Error(LD_ERR_INVALID, "null argument");
+        ld::PoseRequest r;
+        r.seed = seed;
+        r.glowworms = glowworms;
+        r.swarm = swarm;
+        r.first = first;
+        r.n = n;
+        std::memcpy(r.centre, centre, sizeof r.centre);
+        r.radius = radius;
+        r.rec_points = rec_points;
+        r.n_rec = n_rec;
+        r.lig_points = lig_points;
+        r.n_lig = n_lig;
+        r.anm_rec = anm_rec;
+        r.anm_lig = anm_lig;
+        ld::initial_poses(r, rows_out, draws_out);
+    });
+}
+int ld_prepare_pdb(const char *in_path, const char *out_path, int keep_flags, size_t *atoms_out, double centre_out[3]) {
+    return guarded([&] {
+        const ld::PreparedPdb p = ld::prepare_pdb(in_path, out_path, keep_flags);
+        if (atoms_out) *atoms_out = p.atoms;
+        if (centre_out) std::memcpy(centre_out, p.centre, sizeof p.centre);
+    });
+}
+int ld_setup_last_kernel_ms(double *ms_out) {
+    return guarded([&] {
+        if (!ms_out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        *ms_out = ld::setup_last_kernel_ms();
     });
 }
 
