@@ -64,6 +64,53 @@ pub struct ld_group_energies {
 
 pub const LD_GROUP_NONE: u32 = 0xffff_ffff;
 
+/// `ld_refine_history`: j* on an accept, -1 halved, -2 frozen in this iteration, -3 not evaluated
+/// (include/lightdock_hip.h, "Local refinement").
+#[allow(non_camel_case_types)]
+pub type ld_refine_history = i16;
+
+/// `ld_refine_options`: the iterations, the step halvings a pose may take and the three start steps.
+#[allow(non_camel_case_types)]
+#[derive(Clone, Copy)]
+#[repr(C)]
+pub struct ld_refine_options {
+    pub iterations: u32,
+    pub max_halvings: u32,
+    pub trans_step: f64,
+    pub rot_step: f64,
+    pub nm_step: f64,
+    pub slice_poses: u32,
+    pub reserved: u32,
+}
+
+/// `ld_refine_stats`: what the refinement made of one pose.
+#[allow(non_camel_case_types)]
+#[derive(Clone, Copy, Default)]
+#[repr(C)]
+pub struct ld_refine_stats {
+    pub energy_before: f64,
+    pub energy_after: f64,
+    pub accepted: u32,
+    pub halvings: u32,
+    pub evaluations: u32,
+    pub frozen: u32,
+}
+
+/// `ld_refine_state`: the per-pose arrays the two kernel entry points take.
+#[allow(non_camel_case_types)]
+#[repr(C)]
+pub struct ld_refine_state {
+    pub energy: *mut f64,
+    pub trans_step: *mut f64,
+    pub rot_cos: *mut f64,
+    pub rot_sin: *mut f64,
+    pub nm_step: *mut f64,
+    pub halvings: *mut u32,
+    pub accepted: *mut u32,
+    pub evaluations: *mut u32,
+    pub frozen: *mut u8,
+}
+
 /// `ld_complex`: the opaque handle of the analysis half of a run (include/lightdock_hip.h, "Analysis of a finished run").
 #[allow(non_camel_case_types)]
 #[repr(C)]
@@ -73,7 +120,7 @@ pub struct ld_complex {
 
 pub const LD_SASA_POINTS: usize = 128;
 
-// The decomposition and residue entry points (ld_scorer_decompose*, ld_model_*) are declared only: no wrapper uses them yet.
+// The decomposition, refinement and residue entry points (ld_scorer_decompose*, ld_scorer_refine*, ld_refine_*, ld_model_*) are declared only: no wrapper uses them yet.
 #[allow(dead_code)]
 extern "C" {
     fn ld_init(device: c_int) -> c_int;
@@ -87,6 +134,16 @@ extern "C" {
     fn ld_scorer_decompose(s: *mut c_void, n: usize, poses: *const f64, stride: usize, terms_out: *mut ld_energy_terms,
                            receptor: *const ld_group_energies, ligand: *const ld_group_energies) -> c_int;
     fn ld_scorer_decompose_info(s: *const c_void, slice_poses_out: *mut usize, last_kernel_ms_out: *mut f64) -> c_int;
+    fn ld_scorer_refine(s: *mut c_void, opts: *const ld_refine_options, n: usize, poses: *const f64, stride: usize,
+                        poses_out: *mut f64, stats_out: *mut ld_refine_stats, history_out: *mut ld_refine_history) -> c_int;
+    fn ld_scorer_refine_info(s: *const c_void, trials_out: *mut usize, slice_poses_out: *mut usize, last_kernel_ms_out: *mut f64,
+                             evaluations_out: *mut u64) -> c_int;
+    fn ld_refine_plan(pose_len: usize, n: usize, stride: usize, iterations: u32, slice_poses: u32, trials_out: *mut usize,
+                      slice_poses_out: *mut usize, workspace_bytes_out: *mut usize) -> c_int;
+    fn ld_refine_trials(n: usize, pose_len: usize, poses: *const f64, stride: usize, state: *const ld_refine_state,
+                        trials: *mut f64, trial_stride: usize, active_out: *mut u8) -> c_int;
+    fn ld_refine_select(n: usize, pose_len: usize, poses: *mut f64, stride: usize, state: *const ld_refine_state,
+                        energies: *const f64, max_halvings: u32, history_out: *mut ld_refine_history) -> c_int;
     fn ld_model_from_pdb(method: c_int, pdb_path: *const c_char, active: *const *const c_char, n_active: usize,
                          passive: *const *const c_char, n_passive: usize, nmodes: *const f64, nmodes_len: usize, num_anm: usize) -> *mut c_void;
     fn ld_model_view(m: *const c_void, out: *mut LdMolecule) -> c_int;

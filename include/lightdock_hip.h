@@ -312,6 +312,85 @@ int ld_scorer_decompose(ld_scorer *s, size_t n, const double *poses, size_t stri
 int ld_scorer_decompose_info(const ld_scorer *s, size_t *slice_poses_out, double *last_kernel_ms_out);
 
 /* ------------------------------------------------------------------------------------
+ * Local refinement: walk a pose uphill under the scorer's own energy by a compass search, every decision a rule without
+ * randomness or line search, so a host restatement follows it to the bit.  The definition:
+ *   A pose is [t(3) | q wxyz(4) | extents(pose_len - 7)] as the scorer reads it; energies are the scorer's own
+ *     (ld_scorer_energy_batch_device); higher is better, as in the GSO.  Per pose the state is E, dt, c, s, dn, halvings, frozen.
+ *   Start: E = the pose's energy; dt = trans_step, dn = nm_step; c = cos(rot_step / 2), s = sin(rot_step / 2), taken once on
+ *     the host with std::cos / std::sin; halvings = 0.
+ *   Trials of one iteration, K = 12 + 2 (pose_len - 7), in this order:
+ *     j = 2 k + sigma, k = 0..2: t[k] + dt for sigma = 0, t[k] - dt for sigma = 1;
+ *     j = 6 + 2 k + sigma: q' = r q with r = (c, +-s on axis k, 0 elsewhere), +s for sigma = 0; the product is Quaternion::mul
+ *       (src/qt.rs:177-184), the same expression in the same order, unfused, and q' is not normalised.  A left product turns
+ *       the ligand about the origin of its own coordinates, because the energy path poses it as q v q^-1 + t;
+ *     j = 12 + 2 m + sigma: extent[m] +- dn.
+ *     Everything else in a trial row is the pose's bits.
+ *   Choice: NaN trial energies count as -inf; j* is the first index of the maximum; accept iff e[j*] > E, strictly.  On accept
+ *     the pose becomes trial j*, E = e[j*], and the steps stay.
+ *   Failure with halvings < max_halvings: halvings += 1; dt *= 0.5, dn *= 0.5; c' = sqrt((1 + c) 0.5), s = s / (2 c'),
+ *     c = c' (IEEE add, multiply, divide and sqrt only).
+ *   Failure with halvings == max_halvings: the pose is frozen, and never evaluated or touched again.
+ *   History, one ld_refine_history per pose and iteration: j* on an accept, -1 when halved, -2 when frozen in this
+ *     iteration, -3 when not evaluated.   evaluations = 1 + K x (iterations in which the pose was evaluated).
+ * A pose whose start energy is NaN (non-finite input, zero quaternion) therefore comes back with its own bits.
+ * Poses run in passes of `slice` poses (slice x K <= 65 536 trial rows unless slice_poses names it; at most 2^22 rows), each
+ * pass all its iterations: one start-energy launch, then refine_trials, the energy launch over the pass's trial rows by their
+ * mask, refine_select per iteration, on the scorer's stream without a host synchronisation in between.
+ * ---------------------------------------------------------------------------------- */
+typedef int16_t ld_refine_history;
+typedef struct ld_refine_options {
+    uint32_t iterations;
+    uint32_t max_halvings;
+    double trans_step;    /* A */
+    double rot_step;      /* rad, <= pi */
+    double nm_step;       /* extent units */
+    uint32_t slice_poses; /* 0: the library's */
+    uint32_t reserved;    /* 0 */
+} ld_refine_options;
+typedef struct ld_refine_stats {
+    double energy_before;
+    double energy_after;
+    uint32_t accepted;
+    uint32_t halvings;
+    uint32_t evaluations;
+    uint32_t frozen;
+} ld_refine_stats;
+typedef struct ld_refine_state { /* per pose: host arrays of n */
+    double *energy;
+    double *trans_step;
+    double *rot_cos;
+    double *rot_sin;
+    double *nm_step;
+    uint32_t *halvings;
+    uint32_t *accepted;
+    uint32_t *evaluations;
+    uint8_t *frozen;
+} ld_refine_state;
+/* Host pointers, synchronous.  poses: n rows of `stride` >= pose_len doubles.  n == 0 is LD_OK and touches nothing.
+ * LD_ERR_INVALID, every output as it was: iterations == 0, a step that is not finite and > 0, rot_step > pi,
+ * stride < pose_len, poses or poses_out missing with n > 0, slice_poses x K beyond 2^22, any size beyond a size_t. */
+int ld_scorer_refine(ld_scorer *s, const ld_refine_options *opts, size_t n, const double *poses, size_t stride,
+                     double *poses_out /* n x pose_len */, ld_refine_stats *stats_out /* n, or NULL */,
+                     ld_refine_history *history_out /* n x iterations, or NULL */);
+/* Any output may be NULL.  trials: K of this scorer; slice: the poses per pass of the last call (before any: the default);
+ * last_kernel_ms: the device work of the last call, all passes (HIP events); evaluations: its total over all poses. */
+int ld_scorer_refine_info(const ld_scorer *s, size_t *trials_out, size_t *slice_poses_out, double *last_kernel_ms_out,
+                          uint64_t *evaluations_out);
+/* Host only: K, the poses per pass and the device workspace of a call (any output may be NULL).  LD_ERR_INVALID: pose_len
+ * outside 7 .. 135, stride < pose_len, iterations == 0, slice_poses x K beyond 2^22, a size beyond a size_t. */
+int ld_refine_plan(size_t pose_len, size_t n, size_t stride, uint32_t iterations, uint32_t slice_poses, size_t *trials_out,
+                   size_t *slice_poses_out, size_t *workspace_bytes_out);
+/* The two kernels of an iteration on caller-given state, without a scorer (host pointers, synchronous; what the tests hold
+ * to the restatement).  ld_refine_trials: trial j of pose p goes to trials + (p K + j) trial_stride, its first pose_len
+ * doubles; active: n x K bytes, 1 for an unfrozen pose and 0 for a frozen one, whose rows stay as they were.
+ * ld_refine_select: energies n x K (a frozen pose's row is not read); poses and state are updated in place;
+ * history_out: n entries. */
+int ld_refine_trials(size_t n, size_t pose_len, const double *poses, size_t stride, const ld_refine_state *state,
+                     double *trials /* n x K x trial_stride, in and out */, size_t trial_stride, uint8_t *active_out);
+int ld_refine_select(size_t n, size_t pose_len, double *poses, size_t stride, const ld_refine_state *state,
+                     const double *energies, uint32_t max_halvings, ld_refine_history *history_out);
+
+/* ------------------------------------------------------------------------------------
  * GSO: batched over independent swarms.  Replaces GSO::new / GSO::run
  * (src/lib.rs:27-58), Swarm (src/swarm.rs) and Glowworm (src/glowworm.rs).
  * ---------------------------------------------------------------------------------- */

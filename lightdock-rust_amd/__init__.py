@@ -59,6 +59,25 @@ class _GroupEnergies(C.Structure):
                 ("interface_atoms", C.c_void_p)]
 
 
+class _RefineOptions(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("max_halvings", C.c_uint32), ("trans_step", C.c_double), ("rot_step", C.c_double),
+                ("nm_step", C.c_double), ("slice_poses", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _RefineState(C.Structure):
+    _fields_ = [("energy", C.c_void_p), ("trans_step", C.c_void_p), ("rot_cos", C.c_void_p), ("rot_sin", C.c_void_p),
+                ("nm_step", C.c_void_p), ("halvings", C.c_void_p), ("accepted", C.c_void_p), ("evaluations", C.c_void_p),
+                ("frozen", C.c_void_p)]
+
+
+# ld_refine_stats as a structured dtype (32 bytes, no padding)
+REFINE_STATS = np.dtype([("energy_before", np.float64), ("energy_after", np.float64), ("accepted", np.uint32),
+                         ("halvings", np.uint32), ("evaluations", np.uint32), ("frozen", np.uint32)])
+# the per-pose arrays of ld_refine_state
+REFINE_STATE = (("energy", np.float64), ("trans_step", np.float64), ("rot_cos", np.float64), ("rot_sin", np.float64),
+                ("nm_step", np.float64), ("halvings", np.uint32), ("accepted", np.uint32), ("evaluations", np.uint32),
+                ("frozen", np.uint8))
+
 # ld_energy_terms as a structured dtype (72 bytes, no padding)
 ENERGY_TERMS = np.dtype([("pair", np.float64, (2,)), ("score", np.float64), ("rec_restraints", np.float64),
                          ("lig_restraints", np.float64), ("membrane", np.float64), ("energy", np.float64),
@@ -150,6 +169,11 @@ def load_library():
     lib.ld_model_residue_of_atom.argtypes = [vp, vp]
     lib.ld_scorer_decompose.argtypes = [vp, sz, vp, sz, vp, C.POINTER(_GroupEnergies), C.POINTER(_GroupEnergies)]
     lib.ld_scorer_decompose_info.argtypes = [vp, C.POINTER(sz), C.POINTER(C.c_double)]
+    lib.ld_scorer_refine.argtypes = [vp, C.POINTER(_RefineOptions), sz, vp, sz, vp, vp, vp]
+    lib.ld_scorer_refine_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    lib.ld_refine_plan.argtypes = [sz, sz, sz, C.c_uint32, C.c_uint32, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    lib.ld_refine_trials.argtypes = [sz, sz, vp, sz, C.POINTER(_RefineState), vp, sz, vp]
+    lib.ld_refine_select.argtypes = [sz, sz, vp, sz, C.POINTER(_RefineState), vp, C.c_uint32, vp]
     lib.ld_dfire_bin_lut.argtypes = [vp, vp, C.POINTER(C.c_double)]
     lib.ld_dfire_packed_lut.argtypes = [C.c_int, C.c_double, vp, C.POINTER(C.c_double)]
     lib.ld_dfire_bm_lut.argtypes = [C.c_double, C.c_double, vp, C.POINTER(C.c_double)]
@@ -531,6 +555,30 @@ class Scorer:
         slice_poses, ms = C.c_size_t(), C.c_double()
         _check(self.lib.ld_scorer_decompose_info(self._h, C.byref(slice_poses), C.byref(ms)))
         return {"slice": slice_poses.value, "last_kernel_ms": ms.value}
+
+    def refine(self, poses, iterations=20, trans_step=1.0, rot_step=0.1, nm_step=0.5, max_halvings=4, slice_poses=0,
+               history=False):
+        """Walk every pose uphill under this scorer's energy by the compass search of lightdock_hip.h, "Local refinement"
+        (ld_scorer_refine).  poses: (n, >= pose_len).  Returns {"poses": (n, pose_len), "stats": structured array (n,) of
+        REFINE_STATS, "history": (n, iterations) int16 or None}."""
+        poses = _f64(poses)
+        if poses.ndim != 2:
+            raise ValueError("poses must be (n, pose_len)")
+        n = poses.shape[0]
+        opts = _RefineOptions(int(iterations), int(max_halvings), float(trans_step), float(rot_step), float(nm_step),
+                              int(slice_poses), 0)
+        out = {"poses": np.zeros((n, self.pose_len)), "stats": np.zeros(n, dtype=REFINE_STATS),
+               "history": np.zeros((n, max(int(iterations), 0)), dtype=np.int16) if history else None}
+        _check(self.lib.ld_scorer_refine(self._h, C.byref(opts), n, _ptr(poses), poses.shape[1], _ptr(out["poses"]),
+                                         _ptr(out["stats"]), _ptr(out["history"])))
+        return out
+
+    def refine_info(self):
+        """{"trials": K of this scorer, "slice": poses per pass of the last refine() (before any: the default),
+        "last_kernel_ms": its device work (HIP events), "evaluations": its energy evaluations over all poses}."""
+        trials, slice_poses, ms, evals = C.c_size_t(), C.c_size_t(), C.c_double(), C.c_uint64()
+        _check(self.lib.ld_scorer_refine_info(self._h, C.byref(trials), C.byref(slice_poses), C.byref(ms), C.byref(evals)))
+        return {"trials": trials.value, "slice": slice_poses.value, "last_kernel_ms": ms.value, "evaluations": evals.value}
 
     def enable_timing(self, on=True):
         _check(self.lib.ld_scorer_enable_timing(self._h, 1 if on else 0))
@@ -917,6 +965,53 @@ def prepare_pdb(in_path, out_path, keep_h=False, keep_oxt=False, keep_waters=Fal
     atoms, centre = C.c_size_t(), np.zeros(3)
     _check(load_library().ld_prepare_pdb(os.fsencode(in_path), os.fsencode(out_path), flags, C.byref(atoms), _ptr(centre)))
     return atoms.value, centre
+
+
+def refine_plan(pose_len, n, stride=None, iterations=1, slice_poses=0):
+    """K, the poses per pass and the device workspace of a refinement call (ld_refine_plan; host only)."""
+    trials, slice_out, ws = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    _check(load_library().ld_refine_plan(pose_len, n, pose_len if stride is None else stride, iterations, slice_poses,
+                                         C.byref(trials), C.byref(slice_out), C.byref(ws)))
+    return {"trials": trials.value, "slice": slice_out.value, "workspace_bytes": ws.value}
+
+
+def _refine_state(state, n):
+    """The arrays of a state dict (REFINE_STATE) as contiguous arrays of n, and the struct that points at them."""
+    arrays = {k: np.ascontiguousarray(state[k], dtype=dt).copy() for k, dt in REFINE_STATE}
+    if any(a.shape != (n,) for a in arrays.values()):
+        raise ValueError("one state entry per pose")
+    return arrays, _RefineState(*[_ptr(arrays[k]) for k, _ in REFINE_STATE])
+
+
+def refine_trials(poses, pose_len, state, trials, active=None):
+    """refine_trials alone on caller-given state (ld_refine_trials; a test entry).  poses: (n, stride); trials: (n, K,
+    trial_stride), whose rows come back with the trial rows written into them.  Returns (trials, active (n, K) uint8)."""
+    poses = _f64(poses)
+    n, K = poses.shape[0], 12 + 2 * (pose_len - 7)
+    trials = _f64(trials).copy()
+    if trials.shape[:2] != (n, K):
+        raise ValueError("trials must be (n, K, trial_stride)")
+    active = np.zeros((n, K), dtype=np.uint8) if active is None else np.ascontiguousarray(active, dtype=np.uint8).copy()
+    _, struct = keep = _refine_state(state, n)
+    _check(load_library().ld_refine_trials(n, pose_len, _ptr(poses), poses.shape[1], C.byref(struct), _ptr(trials),
+                                           trials.shape[2], _ptr(active)))
+    del keep
+    return trials, active
+
+
+def refine_select(poses, pose_len, state, energies, max_halvings):
+    """refine_select alone on caller-given state and energies (ld_refine_select; a test entry).  Returns (poses, state,
+    history (n,) int16); the inputs are not changed."""
+    poses = _f64(poses).copy()
+    n = poses.shape[0]
+    energies = _f64(energies)
+    if energies.shape != (n, 12 + 2 * (pose_len - 7)):
+        raise ValueError("energies must be (n, K)")
+    arrays, struct = _refine_state(state, n)
+    history = np.zeros(n, dtype=np.int16)
+    _check(load_library().ld_refine_select(n, pose_len, _ptr(poses), poses.shape[1], C.byref(struct), _ptr(energies),
+                                           max_halvings, _ptr(history)))
+    return poses, arrays, history
 
 
 def setup_last_kernel_ms():

@@ -20,9 +20,11 @@
 #include "host/initial_poses.hpp"
 #include "host/io.hpp"
 #include "host/prepare_pdb.hpp"
+#include "host/refine_plan.hpp"
 #include "host/spatial_order.hpp"
 #include "lightdock_hip.h"
 #include "prepare.hpp"
+#include "refine.hpp"
 #include "scorer.hpp"
 
 namespace {
@@ -385,6 +387,48 @@ int ld_scorer_decompose_info(const ld_scorer *s, size_t *slice_poses_out, double
         if (!s) throw ld::Error(LD_ERR_INVALID, "null scorer");
         if (slice_poses_out) *slice_poses_out = ld::Decomposer::slice_of(s->desc.view());
         if (last_kernel_ms_out) *last_kernel_ms_out = s->decomposer ? s->decomposer->last_kernel_ms() : 0.0;
+    });
+}
+
+int ld_scorer_refine(ld_scorer *s, const ld_refine_options *opts, size_t n, const double *poses, size_t stride, double *poses_out,
+                     ld_refine_stats *stats_out, ld_refine_history *history_out) {
+    return guarded([&] {
+        if (!s || !opts) throw ld::Error(LD_ERR_INVALID, "null argument");
+        s->refine().run(*opts, n, poses, stride, poses_out, stats_out, history_out);
+    });
+}
+int ld_scorer_refine_info(const ld_scorer *s, size_t *trials_out, size_t *slice_poses_out, double *last_kernel_ms_out,
+                          uint64_t *evaluations_out) {
+    return guarded([&] {
+        if (!s) throw ld::Error(LD_ERR_INVALID, "null scorer");
+        const ld::RefinePlan plan = ld::refine_plan(s->impl.pose_len(), 0, s->impl.pose_len(), 1, 0);
+        if (trials_out) *trials_out = plan.trials;
+        if (slice_poses_out) *slice_poses_out = s->refiner && s->refiner->last_slice() ? s->refiner->last_slice() : plan.slice;
+        if (last_kernel_ms_out) *last_kernel_ms_out = s->refiner ? s->refiner->last_kernel_ms() : 0.0;
+        if (evaluations_out) *evaluations_out = s->refiner ? s->refiner->last_evaluations() : 0;
+    });
+}
+int ld_refine_plan(size_t pose_len, size_t n, size_t stride, uint32_t iterations, uint32_t slice_poses, size_t *trials_out,
+                   size_t *slice_poses_out, size_t *workspace_bytes_out) {
+    return guarded([&] {
+        const ld::RefinePlan plan = ld::refine_plan(pose_len, n, stride, iterations, slice_poses);
+        if (trials_out) *trials_out = plan.trials;
+        if (slice_poses_out) *slice_poses_out = plan.slice;
+        if (workspace_bytes_out) *workspace_bytes_out = plan.workspace_bytes;
+    });
+}
+int ld_refine_trials(size_t n, size_t pose_len, const double *poses, size_t stride, const ld_refine_state *state, double *trials,
+                     size_t trial_stride, uint8_t *active_out) {
+    return guarded([&] {
+        if (!state) throw ld::Error(LD_ERR_INVALID, "null argument");
+        ld::refine_trials_host(n, pose_len, poses, stride, *state, trials, trial_stride, active_out);
+    });
+}
+int ld_refine_select(size_t n, size_t pose_len, double *poses, size_t stride, const ld_refine_state *state, const double *energies,
+                     uint32_t max_halvings, ld_refine_history *history_out) {
+    return guarded([&] {
+        if (!state) throw ld::Error(LD_ERR_INVALID, "null argument");
+        ld::refine_select_host(n, pose_len, poses, stride, *state, energies, max_halvings, history_out);
     });
 }
 

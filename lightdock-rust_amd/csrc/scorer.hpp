@@ -18,6 +18,7 @@
 #include "kernels/dfire_tiled.hpp"
 #include "kernels/pose_energy.hpp"
 #include "lightdock_hip.h"
+#include "refine.hpp"
 
 namespace ld {
 
@@ -294,9 +295,14 @@ struct ld_scorer {
     ld::Scorer impl;                               // checks the description before anything below reads it
     ld::DescCopy desc;                             // what the decomposer is built from, on first use
     std::unique_ptr<ld::Decomposer> decomposer;
+    std::unique_ptr<ld::Refiner> refiner;          // ld_scorer_refine, on first use; runs its trial rows through `impl`
     explicit ld_scorer(const ld_scorer_desc &d) : impl(d), desc(d) {}
     ld::Decomposer &decompose() {
         if (!decomposer) decomposer.reset(new ld::Decomposer(desc.view()));
         return *decomposer;
+    }
+    ld::Refiner &refine() {
+        if (!refiner) refiner.reset(new ld::Refiner(impl));
+        return *refiner;
     }
 };
