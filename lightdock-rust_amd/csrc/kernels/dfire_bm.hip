@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "dfire_device.hpp"
+#include "pose_energy_tail.hpp"
 #include "dfire_bm_batch.inc"
 
 // The LD_BM_DIAG_* blocks below are TIMING EXPERIMENTS (wrong sums by construction).  They compile only in a diagnostic build
@@ -658,14 +659,6 @@ __global__ __launch_bounds__(kBmCullWaves * 64) void dfire_bm_cull(const BmLaunc
 // share each staging of a block's table rows); a launch with few entries -- the late steps of a GSO run, when few
 // glowworms still move -- is cut finer so that its jobs still spread over every wave of the chip.
 // ---------------------------------------------------------------------------------------------
-// entries per part of a tile pair with n entries: its ceil(n / P) parts are EQUAL (a multiple of 64 each; with parts of P and a
-// remainder, a tile pair of 1070 entries -- the average of a 1k4c launch -- was one full job and one of 46 entries that paid
-// the same set-ups for batches a quarter full)
-__device__ __forceinline__ uint32_t bm_part_size(uint32_t n, uint32_t P) {
-    const uint32_t parts = (n + P - 1) / P;
-    return parts ? ((n + parts - 1) / parts + 63u) / 64u * 64u : P;
-}
-
 __global__ __launch_bounds__(1024) void dfire_bm_plan(const BmLaunch launch_arguments) {
     // One workgroup: P, and the list of (tile pair, part) pairs in any order (dfire_bm_order sorts the jobs).
     BmArgs *T = LD_BM_ARGS;
@@ -680,12 +673,7 @@ __global__ __launch_bounds__(1024) void dfire_bm_plan(const BmLaunch launch_argu
     __syncthreads();
     // about one (tile pair, part) pair per wave of the pair kernel, i.e. kBmJobRows jobs per wave
     const uint32_t waves = (uint32_t)(T->pairs_groups > 0 ? T->pairs_groups : 256) * kBmWavesPerCu;
-#ifndef LD_BM_P_FACTOR
-#define LD_BM_P_FACTOR 8
-#endif
-    uint32_t P = (uint32_t)(((unsigned long long)s_total * LD_BM_P_FACTOR / waves + 63u) / 64u * 64u);
-    const uint32_t part_cap = T->part_cap ? T->part_cap : (uint32_t)kBmPartEntries;   // (the ANM form of the pair kernel holds 512 entries a job)
-    P = P < 64u ? 64u : P > part_cap ? part_cap : P;
+    const uint32_t P = bm_plan_entries(s_total, waves, T->part_cap);   // (the ANM form of the pair kernel holds fewer entries a job)
     for (uint32_t tp = tid; tp < n_tp; tp += 1024) {
         const uint32_t n = T->tp_count[tp];
         if (n == 0) continue;
@@ -713,51 +701,124 @@ __global__ __launch_bounds__(1024) void dfire_bm_plan(const BmLaunch launch_argu
 // (counting sort in LDS): the launch ends on jobs of a few batches, and rows without a block are never drawn.
 // ---------------------------------------------------------------------------------------------
 constexpr int kBmOrderWaves = 16;
-__global__ __launch_bounds__(kBmOrderWaves * 64) void dfire_bm_census(const BmLaunch launch_arguments) {
+// one (tile pair, part) pair, by one wave: the part's entries [lo, lo + size) of tile pair tp
+__device__ __forceinline__ void bm_census_part(BmArgs *T, uint32_t jd, size_t tp, uint32_t lo, uint32_t P, int lane) {
     static_assert(kBmJobRows == 8, "a job row is one byte of the block mask");
+    const uint32_t n = T->tp_count[tp];
+    const uint32_t size = bm_part_size(n, P), hi = n < lo + size ? n : lo + size;
+    constexpr int kChunks = kBmPartEntries / 64;
+    unsigned long long m[kChunks];
+#pragma unroll
+    for (int k = 0; k < kChunks; k++) {
+        const uint32_t e = lo + (uint32_t)k * 64 + lane;
+        m[k] = e < hi ? T->ent_mask[tp * T->cap + e] : 0ull;
+    }
+    uint32_t items[8], present_lo = 0, present_hi = 0;   // per row; the OR of the masks
+#pragma unroll
+    for (int r = 0; r < 8; r++) items[r] = 0;
+#pragma unroll
+    for (int k = 0; k < kChunks; k++) {
+        present_lo |= (uint32_t)m[k];
+        present_hi |= (uint32_t)(m[k] >> 32);
+#pragma unroll
+        for (int r = 0; r < 8; r++) items[r] += (uint32_t)__popc((uint32_t)(m[k] >> (8 * r)) & 0xffu);
+    }
+    // sums over the wave: two rows to a word (each below 2^14)
+    uint32_t pk[4] = {items[0] | items[1] << 16, items[2] | items[3] << 16, items[4] | items[5] << 16, items[6] | items[7] << 16};
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) pk[q] += (uint32_t)__shfl_xor((int)pk[q], off, 64);
+        present_lo |= (uint32_t)__shfl_xor((int)present_lo, off, 64);
+        present_hi |= (uint32_t)__shfl_xor((int)present_hi, off, 64);
+    }
+    if (lane < 8) {
+        const uint32_t word = lane < 2 ? pk[0] : lane < 4 ? pk[1] : lane < 6 ? pk[2] : pk[3];
+        const uint32_t it = (lane & 1) ? word >> 16 : word & 0xffffu;
+        const uint32_t blocks = (uint32_t)__popc(((lane < 4 ? present_lo : present_hi) >> (8 * (lane & 3))) & 0xffu);
+        T->job_cost[(size_t)jd * kBmJobRows + lane] = it ? it + 96u * blocks + 224u : 0u;
+        // the job's record, whole: what dfire_bm_pairs needs to start on it in ONE load behind its place in the order
+        // (tile pair, first entry, one past its last entry, ligand subtile)
+        reinterpret_cast<uint4 *>(T->job_rec)[(size_t)jd * kBmJobRows + lane] = uint4{(uint32_t)tp, lo, hi, (uint32_t)lane};
+    }
+}
+
+// PLAN: no dfire_bm_plan ran in front (bm_census_plans).  Every workgroup cuts the launch's entries into parts itself, with
+// dfire_bm_plan's arithmetic (bm_plan_entries, bm_part_count): its 1024 threads take 4 consecutive tile pairs each, reduce the
+// entries (-> P), scan the parts, and leave in LDS each tile pair's first (tile pair, part) index; (tile pair, part) pair jd is then
+// part jd - first[tp] of the last tile pair whose first index is <= jd, found by two 64-way looks (a tile pair without entries
+// has no parts and shares its successor's index: never the last).  The list is the scan's order, the same in every workgroup
+// and every launch.  Workgroup 0 leaves the number of pairs and P in job_count for dfire_bm_order and dfire_bm_pairs, behind
+// this kernel's end.  A redundant 11 KB of L2 reads and a few barriers a workgroup, against a kernel of one workgroup and its boundary.
+template <bool PLAN>
+__global__ __launch_bounds__(kBmOrderWaves * 64) void dfire_bm_census(const BmLaunch launch_arguments) {
     BmArgs *T = LD_BM_ARGS;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t n_pairs = T->job_count[0], P = T->job_count[2];
-    for (uint32_t jd = blockIdx.x * kBmOrderWaves + wave; jd < n_pairs; jd += gridDim.x * kBmOrderWaves) {
-        const size_t tp = T->jobs[2 * jd];
-        const uint32_t lo = T->jobs[2 * jd + 1];
-        const uint32_t n = T->tp_count[tp];
-        const uint32_t size = bm_part_size(n, P), hi = n < lo + size ? n : lo + size;
-        constexpr int kChunks = kBmPartEntries / 64;
-        unsigned long long m[kChunks];
+    if constexpr (!PLAN) {
+        const uint32_t n_pairs = T->job_count[0], P = T->job_count[2];
+        for (uint32_t jd = blockIdx.x * kBmOrderWaves + wave; jd < n_pairs; jd += gridDim.x * kBmOrderWaves)
+            bm_census_part(T, jd, T->jobs[2 * jd], T->jobs[2 * jd + 1], P, lane);
+    } else {
+        constexpr int kPer = kBmCensusTilePairs / (kBmOrderWaves * 64);
+        static_assert(kPer * kBmOrderWaves * 64 == kBmCensusTilePairs && kBmCensusTilePairs == 64 * 64, "whole threads; two 64-way looks");
+        __shared__ uint32_t s_first[kBmCensusTilePairs], s_coarse[64], s_sum[2][kBmOrderWaves];
+        const uint32_t n_tp = (uint32_t)(T->m.lig.n_tiles * T->m.rec_n_tiles);
+        uint32_t count[kPer], mine = 0;
 #pragma unroll
-        for (int k = 0; k < kChunks; k++) {
-            const uint32_t e = lo + (uint32_t)k * 64 + lane;
-            m[k] = e < hi ? T->ent_mask[tp * T->cap + e] : 0ull;
+        for (int u = 0; u < kPer; u++) {
+            const uint32_t tp = (uint32_t)tid * kPer + u;
+            count[u] = tp < n_tp ? T->tp_count[tp] : 0u;
+            mine += count[u];
         }
-        uint32_t items[8], present_lo = 0, present_hi = 0;   // per row; the OR of the masks
 #pragma unroll
-        for (int r = 0; r < 8; r++) items[r] = 0;
+        for (int off = 32; off > 0; off >>= 1) mine += (uint32_t)__shfl_xor((int)mine, off, 64);
+        if (lane == 0) s_sum[0][wave] = mine;
+        __syncthreads();
+        uint32_t total = 0;
 #pragma unroll
-        for (int k = 0; k < kChunks; k++) {
-            present_lo |= (uint32_t)m[k];
-            present_hi |= (uint32_t)(m[k] >> 32);
+        for (int w = 0; w < kBmOrderWaves; w++) total += s_sum[0][w];
+        const uint32_t waves = (uint32_t)(T->pairs_groups > 0 ? T->pairs_groups : 256) * kBmWavesPerCu;
+        const uint32_t P = bm_plan_entries(total, waves, T->part_cap);
+        uint32_t parts[kPer], run = 0;
 #pragma unroll
-            for (int r = 0; r < 8; r++) items[r] += (uint32_t)__popc((uint32_t)(m[k] >> (8 * r)) & 0xffu);
+        for (int u = 0; u < kPer; u++) {
+            parts[u] = bm_part_count(count[u], P);
+            run += parts[u];
         }
-        // sums over the wave: two rows to a word (each below 2^14)
-        uint32_t pk[4] = {items[0] | items[1] << 16, items[2] | items[3] << 16, items[4] | items[5] << 16, items[6] | items[7] << 16};
+        uint32_t incl = run;   // inclusive scan of the threads' parts over the wave
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) pk[q] += (uint32_t)__shfl_xor((int)pk[q], off, 64);
-            present_lo |= (uint32_t)__shfl_xor((int)present_lo, off, 64);
-            present_hi |= (uint32_t)__shfl_xor((int)present_hi, off, 64);
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t up = (uint32_t)__shfl_up((int)incl, off, 64);
+            if (lane >= off) incl += up;
         }
-        if (lane < 8) {
-            const uint32_t word = lane < 2 ? pk[0] : lane < 4 ? pk[1] : lane < 6 ? pk[2] : pk[3];
-            const uint32_t it = (lane & 1) ? word >> 16 : word & 0xffffu;
-            const uint32_t blocks = (uint32_t)__popc(((lane < 4 ? present_lo : present_hi) >> (8 * (lane & 3))) & 0xffu);
-            T->job_cost[(size_t)jd * kBmJobRows + lane] = it ? it + 96u * blocks + 224u : 0u;
-            // the job's record, whole: what dfire_bm_pairs needs to start on it in ONE load behind its place in the order
-            // (tile pair, first entry, one past its last entry, ligand subtile)
-            reinterpret_cast<uint4 *>(T->job_rec)[(size_t)jd * kBmJobRows + lane] = uint4{(uint32_t)tp, lo, hi, (uint32_t)lane};
+        if (lane == 63) s_sum[1][wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, n_pairs = 0;
+#pragma unroll
+        for (int w = 0; w < kBmOrderWaves; w++) {
+            const uint32_t v = s_sum[1][w];
+            if (w < wave) before += v;
+            n_pairs += v;
+        }
+        uint32_t first = before + incl - run;
+#pragma unroll
+        for (int u = 0; u < kPer; u++) {
+            s_first[tid * kPer + u] = first;   // (tile pairs beyond n_tp: no parts, first index = n_pairs, beyond every jd)
+            first += parts[u];
+        }
+        if ((tid * kPer) % 64 == 0) s_coarse[tid * kPer / 64] = before + incl - run;
+        __syncthreads();
+        if (blockIdx.x == 0 && tid == 0) {
+            T->job_count[0] = n_pairs;
+            T->job_count[2] = P;
+        }
+        for (uint32_t jd = blockIdx.x * kBmOrderWaves + wave; jd < n_pairs; jd += gridDim.x * kBmOrderWaves) {
+            // s_coarse[g] = first index of tile pair 64 g; both arrays ascend, [0] = 0 <= jd: the lanes that hold are a prefix, never empty
+            const uint32_t g = (uint32_t)__popcll(__ballot(s_coarse[lane] <= jd)) - 1u;
+            const uint32_t tp = g * 64u + (uint32_t)__popcll(__ballot(s_first[g * 64u + lane] <= jd)) - 1u;
+            const uint32_t k = jd - s_first[tp];
+            bm_census_part(T, jd, tp, k * bm_part_size(T->tp_count[tp], P), P, lane);
         }
     }
 }
@@ -1844,6 +1905,48 @@ __global__ __launch_bounds__(256) void dfire_bm_gather(const BmLaunch launch_arg
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// dfire_bm_finish: dfire_bm_gather and pose_energy_finish in one kernel, for an energy launch of ONE pass (every row of the batch
+// is a row of this pass).  Eight lanes = row of the pass, as in both.  The f64 sum is dfire_bm_gather's, operation for operation:
+// the lane's strided sum over the ligand tiles, the 4-2-1 tree, + the exact path's sum, x 1 / fix_scale; pose_energy_finish folds
+// that one partial with zeros (0.0 + partial: the same value), then scans the membrane beads and applies the tail
+// (pose_energy_tail.hpp).  By row, pose = bm_pose_of(row): a GSO's list of the glowworms that moved works unchanged.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dfire_bm_finish(const BmLaunch launch_arguments) {
+    static_assert(kFinishLanes == 8, "eight lanes per row, as in dfire_bm_gather");
+    BmArgs *T = LD_BM_ARGS;
+    const int n_lt = T->m.lig.n_tiles;
+    const size_t n_rows = bm_rows(T);
+    const int sub = (int)threadIdx.x & 7;
+    const int rec_words = T->m.rec_flag_words, words = rec_words + T->m.lig.flag_words;
+    TailTables tail;
+    tail.n_rec_groups = T->tail.n_rec_groups;
+    tail.n_lig_groups = T->tail.n_lig_groups;
+    tail.n_membrane = T->tail.n_membrane;
+    tail.rec_group_offsets = T->tail.rec_group_offsets;
+    tail.rec_group_slots = T->tail.rec_group_slots;
+    tail.lig_group_offsets = T->tail.lig_group_offsets;
+    tail.lig_group_slots = T->tail.lig_group_slots;
+    tail.membrane_slots = T->tail.membrane_slots;
+    const size_t rows_per_trip = (size_t)gridDim.x * 32;
+    for (size_t first = (size_t)blockIdx.x * 32; first < n_rows; first += rows_per_trip) {   // (whole waves stay together for the shuffles)
+        const size_t row = first + threadIdx.x / 8;
+        const long long pp = row < n_rows ? bm_pose_of(T, row) : -1;
+        const bool live = pp >= 0;
+        double units = 0.0;
+        if (live)
+            for (int lt = sub; lt < n_lt; lt += 8) units += (double)T->tile_sum[(size_t)lt * T->cap + row];   // [ligand tile][row of the pass]
+#pragma unroll
+        for (int off = 4; off > 0; off >>= 1) units += __shfl_xor(units, off, 64);
+        const uint32_t *rwords = T->flags + (live ? (size_t)pp : 0) * (size_t)words;
+        const int beads = membrane_beads(rwords, tail.n_membrane, tail.membrane_slots, sub, live);
+        if (!live || sub != 0) continue;
+        units += (double)T->exact_fix[row];
+        const double partial = units * (1.0 / T->m.fix_scale);
+        T->energies[(size_t)pp] = pose_energy_tail(0, 0.0 + partial, 0.0, rwords, rec_words, tail, beads);
+    }
+}
+
 }  // namespace
 
 size_t bm_pairs_lds_bytes() { return sizeof(BmShared); }
@@ -1893,8 +1996,12 @@ static unsigned bm_pairs_groups(const BmLaunch &t) {   // persistent: what the c
 
 hipError_t launch_bm_pairs(const BmLaunch &t, hipStream_t stream) {
     if (t.n_poses == 0) return hipSuccess;
-    hipLaunchKernelGGL(dfire_bm_plan, dim3(1), dim3(1024), 0, stream, t);
-    hipLaunchKernelGGL(dfire_bm_census, dim3(128), dim3(kBmOrderWaves * 64), 0, stream, t);
+    if (bm_census_plans((size_t)t.m.rec_n_tiles, (size_t)t.m.lig.n_tiles)) {
+        hipLaunchKernelGGL(dfire_bm_census<true>, dim3(128), dim3(kBmOrderWaves * 64), 0, stream, t);
+    } else {
+        hipLaunchKernelGGL(dfire_bm_plan, dim3(1), dim3(1024), 0, stream, t);
+        hipLaunchKernelGGL(dfire_bm_census<false>, dim3(128), dim3(kBmOrderWaves * 64), 0, stream, t);
+    }
     hipLaunchKernelGGL(dfire_bm_order, dim3(1), dim3(kBmOrderWaves * 64), 0, stream, t);
     const unsigned groups = bm_pairs_groups(t);
     if (t.amp != nullptr) {   // molecules that flex per pose
@@ -1910,6 +2017,13 @@ hipError_t launch_bm_pairs(const BmLaunch &t, hipStream_t stream) {
 hipError_t launch_bm_gather(const BmLaunch &t, hipStream_t stream) {
     if (t.n_poses == 0) return hipSuccess;
     hipLaunchKernelGGL(dfire_bm_gather, dim3((unsigned)std::min<size_t>((t.n_poses + 31) / 32, 8192)), dim3(256), 0, stream, t);   // 8 lanes per row
+    return hipGetLastError();
+}
+
+hipError_t launch_bm_finish(const BmLaunch &t, hipStream_t stream) {
+    if (t.n_poses == 0) return hipSuccess;
+    if (t.energies == nullptr || t.count_mode || t.first != 0) return hipErrorInvalidValue;   // a single-pass energy launch only
+    hipLaunchKernelGGL(dfire_bm_finish, dim3((unsigned)std::min<size_t>((t.n_poses + 31) / 32, 8192)), dim3(256), 0, stream, t);   // 8 lanes per row
     return hipGetLastError();
 }
 

@@ -13,9 +13,12 @@
 //                    boxes, 64x64 and 8x8 box tests; every surviving (ligand tile, receptor tile) pair of a pose becomes one
 //                    ENTRY {row of the pass, 64-bit block mask} appended to that tile pair's list (one global atomic per
 //                    tile pair per wave)
-//   dfire_bm_plan    one workgroup: every tile pair's entries cut into equal parts of at most P entries
-//   dfire_bm_census  one wave per (tile pair, part): per ligand-subtile row the block bits of its entries -> the estimated
-//                    length of the JOB (tile pair, part, row), and the job's 16-byte record
+//   dfire_bm_census  every workgroup first cuts every tile pair's entries into equal parts of at most P entries (a reduction and a
+//                    scan over the tile pairs' counts, in LDS: the first (tile pair, part) index of each tile pair); then one wave
+//                    per (tile pair, part): per ligand-subtile row the block bits of its entries -> the estimated length of the
+//                    JOB (tile pair, part, row), and the job's 16-byte record
+//   dfire_bm_plan    (only a complex of more than kBmCensusTilePairs tile pairs) one workgroup, in front of dfire_bm_census:
+//                    the same cut, listed in `jobs`
 //   dfire_bm_order   one workgroup: the jobs that have any work, longest first (counting sort into classes)
 //   dfire_bm_pairs   persistent workgroups of 4 independent waves (two per CU); a wave takes a job and, for each of its 8
 //                    blocks (a, b): the 64 table rows T[type_i][type_j][.] of the block are staged in the wave's slice of LDS
@@ -28,8 +31,11 @@
 //                    (64-bit fixed point, LDS; the row's address is an instruction constant), integer add.  A flagged cell's
 //                    slot holds a MARKER that names the pair (below).  An (entry, ligand subtile)'s finished sum goes to the
 //                    pose's (row, ligand tile) sum by an integer atomic.  No gather ever leaves the CU.
-//   dfire_bm_gather  eight lanes per row: the row's ligand-tile sums + the exact path's sum -> f64 -> the [pose][1][2]
-//                    partials that pose_energy_finish folds (restraint / membrane tail, src/dfire.rs:347-361)
+//   dfire_bm_finish  (an energy launch of one pass) eight lanes per row: the row's ligand-tile sums + the exact path's sum -> f64
+//                    -> the pose's energy: the restraint / membrane tail of src/dfire.rs:347-361 (pose_energy_tail.hpp), in the
+//                    same kernel -- no partial travels through memory, and the step is one kernel shorter
+//   dfire_bm_gather  (batches of several passes, counting launches, LIGHTDOCK_BM_DEBUG) the same sums -> the [pose][1][2]
+//                    partials (or counts) that pose_energy_finish folds
 //
 // Numerics: records are u = fl32(8 (x - c)); the ligand is posed by an f32 affine map whose error
 // is part of `eps`; a LUT cell (1/16 of a unit of 4 d2) whose interval, widened by eps, holds a bin step or the cutoff is
@@ -50,6 +56,7 @@
 #include <cstdint>
 
 #include "dfire_tiled.hpp"
+#include "pose_energy.hpp"
 
 namespace ld {
 
@@ -123,6 +130,33 @@ constexpr double kBmFixLimit = 1024.0;       // |table value| the fixed-point su
 constexpr int kBmCounters = 8;               // words behind tp_count, zeroed per launch: (tile pair, part) pairs listed, jobs drawn, entries per
                                              // part, jobs listed; behind them kBmCullQueueWords item counters of dfire_bm_cull
 constexpr int kBmCullQueueWords = 256;
+// ---- How a launch's entries are cut into jobs: the arithmetic of dfire_bm_plan, which every workgroup of dfire_bm_census repeats
+// for itself where the tile pairs fit its LDS (below).  One statement of it for both kernels (and the host: tests).
+#ifndef LD_BM_P_FACTOR
+#define LD_BM_P_FACTOR 8
+#endif
+// P, the entries a part holds at most: about one (tile pair, part) pair per wave of the pair kernel, i.e. kBmJobRows jobs per wave; a
+// multiple of 64 between 64 and part_cap (0: kBmPartEntries; the ANM form's jobs hold fewer).  `waves` = CUs x kBmWavesPerCu.
+__host__ __device__ inline uint32_t bm_plan_entries(uint32_t total_entries, uint32_t waves, uint32_t part_cap) {
+    uint32_t P = (uint32_t)(((unsigned long long)total_entries * LD_BM_P_FACTOR / waves + 63u) / 64u * 64u);
+    if (!part_cap) part_cap = (uint32_t)kBmPartEntries;
+    return P < 64u ? 64u : P > part_cap ? part_cap : P;
+}
+// entries per part of a tile pair with n entries: its ceil(n / P) parts are EQUAL (a multiple of 64 each; with parts of P and a
+// remainder, a tile pair of 1070 entries -- the average of a 1k4c launch -- was one full job and one of 46 entries that paid
+// the same set-ups for batches a quarter full)
+__host__ __device__ inline uint32_t bm_part_size(uint32_t n, uint32_t P) {
+    const uint32_t parts = (n + P - 1) / P;
+    return parts ? ((n + parts - 1) / parts + 63u) / 64u * 64u : P;
+}
+// parts of a tile pair with n entries (0: none) = ceil(n / bm_part_size(n, P)), which is ceil(n / P): the size is at most P (P is a
+// multiple of 64), so one part fewer would hold less than n, and ceil(n / P) parts of ceil(n / parts) hold n.  One division.
+__host__ __device__ inline uint32_t bm_part_count(uint32_t n, uint32_t P) { return (n + P - 1) / P; }
+// dfire_bm_census plans for itself -- no dfire_bm_plan in front of it, the list of (tile pair, part) pairs is the scan's order --
+// while the tile pairs' first-part indices fit this LDS array: 4 per thread of its 1024 (16 KB; 1k4c has 2 808 tile pairs).
+// Beyond it (a 9 000-atom receptor against 1k4c's ligand: 7 332) dfire_bm_plan lists the pairs in `jobs` as before.
+constexpr int kBmCensusTilePairs = 4096;
+__host__ __device__ inline bool bm_census_plans(size_t n_rt, size_t n_lt) { return n_rt * n_lt <= (size_t)kBmCensusTilePairs; }
 constexpr int kBmCostClasses = 80;           // jobs are drawn in classes of estimated length, longest first
 // dfire_bm_cull's LDS: the receptor's boxes (one per tile and 8 per tile of 32 bytes) and per wave of the workgroup a hit list
 // -- 14 bytes a hit, room for `hit tiles` poses that reach every receptor tile: a pose adds at most one hit per receptor tile, and
@@ -224,7 +258,8 @@ struct BmLaunch {
     unsigned long long *ent_mask = nullptr;  // [tile pair][cap]
     long long *ent_partial = nullptr;      // [wave of dfire_bm_pairs][kBmPartEntries], fixed point: the partial sums of the wave's CURRENT job, one per entry of the
                                            // part (8 KB a wave that never leave the L2; until round 5 a sparse [tile pair][8][cap] array: 33 M scattered HBM read-modify-writes a launch)
-    uint32_t *jobs = nullptr;              // [(tile pair, part)][2]: tile pair, first entry; written by dfire_bm_plan
+    uint32_t *jobs = nullptr;              // [(tile pair, part)][2]: tile pair, first entry; written by dfire_bm_plan (not used while
+                                           // dfire_bm_census plans for itself: bm_census_plans)
     uint32_t *job_count = nullptr;         // [kBmCounters], zeroed per launch: (tile pair, part) pairs listed, jobs drawn (job_next = job_count + 1),
                                            // entries per part, jobs listed in job_order
     uint32_t *job_next = nullptr;
@@ -244,6 +279,9 @@ struct BmLaunch {
     uint32_t *count_partial = nullptr;     // out: [pose][1] or nullptr
     uint32_t *tested_partial = nullptr;    // out: [pose][1] or nullptr
     uint32_t *exact_partial = nullptr;     // out: [pose][1] or nullptr
+    // dfire_bm_finish only (a single-pass energy launch: the sums go straight to the energies, `partial` is not written)
+    TailTables tail;                       // restraint groups and membrane beads over flag slots (the scorer's)
+    double *energies = nullptr;            // out: [pose]
 };
 
 // ---- The workspace of a block-major batch: THE description (host only).  Everything that reserves, points into or counts
@@ -369,5 +407,6 @@ hipError_t launch_bm_pose(const BmLaunch &t, hipStream_t stream);
 hipError_t launch_bm_cull(const BmLaunch &t, hipStream_t stream);
 hipError_t launch_bm_pairs(const BmLaunch &t, hipStream_t stream);
 hipError_t launch_bm_gather(const BmLaunch &t, hipStream_t stream);
+hipError_t launch_bm_finish(const BmLaunch &t, hipStream_t stream);   // in place of launch_bm_gather + launch_finish_kernel (t.tail, t.energies)
 
 }  // namespace ld

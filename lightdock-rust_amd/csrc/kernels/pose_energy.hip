@@ -23,6 +23,8 @@
 // No MFMA: this is a lookup/reduction, not a contraction.
 #include "pose_energy.hpp"
 
+#include "pose_energy_tail.hpp"
+
 namespace ld {
 
 namespace {
@@ -323,28 +325,8 @@ __global__ __launch_bounds__(kBlockThreads) void pose_energy_pairs(const PairLau
     }
 }
 
-__device__ __forceinline__ bool flag_set(const uint32_t *words, uint32_t slot) {
-    return (words[slot >> 5] >> (slot & 31)) & 1u;
-}
-
-// scoring.rs:21-36 over flag slots
-__device__ double satisfied_fraction(const uint32_t *words, int n_groups, const uint32_t *offsets,
-                                     const uint32_t *slots) {
-    if (n_groups == 0) return 0.0;
-    int hit = 0;
-    for (int g = 0; g < n_groups; g++) {
-        for (uint32_t k = offsets[g]; k < offsets[g + 1]; k++)
-            if (flag_set(words, slots[k])) {
-                hit++;
-                break;
-            }
-    }
-    return (double)hit / (double)n_groups;
-}
-
-// Eight lanes per pose: lane k folds the partials k, k + 8, ... in that order, the eight sums are folded as a
-// fixed tree (the same for every launch), lane 0 applies the tail.
-constexpr int kFinishLanes = 8;
+// Eight lanes per pose (kFinishLanes): lane k folds the partials k, k + 8, ... in that order, the eight sums are folded as a
+// fixed tree (the same for every launch), the lanes share the membrane scan, lane 0 applies the tail (pose_energy_tail.hpp).
 __global__ __launch_bounds__(kBlockThreads) void pose_energy_finish(const FinishLaunch F) {
     const size_t t = (size_t)blockIdx.x * kBlockThreads + threadIdx.x;
     const size_t pose = t / kFinishLanes;
@@ -366,30 +348,10 @@ __global__ __launch_bounds__(kBlockThreads) void pose_energy_finish(const Finish
         s1 += __shfl_xor(s1, d);
         cnt += __shfl_xor(cnt, d);
     }
-    // membrane beads (src/scoring.rs:38-47): the pose's eight lanes share the scan, the count is an integer
     const uint32_t *rwords = F.flags + (live ? pose : 0) * (size_t)(F.rec_flag_words + F.lig_flag_words);
-    int beads = 0;
-    if (live)
-        for (int k = sub; k < F.tail.n_membrane; k += kFinishLanes) beads += flag_set(rwords, F.tail.membrane_slots[k]) ? 1 : 0;
-    if (F.tail.n_membrane > 0)
-        for (int d = 1; d < kFinishLanes; d <<= 1) beads += __shfl_xor(beads, d);
+    const int beads = membrane_beads(rwords, F.tail.n_membrane, F.tail.membrane_slots, sub, live);
     if (!live || sub != 0) return;
-    double score;
-    if (F.method == 0) {
-        score = (s0 * 0.0157 - 4.7) * -1.0;  // src/dfire.rs:347
-    } else {
-        const double total_elec = s0 * 332.0 / 4.0;  // src/dna.rs:513
-        score = (total_elec + s1) * -1.0;            // src/dna.rs:514
-    }
-    const uint32_t *lwords = rwords + F.rec_flag_words;
-    const double pr = satisfied_fraction(rwords, F.tail.n_rec_groups, F.tail.rec_group_offsets, F.tail.rec_group_slots);
-    const double pl = satisfied_fraction(lwords, F.tail.n_lig_groups, F.tail.lig_group_offsets, F.tail.lig_group_slots);
-    double penalty = 0.0;
-    if (F.tail.n_membrane > 0) {  // src/scoring.rs:38-47, src/dfire.rs:355-359
-        const double intersection = (double)beads / (double)F.tail.n_membrane;
-        if (intersection > 0.0) penalty = 999.0 * intersection;
-    }
-    F.energies[pose] = score + pr * score + pl * score - penalty;  // src/dfire.rs:361
+    F.energies[pose] = pose_energy_tail(F.method, s0, s1, rwords, F.rec_flag_words, F.tail, beads);
     if (F.pair_counts) F.pair_counts[pose] = cnt;
 }
 

@@ -1331,11 +1331,14 @@ BmShape BlockMajorPath::shape(size_t n, bool counts, bool debug) const {
     return s;
 }
 
-void BlockMajorPath::run(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, const uint32_t *d_list, const uint32_t *d_count,
-                         const PoseOutputs &out, hipStream_t stream) {
+bool BlockMajorPath::run(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, const uint32_t *d_list, const uint32_t *d_count,
+                         const PoseOutputs &out, const TailTables &tail, double *d_energies, hipEvent_t pairs_done, hipStream_t stream) {
     const bool counts = out.count_partial != nullptr;
     const char *dbg = std::getenv("LIGHTDOCK_BM_DEBUG");
     const BmShape s = shape(n, counts, dbg != nullptr);
+    // One pass, energies only: the sums go straight to the energies (dfire_bm_finish).  Several passes (two streams), a counting
+    // launch in front, or the diagnostics keep dfire_bm_gather and the caller's pose_energy_finish.
+    const bool fused = s.sets == 1 && n <= s.cap && !counts && !dbg;
     const BmLayout layout = bm_layout(s);
     if (dbg) ws_.reserve(layout);   // (the debug words are the one region reserve() leaves out)
     BmLaunch t;
@@ -1352,6 +1355,8 @@ void BlockMajorPath::run(size_t n, const double *d_poses, size_t stride, const u
     t.count_partial = out.count_partial;
     t.tested_partial = out.tested_partial;
     t.exact_partial = out.exact_partial;
+    t.tail = tail;
+    t.energies = d_energies;
     if (s.anm) t.part_cap = (uint32_t)kBmAnmPartEntries;
     if (const char *e = std::getenv("LIGHTDOCK_BM_PART_CAP")) {   // A/B: jobs of fewer entries than the LDS has room for (a multiple of 64)
         const long v = std::atol(e);
@@ -1385,7 +1390,12 @@ void BlockMajorPath::run(size_t n, const double *d_poses, size_t stride, const u
             hip_check(launch_bm_pose(t, st), "launch dfire_bm_pose");
             hip_check(launch_bm_cull(t, st), "launch dfire_bm_cull");
             hip_check(launch_bm_pairs(t, st), "launch dfire_bm_pairs");
-            hip_check(launch_bm_gather(t, st), "launch dfire_bm_gather");
+            if (fused) {
+                if (pairs_done) hip_check(hipEventRecord(pairs_done, st), "hipEventRecord");
+                hip_check(launch_bm_finish(t, st), "launch dfire_bm_finish");
+            } else {
+                hip_check(launch_bm_gather(t, st), "launch dfire_bm_gather");
+            }
         }
     }
     if (two_lanes) {
@@ -1405,6 +1415,7 @@ void BlockMajorPath::run(size_t n, const double *d_poses, size_t stride, const u
             std::fclose(f);
         }
     }
+    return fused;
 }
 
 Scorer::~Scorer() {
@@ -1426,7 +1437,7 @@ uint64_t Scorer::workspace_generation() const {
     return g + (bm_ ? bm_->generation() : 0) + (packed_ ? packed_->generation() : 0);
 }
 
-size_t Scorer::partials_per_pose() const {  // (dfire_bm_gather leaves one partial per pose)
+size_t Scorer::partials_per_pose() const {  // (dfire_bm_gather leaves one partial per pose; dfire_bm_finish none, the room stays)
     return bm_ ? 1 : packed_ ? packed_->partials_per_pose() : all_pairs_->partials_per_pose();
 }
 
@@ -1490,9 +1501,10 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
         }
         hip_check(hipEventRecord(events_[events_used_].first, stream_), "hipEventRecord");
     }
+    bool finished = false;   // the route wrote the energies itself
     switch (route_) {
     case PairRoute::block_major:
-        bm_->run(n, d_poses, stride, d_active, d_list, d_count, out, stream_);
+        finished = bm_->run(n, d_poses, stride, d_active, d_list, d_count, out, tail_, d_energies, timing ? events_[events_used_].second : nullptr, stream_);
         break;
     case PairRoute::packed:
         packed_->run(n, d_poses, stride, d_active, d_list, d_count, out, stream_);
@@ -1502,10 +1514,11 @@ void Scorer::energy_batch_device(size_t n, const double *d_poses, size_t stride,
         break;
     }
     if (timing) {
-        hip_check(hipEventRecord(events_[events_used_].second, stream_), "hipEventRecord");
+        if (!finished) hip_check(hipEventRecord(events_[events_used_].second, stream_), "hipEventRecord");   // (a fused launch recorded it in front of its tail)
         events_used_++;
     }
 
+    if (finished) return;
     FinishLaunch f;
     f.method = method_;
     f.n_chunks = (int)partials_per_pose();

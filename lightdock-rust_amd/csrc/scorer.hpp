@@ -194,9 +194,13 @@ class BlockMajorPath {
     // the workspace of a batch of n poses (no allocation in a following run() of that size)
     void reserve(size_t n, bool counts) { ws_.reserve(bm_layout(shape(n, counts, false))); }
     // One batch: passes of at most pass_poses(n) poses, each dfire_bm_pose .. dfire_bm_gather, on `stream` (and, two passes in
-    // flight, the path's second stream, joined before returning).  Leaves one partial per pose in `partial`.
-    void run(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, const uint32_t *d_list, const uint32_t *d_count,
-             const PoseOutputs &out, hipStream_t stream);
+    // flight, the path's second stream, joined before returning).  Leaves one partial per pose in `partial` and returns false:
+    // pose_energy_finish is the caller's.  A batch of ONE pass that wants no pair counts (and no LIGHTDOCK_BM_DEBUG) ends in
+    // dfire_bm_finish instead of dfire_bm_gather: the energies are written to `d_energies` with the scorer's `tail`, `partial`
+    // is not, and run() returns true -- the step is one kernel shorter.  `pairs_done` (or nullptr) is then recorded in front of
+    // dfire_bm_finish: the caller's timing brackets the pair kernels and not the tail, as it does around an unfused batch.
+    bool run(size_t n, const double *d_poses, size_t stride, const uint8_t *d_active, const uint32_t *d_list, const uint32_t *d_count,
+             const PoseOutputs &out, const TailTables &tail, double *d_energies, hipEvent_t pairs_done, hipStream_t stream);
     uint64_t generation() const { return ws_.generation(); }
     uint32_t quiet_subtiles() const { return quiet_subtiles_; }
 

@@ -8,7 +8,7 @@ import os
 import sys
 
 out = sys.argv[1]
-KERNELS = ("dfire_bm_pairs<false", "dfire_bm_cull<false", "dfire_bm_gather", "dfire_bm_pose", "dfire_bm_plan", "dfire_bm_census", "dfire_bm_order",
+KERNELS = ("dfire_bm_pairs<false", "dfire_bm_cull<false", "dfire_bm_finish", "dfire_bm_gather", "dfire_bm_pose", "dfire_bm_plan", "dfire_bm_census", "dfire_bm_order",
            "dfire_packed_pairs<false", "pose_energy_pairs<1", "pose_energy_pairs<0", "gso_movement_phase",
            "pose_energy_finish", "dfire_packed_prepare")
 
@@ -35,12 +35,13 @@ for p in glob.glob(os.path.join(out, "trace", "*", "*kernel_stats.csv")):
     for i, r in enumerate(csv.DictReader(open(p))):
         if i < 11:
             print("  %-84s calls %5s avg %12.1f ns  %6s %%" % (r["Name"][:84], r["Calls"], float(r["AverageNs"]), r["Percentage"]))
-    # the block-major K1 is seven kernels; bench.py's HIP events bracket all of them (`roofline.kernel_ms`)
+    # the block-major K1 is six kernels (a batch of several passes: eight, with dfire_bm_plan and dfire_bm_gather + pose_energy_finish
+    # in dfire_bm_finish's place); bench.py's HIP events bracket all of them (`roofline.kernel_ms`)
     rows = list(csv.DictReader(open(p)))
     bm = [r for r in rows if "dfire_bm_" in r["Name"] and "<true>" not in r["Name"]]
     if bm:
         calls = max(int(r["Calls"]) for r in bm if "pairs" in r["Name"])
-        print("  block-major K1 (pose + cull + plan + census + order + pairs + gather), sum of the average durations: %.1f ns over %d launches of the sequence"
+        print("  block-major K1 (pose + cull + census + order + pairs + finish), sum of the average durations: %.1f ns over %d launches of the sequence"
               % (sum(float(r["TotalDurationNs"]) for r in bm) / calls, calls))
 try:
     b = json.load(open(os.path.join(out, "bench_traced.json")))
@@ -58,8 +59,8 @@ for kern, c in allc.items():
         lo = (c["FETCH_SIZE"] + c["WRITE_SIZE"]) * 1024
         hi = (2 * c["FETCH_SIZE"] + c["WRITE_SIZE"]) * 1024
         # profiles/r04_fetch_size_calibration.txt: coalesced reads are 128-byte requests counted as 64 (x 2); the random 8-byte
-        # reads of dfire_bm_gather are one request each, counted as 64 bytes: taken as reported
-        best = lo if kern.startswith("dfire_bm_gather") else hi
+        # reads of dfire_bm_gather / dfire_bm_finish are one request each, counted as 64 bytes: taken as reported
+        best = lo if kern.startswith(("dfire_bm_gather", "dfire_bm_finish")) else hi
         print("  HBM bytes per launch: %.4g (as reported) .. %.4g (FETCH_SIZE x2 gfx950 correction); calibrated for this kernel's access pattern: %.4g" % (lo, hi, best))
         print("  traffic_json hbm_bytes_per_launch %.0f" % best)
     if "SQ_INSTS_VALU" in c:

@@ -57,7 +57,7 @@ for wdir in sorted(glob.glob(os.path.join(src, "*"))):
         if v is not None:
             entry[field] = v
     entry["valu_source"] = "SQ_INSTS_VALU (wave-level vector instructions) per launch of %s, same file" % (
-        "the block-major sequence (pose, cull, plan, census, order, pairs, gather)" if kernel.startswith("dfire_bm") else kernel)
+        "the block-major sequence (pose, cull, census, order, pairs, finish)" if kernel.startswith("dfire_bm") else kernel)
     entry["binding"] = "valu-issue"
     if entry.get("lds_busy_cycles_per_launch"):
         entry["lds_bank_conflict_share"] = entry.get("lds_bank_conflict_cycles_per_launch", 0.0) / entry["lds_busy_cycles_per_launch"]
