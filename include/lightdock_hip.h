@@ -509,6 +509,58 @@ int ld_complex_contacts(ld_complex *c, size_t n, const double *poses, size_t str
                         uint32_t *rec_bits /* n x ceil(n_rec_res / 32) */,
                         uint32_t *lig_bits /* n x ceil(n_lig_res / 32) */);
 
+/* Clustering by common contacts: models grouped by what their interface is made of -- the fraction of common contacts
+ * (FCC) of HADDOCK's cluster_fcc.py -- and a CONSRANK-style consensus score, how often a model's residue pairs recur over
+ * all the models.  This library's own rule, modelled on those two; no byte compatibility with an outside tool is claimed.
+ * Everything is integer arithmetic, so a result is the same bits whatever the batch or the schedule.
+ *   Pair set of a pose: residues, posing, rounding and the atom test are exactly those of "Interface contacts" (posed f64,
+ *     integer thousandths, C = llrint(cutoff * 1000), 1 <= C <= 30000, d^2 <= C^2 in exact integers, all atoms count).
+ *     P_i is the set of keys r * n_lig_res + l, r a receptor and l a ligand residue index; a key is in the set when some
+ *     atom of r touches some atom of l.  Keys are uint32_t: a complex with n_rec_res * n_lig_res >= 2^32 is refused.  A
+ *     pose's keys are emitted in ascending order.  The projection of P_i onto either side is, word for word, that pose's
+ *     row of ld_complex_contacts at the same cutoff.
+ *   Common contacts: s_i = |P_i|, c_ij = |P_i & P_j|.
+ *   Neighbours: T = llrint(threshold * 1000), 1 <= T <= 1000.  For i != j, poses i and j are neighbours iff s_i > 0,
+ *     s_j > 0 and 1000 * c_ij >= T * max(s_i, s_j) in 64-bit integers: FCC with strictness 1, a symmetric relation.  A
+ *     pose with an empty set has no neighbours.
+ *   Clusters: all poses start alive.  Until no pose is alive: (1) for every alive pose d_i = 1 + the number of its alive
+ *     neighbours; (2) the centre is the alive pose with the largest d, ties to the larger scoring, then to the smaller
+ *     index; (3) if that d < min_size (min_size >= 1) the repetition stops and every pose still alive gets cluster -1;
+ *     (4) otherwise the centre and its alive neighbours form the next cluster and die.  Clusters are numbered in creation
+ *     order, so their sizes never increase.
+ *   Outputs, as ld_complex_cluster_ranked's: cluster_of (n, -1 for unclustered), centres (n, input indices in creation
+ *     order, -1 after the last), n_clusters (one word).
+ *   Consensus: freq[k] is the number of poses whose set holds key k; consensus_i is the sum of freq[k] over k in P_i.  The
+ *     fraction is consensus_i / (s_i * n), and 0 for an empty set: the caller's arithmetic.
+ * LD_ERR_INVALID, nothing written: everything ld_complex_contacts refuses; a non-finite scoring; a threshold that is NaN or
+ * whose T is outside 1 .. 1000; min_size == 0; for the entries that take sets from the caller, offsets that do not start
+ * at 0 or do not ascend and keys that are not strictly ascending within a set; a cap below the number of keys; a list
+ * beyond the workspace bounds: more than 65536 sets to cluster (the neighbour bits, n^2 / 8 B, stay within 512 MiB), more
+ * than 16384 sets for ld_fcc_common (n x n words within 1 GiB), more than 4194304 poses for ld_complex_pair_contacts --
+ * these three are checked before the list is read, so an absurd n is an error, not a crash -- and sets whose bit rows,
+ * n x ceil(U / 32) words for U distinct keys over the list, would exceed 1 GiB.  n == 0 is LD_OK and sets *n_clusters = 0
+ * (offsets[0] = 0, *total_out = 0).  Further device workspace: a bit a key of the span between the smallest and the
+ * largest key (at most 528 MiB); per workgroup in flight the slot of ld_complex_contacts plus a bit a residue pair, at
+ * most 1024 slots and 256 MiB (or one slot). */
+/* offsets: n + 1 words, the keys of pose i are keys[offsets[i] .. offsets[i + 1]).  keys == NULL: offsets and the total
+ * only; otherwise cap is the room in keys.  Any output may be NULL.  ld_complex_last_kernel_ms then reports this call. */
+int ld_complex_pair_contacts(ld_complex *c, size_t n, const double *poses, size_t stride, double cutoff /* 5.0 */,
+                             uint32_t *offsets /* n + 1 */, uint32_t *keys /* cap, or NULL */, size_t cap,
+                             size_t *total_out);
+/* The two steps in one call, the sets never leaving the device; the outputs equal ld_fcc_cluster's on
+ * ld_complex_pair_contacts's sets word for word.  set_sizes and consensus may be NULL.  ld_complex_last_kernel_ms then
+ * reports this call from its first launch to its last. */
+int ld_complex_cluster_fcc(ld_complex *c, size_t n, const double *poses, size_t stride, const double *scoring,
+                           double cutoff /* 5.0 */, double threshold /* 0.6 */, uint32_t min_size /* 1 */,
+                           int32_t *cluster_of /* n */, int32_t *centres /* n */, uint32_t *n_clusters /* 1 */,
+                           uint32_t *set_sizes /* n, or NULL */, uint64_t *consensus /* n, or NULL */);
+/* The kernels on the caller's sets; no complex is needed.  common: c_ij, n x n, the diagonal s_i. */
+int ld_fcc_common(size_t n, const uint32_t *offsets /* n + 1 */, const uint32_t *keys, uint32_t *common /* n x n */);
+int ld_fcc_cluster(size_t n, const uint32_t *offsets /* n + 1 */, const uint32_t *keys, const double *scoring /* n */,
+                   double threshold, uint32_t min_size, int32_t *cluster_of /* n */, int32_t *centres /* n */,
+                   uint32_t *n_clusters /* 1 */, uint64_t *consensus /* n, or NULL */);
+int ld_fcc_last_kernel_ms(double *ms_out); /* device time of the calling thread's last ld_fcc_common / ld_fcc_cluster (HIP events) */
+
 /* Model quality: how close every pose is to a reference (bound) complex -- fnat, i-RMSD, L-RMSD, from which DockQ and
  * the CAPRI class follow by host arithmetic (lightdock-rust_amd/assess.py).  The rule is this library's own, modelled
  * on CAPRI / DockQ; no byte compatibility with any outside tool is claimed.

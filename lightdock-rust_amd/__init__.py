@@ -197,6 +197,11 @@ def load_library():
     lib.ld_complex_residue_id.argtypes = [vp, C.c_int, sz, C.c_char_p, sz]
     lib.ld_complex_residue_of_atom.argtypes = [vp, C.c_int, vp]
     lib.ld_complex_contacts.argtypes = [vp, sz, vp, sz, C.c_double, vp, vp]
+    lib.ld_complex_pair_contacts.argtypes = [vp, sz, vp, sz, C.c_double, vp, vp, sz, C.POINTER(sz)]
+    lib.ld_complex_cluster_fcc.argtypes = [vp, sz, vp, sz, vp, C.c_double, C.c_double, C.c_uint32, vp, vp, vp, vp, vp]
+    lib.ld_fcc_common.argtypes = [sz, vp, vp, vp]
+    lib.ld_fcc_cluster.argtypes = [sz, vp, vp, vp, C.c_double, C.c_uint32, vp, vp, vp, vp]
+    lib.ld_fcc_last_kernel_ms.argtypes = [dp]
     lib.ld_sasa_directions.argtypes = [vp]
     lib.ld_complex_sasa_radii.argtypes = [vp, C.c_int, vp]
     lib.ld_complex_sasa.argtypes = [vp, sz, vp, sz, C.c_double, vp, vp, vp]
@@ -676,7 +681,8 @@ class GSO:
 
 class Complex:
     """LightDock's analysis of a run (ld_complex_*): posed coordinates, BSAS clustering of whole swarms and of one ranked
-    list across swarms, top-model PDBs, per-pose interface contacts, solvent-accessible and buried surface."""
+    list across swarms, top-model PDBs, per-pose interface contacts and residue-pair sets, clustering by common contacts, solvent-accessible
+    and buried surface."""
 
     def __init__(self, receptor_pdb, ligand_pdb, rec_nmodes=None, rec_num_anm=0, lig_nmodes=None, lig_num_anm=0):
         self.lib = load_library()
@@ -778,6 +784,40 @@ class Complex:
             out[k] = bits[:, :self.num_residues(side)].astype(bool)
         return out
 
+    def pair_contacts(self, poses, cutoff=5.0):
+        """(n, >= pose_len) poses -> (offsets (n + 1,), keys): the residue pairs of every pose in contact within `cutoff`,
+        pose i's as the ascending keys r * num_residues(1) + l in keys[offsets[i]:offsets[i + 1]]
+        (ld_complex_pair_contacts: a count call, then the keys)."""
+        poses = _f64(poses)
+        if poses.ndim != 2:
+            raise ValueError("poses must be (n, pose_len)")
+        n, total = poses.shape[0], C.c_size_t()
+        offsets = np.zeros(n + 1, dtype=np.uint32)
+        _check(self.lib.ld_complex_pair_contacts(self._h, n, _ptr(poses), poses.shape[1], C.c_double(cutoff), _ptr(offsets), None, 0,
+                                                 C.byref(total)))
+        keys = np.zeros(total.value, dtype=np.uint32)
+        if total.value:
+            _check(self.lib.ld_complex_pair_contacts(self._h, n, _ptr(poses), poses.shape[1], C.c_double(cutoff), _ptr(offsets), _ptr(keys),
+                                                     keys.size, C.byref(total)))
+        return offsets, keys
+
+    def cluster_fcc(self, poses, scoring, cutoff=5.0, threshold=0.6, min_size=1):
+        """One list of poses clustered by the fraction of common contacts (ld_complex_cluster_fcc; lightdock_hip.h,
+        "Clustering by common contacts"): poses (n, >= pose_len), scoring (n,) -> dict of cluster_of (n,) in input order
+        (-1: unclustered), centres (n,) input indices in creation order (-1 after the last), n_clusters, set_sizes (n,),
+        consensus (n,) uint64; fcc_consensus_fraction() turns the last two into fractions."""
+        poses, scoring = _f64(poses), _f64(scoring)
+        if poses.ndim != 2 or scoring.shape != poses.shape[:1]:
+            raise ValueError("poses must be (n, pose_len), scoring (n,)")
+        n, k = scoring.shape[0], np.zeros(1, dtype=np.uint32)
+        out = {"cluster_of": np.full(n, -1, dtype=np.int32), "centres": np.full(n, -1, dtype=np.int32),
+               "set_sizes": np.zeros(n, dtype=np.uint32), "consensus": np.zeros(n, dtype=np.uint64)}
+        _check(self.lib.ld_complex_cluster_fcc(self._h, n, _ptr(poses), poses.shape[1], _ptr(scoring), C.c_double(cutoff),
+                                               C.c_double(threshold), min_size, _ptr(out["cluster_of"]), _ptr(out["centres"]), _ptr(k),
+                                               _ptr(out["set_sizes"]), _ptr(out["consensus"])))
+        out["n_clusters"] = int(k[0])
+        return out
+
     def sasa_radii(self, side):
         """The radius of every atom of a side (0 receptor, 1 ligand) in thousandths of an A, 0 for an atom that takes no
         part in the surface: a hydrogen, a deuterium, a membrane bead (ld_complex_sasa_radii)."""
@@ -836,6 +876,54 @@ class Complex:
         n_native = self.reference_counts()["native_pairs"]
         _check(self.lib.ld_complex_assess(self._h, n, _ptr(poses), poses.shape[1], _ptr(kept), _ptr(lrmsd), _ptr(irmsd)))
         return {"kept": kept, "fnat": kept / float(n_native), "lrmsd": lrmsd, "irmsd": irmsd}
+
+
+def _sets(offsets, keys):
+    offsets, keys = np.ascontiguousarray(offsets, dtype=np.uint32), np.ascontiguousarray(keys, dtype=np.uint32)
+    if offsets.ndim != 1 or offsets.size < 1 or keys.ndim != 1:
+        raise ValueError("offsets must be (n + 1,), keys (total,)")
+    if keys.size < int(offsets.max()):
+        raise ValueError("offsets point beyond the keys")
+    return offsets, keys
+
+
+def fcc_common(offsets, keys):
+    """Sets in CSR form (set i: the strictly ascending keys[offsets[i]:offsets[i + 1]]) -> (n, n) uint32, the number of
+    keys every two sets share, the diagonal their sizes (ld_fcc_common)."""
+    offsets, keys = _sets(offsets, keys)
+    n = offsets.size - 1
+    out = np.zeros((n, n), dtype=np.uint32)
+    _check(load_library().ld_fcc_common(n, _ptr(offsets), _ptr(keys), _ptr(out)))
+    return out
+
+
+def fcc_cluster(offsets, keys, scoring, threshold=0.6, min_size=1):
+    """Complex.cluster_fcc's rule on the caller's sets (ld_fcc_cluster) -> dict of cluster_of, centres, n_clusters,
+    set_sizes, consensus."""
+    offsets, keys = _sets(offsets, keys)
+    scoring = _f64(scoring)
+    n, k = offsets.size - 1, np.zeros(1, dtype=np.uint32)
+    if scoring.shape != (n,):
+        raise ValueError("scoring must be (n,)")
+    out = {"cluster_of": np.full(n, -1, dtype=np.int32), "centres": np.full(n, -1, dtype=np.int32),
+           "consensus": np.zeros(n, dtype=np.uint64)}
+    _check(load_library().ld_fcc_cluster(n, _ptr(offsets), _ptr(keys), _ptr(scoring), C.c_double(threshold), min_size,
+                                         _ptr(out["cluster_of"]), _ptr(out["centres"]), _ptr(k), _ptr(out["consensus"])))
+    out["n_clusters"] = int(k[0])
+    out["set_sizes"] = np.diff(offsets.astype(np.int64)).astype(np.uint32)
+    return out
+
+
+def fcc_consensus_fraction(consensus, set_sizes):
+    """consensus_i / (s_i * n), and 0 for an empty set: how often, on average, a pose's pairs recur over the list."""
+    consensus, sizes = np.asarray(consensus, dtype=np.float64), np.asarray(set_sizes, dtype=np.float64)
+    return np.where(sizes > 0, consensus / np.maximum(sizes * max(1, sizes.size), 1.0), 0.0)
+
+
+def fcc_last_kernel_ms():
+    ms = C.c_double()
+    _check(load_library().ld_fcc_last_kernel_ms(C.byref(ms)))
+    return ms.value
 
 
 SASA_POINTS = 128

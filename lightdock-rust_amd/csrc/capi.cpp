@@ -13,6 +13,7 @@
 
 #include "anm.hpp"
 #include "complex.hpp"
+#include "fcc.hpp"
 #include "gso.hpp"
 #include "host/cli.hpp"
 #include "host/docking_model.hpp"
@@ -545,6 +546,34 @@ int ld_complex_contacts(ld_complex *c, size_t n, const double *poses, size_t str
     return guarded([&] {
         if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
         c->impl.contacts(n, poses, stride, cutoff, rec_bits, lig_bits);
+    });
+}
+int ld_complex_pair_contacts(ld_complex *c, size_t n, const double *poses, size_t stride, double cutoff, uint32_t *offsets, uint32_t *keys,
+                             size_t cap, size_t *total_out) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.pair_contacts(n, poses, stride, cutoff, offsets, keys, cap, total_out);
+    });
+}
+int ld_complex_cluster_fcc(ld_complex *c, size_t n, const double *poses, size_t stride, const double *scoring, double cutoff,
+                           double threshold, uint32_t min_size, int32_t *cluster_of, int32_t *centres, uint32_t *n_clusters,
+                           uint32_t *set_sizes, uint64_t *consensus) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.cluster_fcc(n, poses, stride, scoring, cutoff, threshold, min_size, cluster_of, centres, n_clusters, set_sizes, consensus);
+    });
+}
+int ld_fcc_common(size_t n, const uint32_t *offsets, const uint32_t *keys, uint32_t *common) {
+    return guarded([&] { ld::fcc_common_host(n, offsets, keys, common); });
+}
+int ld_fcc_cluster(size_t n, const uint32_t *offsets, const uint32_t *keys, const double *scoring, double threshold, uint32_t min_size,
+                   int32_t *cluster_of, int32_t *centres, uint32_t *n_clusters, uint64_t *consensus) {
+    return guarded([&] { ld::fcc_cluster_host(n, offsets, keys, scoring, threshold, min_size, cluster_of, centres, n_clusters, consensus); });
+}
+int ld_fcc_last_kernel_ms(double *ms_out) {
+    return guarded([&] {
+        if (!ms_out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        *ms_out = ld::fcc_last_kernel_ms();
     });
 }
 int ld_sasa_directions(int32_t *out) {

@@ -19,7 +19,8 @@ void check_modes(const char *side, const double *modes, size_t len, size_t num_a
                                         " mode values, expected num_anm x atoms x 3 = " + std::to_string(num_anm * n_atoms * 3));
 }
 
-// C = llrint(cutoff * 1000), 1 .. 30000, of a contact cutoff in A (lightdock_hip.h, "Interface contacts").
+}  // namespace
+
 long long cutoff_thousandths(double cutoff, const char *message) {
     const double scaled = cutoff * 1000.0;
     if (!(scaled > 0.0 && scaled < 30001.0)) throw Error(LD_ERR_INVALID, message);
@@ -27,8 +28,6 @@ long long cutoff_thousandths(double cutoff, const char *message) {
     if (C < 1 || C > 30000) throw Error(LD_ERR_INVALID, message);
     return C;
 }
-
-}  // namespace
 
 uint32_t sasa_radius(const char *line, size_t len) {
     static const struct {

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "device_memory.hpp"
+#include "fcc.hpp"
 #include "host/pdb_file.hpp"
 #include "kernels/assess.hpp"
 #include "kernels/cluster.hpp"
@@ -15,6 +16,9 @@
 #include "kernels/sasa.hpp"
 
 namespace ld {
+
+// C = llrint(cutoff * 1000), 1 .. 30000, of a contact cutoff in A (lightdock_hip.h, "Interface contacts"); `message` otherwise.
+long long cutoff_thousandths(double cutoff, const char *message);
 
 class Complex {
    public:
@@ -37,6 +41,12 @@ class Complex {
     void cluster_ranked(size_t n, const double *poses, size_t stride, const double *scoring, double cutoff, int atoms,
                         int32_t *cluster_of, int32_t *representatives, uint32_t *n_clusters);
     void contacts(size_t n, const double *poses, size_t stride, double cutoff, uint32_t *rec_bits, uint32_t *lig_bits);
+    // Clustering by common contacts (lightdock_hip.h, "Clustering by common contacts"; fcc.cpp)
+    void pair_contacts(size_t n, const double *poses, size_t stride, double cutoff, uint32_t *offsets, uint32_t *keys, size_t cap,
+                       size_t *total_out);
+    void cluster_fcc(size_t n, const double *poses, size_t stride, const double *scoring, double cutoff, double threshold,
+                     uint32_t min_size, int32_t *cluster_of, int32_t *centres, uint32_t *n_clusters, uint32_t *set_sizes,
+                     uint64_t *consensus);
     void write_pdb(const double *pose, const char *path);
     // Solvent-accessible surface (lightdock_hip.h, "Solvent-accessible surface")
     void sasa_radii(int side, uint32_t *radii_out) const;  // thousandths, 0 for an atom that takes no part
@@ -55,6 +65,8 @@ class Complex {
     void upload_poses(size_t n, const double *poses, size_t stride);  // n rows of `stride` doubles, copied as they are
     void pose_all(size_t n, const double *poses, size_t stride, double *out);  // all atoms of n poses, unrounded
     void finish_timed(const int *d_overflow, const char *what, const char *overflow_message);
+    void check_pair_keys() const;
+    FccCluster::Sets pair_sets(size_t n, const double *poses, size_t stride, long long C, bool fill, size_t cap, int **d_overflow_out);
     void destroy();
 
     PdbFile rec_, lig_;
@@ -77,6 +89,8 @@ class Complex {
     } ref_;
     DeviceBuffer d_ref_atoms_, d_ref_xyz_, d_ref_native_;  // behind ref_.dev: a later reference reuses them
     DeviceBuffer d_poses_, d_scores_, d_out_, d_ws_, d_ids_;
+    DeviceBuffer d_pair_keys_;  // the keys of pair_sets
+    FccCluster fcc_;            // cluster_fcc's workspace
     DeviceBuffer d_ranked_ws_;  // cluster_ranked's resident thousandths (up to kRankedWorkspaceBytes), apart from d_ws_
     hipStream_t stream_ = nullptr;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;

@@ -173,39 +173,7 @@ unsigned grid_for(size_t total) {
 
 constexpr int kCoordBound = 1000000000;        // thousandths: +-1.0e6 A
 
-// Box b of a pose is box[k * n_boxes + b], k = min x, y, z, max x, y, z: consecutive lanes read consecutive words.
-// b: residues (receptor, then ligand), receptor groups, ligand groups.
-struct Box {
-    int lo[3], hi[3];
-};
-
-__device__ __forceinline__ Box load_box(const int *box, int n_boxes, int b) {
-    Box v;
-    for (int k = 0; k < 3; k++) {
-        v.lo[k] = box[k * n_boxes + b];
-        v.hi[k] = box[(3 + k) * n_boxes + b];
-    }
-    return v;
-}
-
-__device__ __forceinline__ void store_box(int *box, int n_boxes, int b, const Box &v) {
-    for (int k = 0; k < 3; k++) {
-        box[k * n_boxes + b] = v.lo[k];
-        box[(3 + k) * n_boxes + b] = v.hi[k];
-    }
-}
-
-// The gap between two intervals on one axis (0 when they overlap), clamped like a difference.
-__device__ __forceinline__ uint32_t clamped_gap(int lo_a, int hi_a, int lo_b, int hi_b) {
-    return min((uint32_t)max(max(lo_a - hi_b, lo_b - hi_a), 0), kAxisClamp);
-}
-
-// Exact: every atom pair of the two boxes is at least the gap apart on each axis, so a box distance above C (which an
-// axis gap above C implies) leaves no pair within C.  Nothing is padded.
-__device__ __forceinline__ bool boxes_within(const Box &a, const Box &b, uint32_t C2) {
-    return square_sum(clamped_gap(a.lo[0], a.hi[0], b.lo[0], b.hi[0]), clamped_gap(a.lo[1], a.hi[1], b.lo[1], b.hi[1]),
-                      clamped_gap(a.lo[2], a.hi[2], b.lo[2], b.hi[2])) <= C2;
-}
+// The boxes and their exact distance test: kernels/complex_pose.hpp, shared with kernels/fcc.hip.
 
 // 8 waves a SIMD: four workgroups a CU hide the latency of the dependent loads
 __global__ void __launch_bounds__(kContactThreads, 8) complex_contacts(ComplexDevice m, ContactsDevice d, const double *poses,

@@ -1,6 +1,6 @@
-// complex_pose.hpp -- device code the analysis kernels share (kernels/cluster.hip, kernels/assess.hip, kernels/ranked.hip, kernels/sasa.hip):
-// the posing of one atom of a complex, the rounding to the thousandths "%8.3f" prints, the clustering's RMSD test, and the
-// 32-bit contact test on two atoms' thousandths.
+// complex_pose.hpp -- device code the analysis kernels share (kernels/cluster.hip, kernels/assess.hip, kernels/ranked.hip, kernels/sasa.hip, kernels/fcc.hip):
+// the posing of one atom of a complex, the rounding to the thousandths "%8.3f" prints, the clustering's RMSD test, the
+// 32-bit contact test on two atoms' thousandths, and the integer boxes with their exact distance test.
 // Include from a .hip file only.
 // Posing: receptor R_a + sum_m rec_ext[m] rec_mode[m][a]; ligand rotate(q, L_a + sum_m lig_ext[m] lig_mode[m][a]) + t,
 // i.e. the ligand's modes in the ligand frame -- NOT the energy's convention (src/dfire.rs:282-302).  f64, qt.rs order,
@@ -90,6 +90,42 @@ __device__ __forceinline__ uint32_t square_sum(uint32_t x, uint32_t y, uint32_t 
 
 __device__ __forceinline__ bool in_contact(const int4 &a, const int4 &b, uint32_t C2) {
     return square_sum(clamped_abs(a.x - b.x), clamped_abs(a.y - b.y), clamped_abs(a.z - b.z)) <= C2;
+}
+
+// --- residue and group boxes on the thousandths (kernels/cluster.hip, kernels/fcc.hip) ---------------------------------
+
+// Box b of a pose is box[k * n_boxes + b], k = min x, y, z, max x, y, z: consecutive lanes read consecutive words.
+// b: residues (receptor, then ligand), receptor groups, ligand groups.
+struct Box {
+    int lo[3], hi[3];
+};
+
+__device__ __forceinline__ Box load_box(const int *box, int n_boxes, int b) {
+    Box v;
+    for (int k = 0; k < 3; k++) {
+        v.lo[k] = box[k * n_boxes + b];
+        v.hi[k] = box[(3 + k) * n_boxes + b];
+    }
+    return v;
+}
+
+__device__ __forceinline__ void store_box(int *box, int n_boxes, int b, const Box &v) {
+    for (int k = 0; k < 3; k++) {
+        box[k * n_boxes + b] = v.lo[k];
+        box[(3 + k) * n_boxes + b] = v.hi[k];
+    }
+}
+
+// The gap between two intervals on one axis (0 when they overlap), clamped like a difference.
+__device__ __forceinline__ uint32_t clamped_gap(int lo_a, int hi_a, int lo_b, int hi_b) {
+    return min((uint32_t)max(max(lo_a - hi_b, lo_b - hi_a), 0), kAxisClamp);
+}
+
+// Exact: every atom pair of the two boxes is at least the gap apart on each axis, so a box distance above C (which an
+// axis gap above C implies) leaves no pair within C.  Nothing is padded.
+__device__ __forceinline__ bool boxes_within(const Box &a, const Box &b, uint32_t C2) {
+    return square_sum(clamped_gap(a.lo[0], a.hi[0], b.lo[0], b.hi[0]), clamped_gap(a.lo[1], a.hi[1], b.lo[1], b.hi[1]),
+                      clamped_gap(a.lo[2], a.hi[2], b.lo[2], b.hi[2])) <= C2;
 }
 
 }  // namespace
