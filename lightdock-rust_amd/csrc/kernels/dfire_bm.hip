@@ -599,7 +599,9 @@ __global__ __launch_bounds__(kBmCullWaves * 64) void dfire_bm_cull(const BmLaunc
             else if (base + lane < n_rt) {
                 const TiledBox tb = tile_at(base + lane);
                 tile_near = box_gap2(whole, tb) <= (COUNT ? kBmBoxCut : tb.pad0);
+                if constexpr (!ANM) asm volatile("" : : "v"(tb.pad0), "v"(tb.pad1));   // (whole 16-byte reads, as the subtile boxes below)
             }
+            if constexpr (!ANM) asm volatile("" : : "v"(my_tile.pad0), "v"(my_tile.pad1));
             unsigned long long rtmask = __builtin_amdgcn_ballot_w64(tile_near);
             if (rtmask) {
                 // one surviving tile at a time, the next one's subtile boxes loaded while this one's are tested (the last trip loads
@@ -618,6 +620,12 @@ __global__ __launch_bounds__(kBmCullWaves * 64) void dfire_bm_cull(const BmLaunc
 #else
                     const unsigned long long smask = __builtin_amdgcn_ballot_w64(bm_cull_gap2(sub_x, sub_y, sub_z, nb) <= (COUNT ? kBmBoxCut : nb.cut));  // bit = ligand subtile (lane >> 3) * 8 + receptor subtile
 #endif
+                    // The box's spare word is kept alive (no instruction) so that its second half stays ONE 16-byte read: without it the
+                    // compiler narrows that read to ds_read_b96, which the LDS serves in 8 groups of 8 lanes on 32 banks -- 8 cycles, and the
+                    // boxes' 32-byte stride puts subtiles s and s + 4 of a group on the same banks, 16 -- where ds_read_b128 (4 groups of 16
+                    // lanes, 64 banks: the eight boxes of a tile on distinct banks) takes 4.  A step's two reads: 20 LDS cycles -> 8.
+                    // tests/test_host_bm_cull_lds_reads.py holds the built kernel to it.
+                    if constexpr (!ANM) asm volatile("" : : "v"(nb.cut), "v"(nb.unused));
                     if (smask) {   // hit `held` of this ballot stays in lane `held` until the ballot's tiles are done
                         held_lo = (uint32_t)bm_writelane((int)(uint32_t)smask, (int)held, (int)held_lo);
                         held_hi = (uint32_t)bm_writelane((int)(uint32_t)(smask >> 32), (int)held, (int)held_hi);
