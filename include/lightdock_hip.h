@@ -154,6 +154,20 @@ int ld_dfire_packed_lut(int cells_per_unit, double ubound, uint32_t *words_out, 
  *                                cutoff inside the cell's interval (hence r = 15.0 exactly, the reference's read past the row, :338)
  * codes_out: 14592 entries. */
 int ld_dfire_bm_lut(double ubound, double lig_extent, uint8_t *codes_out, double *eps_cells_out);
+/* The record frames the two culled DFIRE routes derive of a complex's coordinates (host-side, no GPU), for tests: the scorer's
+ * own route predicates up to the frame, so a test that needs a frame of a given size asks instead of restating the rule.
+ * anm: the complex flexes (the block-major ANM form keeps room for its deformations).  Either output may be NULL.
+ * rec_types: the receptor's DFIRE types, with which its 8-atom subtiles are laid out as the scorer lays them out
+ * (ld_dfire_tile_layout) and the widest subtile box enters the block-major bound; NULL: no subtile is taken to be wider than the
+ * bound assumes (eps is then ld_dfire_bm_lut's for that frame).
+ *   bm_out[9]      centre x y z (A), ubound (record units of 1/8 A), lig_extent (A), eps (LUT cells), 1.0 if eps < 8 (the
+ *                  block-major route declines the complex otherwise) else 0.0, the widest receptor subtile box's half extent
+ *                  along an axis and its half diagonal (record units, rounded up a little; 0 without rec_types)
+ *   packed_out[8]  centre x y z, kappa (record units per A), ubound (record units), eps (units of 4 d2), LUT cells per unit of
+ *                  4 d2, 1.0 if the pose-major packed route takes the receptor (the all-pairs kernel otherwise), else 0.0
+ * LIGHTDOCK_PACKED_CELLS and LIGHTDOCK_PACKED_EPS_SCALE are read as the scorer reads them. */
+int ld_dfire_route_frames(const double *rec_xyz /* n_rec x 3 */, const uint32_t *rec_types /* n_rec, or NULL */, size_t n_rec,
+                          const double *lig_xyz /* n_lig x 3 */, size_t n_lig, int anm, double *bm_out /* 9 */, double *packed_out /* 8 */);
 /* The fixed-point scale of that kernel (host-side, no GPU): table values enter a pose's sum as rint(v * scale), scale =
  * 2^(44 - e - x), 2^e >= table_vmax, integer adds in any order (the sum src/dfire.rs:325-345 takes in f64).  x makes the sum of
  * one (pose, ligand tile) -- 64 ligand atoms x the receptor atoms within `reach` = cutoff + the tile's radius of its centre --

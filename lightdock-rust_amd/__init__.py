@@ -328,6 +328,23 @@ def dfire_bm_lut(ubound=1024.0, lig_extent=45.0):
     return codes, eps.value
 
 
+def dfire_route_frames(rec_xyz, lig_xyz, anm=False, rec_types=None):
+    """The record frames of the two culled DFIRE routes for a complex's coordinates, see ld_dfire_route_frames in the header:
+    {"bm": dict(centre, ubound, lig_extent, eps, takes, sub_axis, sub_diag), "packed": dict(centre, kappa, ubound, eps, cells,
+    takes)}.  rec_types: the receptor's DFIRE types (its subtiles then enter the block-major bound, as in the scorer)."""
+    rec, lig = _f64(rec_xyz).reshape(-1, 3), _f64(lig_xyz).reshape(-1, 3)
+    types = None if rec_types is None else np.ascontiguousarray(rec_types, dtype=np.uint32)
+    if types is not None and types.shape != (rec.shape[0],):
+        raise ValueError("one DFIRE type per receptor atom")
+    bm, packed = np.zeros(9), np.zeros(8)
+    lib = load_library()
+    lib.ld_dfire_route_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+    _check(lib.ld_dfire_route_frames(_ptr(rec), _ptr(types), rec.shape[0], _ptr(lig), lig.shape[0], 1 if anm else 0, _ptr(bm), _ptr(packed)))
+    return {"bm": dict(centre=bm[:3].copy(), ubound=bm[3], lig_extent=bm[4], eps=bm[5], takes=bool(bm[6]), sub_axis=bm[7], sub_diag=bm[8]),
+            "packed": dict(centre=packed[:3].copy(), kappa=packed[3], ubound=packed[4], eps=packed[5], cells=int(packed[6]),
+                           takes=bool(packed[7]))}
+
+
 def dfire_bm_fix_scale(rec_xyz, reach, table_vmax):
     """(reach count, extra bits, scale) of the block-major kernel's fixed-point sums, see ld_dfire_bm_fix_scale in the header."""
     xyz = _f64(rec_xyz).reshape(-1, 3)

@@ -207,6 +207,43 @@ int ld_dfire_bm_lut(double ubound, double lig_extent, uint8_t *codes_out, double
         if (eps_cells_out) *eps_cells_out = eps;
     });
 }
+int ld_dfire_route_frames(const double *rec_xyz, const uint32_t *rec_types, size_t n_rec, const double *lig_xyz, size_t n_lig, int anm,
+                          double *bm_out, double *packed_out) {
+    return guarded([&] {
+        if (!rec_xyz || !n_rec || !lig_xyz || !n_lig) throw ld::Error(LD_ERR_INVALID, "coordinates of both molecules");
+        ld_molecule rec{}, lig{};
+        rec.n_atoms = n_rec;
+        rec.coordinates = rec_xyz;
+        lig.n_atoms = n_lig;
+        lig.coordinates = lig_xyz;
+        if (bm_out) {
+            double sub_axis = 0.0, sub_diag = 0.0;
+            if (rec_types) {   // the receptor in the scorer's tile order, as bm_accepts measures its subtiles
+                const std::vector<uint32_t> order = ld::dfire_tile_layout(rec_xyz, rec_types, n_rec).order;
+                std::vector<double> x(order.size(), 0.0), y(order.size(), 0.0), z(order.size(), 0.0);
+                std::vector<uint32_t> type(order.size(), std::numeric_limits<uint32_t>::max());
+                for (size_t i = 0; i < order.size(); i++) {
+                    if (order[i] >= n_rec) continue;
+                    x[i] = rec_xyz[3 * (size_t)order[i]];
+                    y[i] = rec_xyz[3 * (size_t)order[i] + 1];
+                    z[i] = rec_xyz[3 * (size_t)order[i] + 2];
+                    type[i] = rec_types[order[i]];
+                }
+                ld::dfire_bm_subtile_extents(x, y, z, type, &sub_axis, &sub_diag);
+            }
+            ld::BmFrame f;
+            const bool takes = ld::dfire_bm_frame(rec, lig, anm != 0, sub_axis, sub_diag, &f);
+            const double row[9] = {f.centre[0], f.centre[1], f.centre[2], f.ubound, f.extent, f.eps, takes ? 1.0 : 0.0, sub_axis, sub_diag};
+            std::memcpy(bm_out, row, sizeof row);
+        }
+        if (packed_out) {
+            ld::PackedFrame f;
+            const bool takes = ld::packed_accepts(rec, &f);
+            const double row[8] = {f.centre[0], f.centre[1], f.centre[2], f.kappa, f.ubound, f.eps, (double)f.cells, takes ? 1.0 : 0.0};
+            std::memcpy(packed_out, row, sizeof row);
+        }
+    });
+}
 int ld_dfire_bm_fix_scale(const double *rec_xyz, size_t n_rec, double reach, double table_vmax, uint64_t *reach_count_out,
                           int *extra_bits_out, double *scale_out) {
     return guarded([&] {

@@ -759,7 +759,9 @@ double dfire_bm_pose_error(double ubound, double lig_extent, bool anm) {
     return std::sqrt(3.0) * e;
 }
 
-double dfire_bm_error_bound(double ubound, double lig_extent, bool anm) {
+double dfire_bm_error_bound(double ubound, double lig_extent, bool anm) { return dfire_bm_error_bound(ubound, lig_extent, anm, 0.0, 0.0); }
+
+double dfire_bm_error_bound(double ubound, double lig_extent, bool anm, double sub_axis, double sub_diag) {
     // What dfire_bm_pairs computes: coordinates relative to the centre c of the receptor subtile's box (an f32 constant),
     //   D'' = (|r - c|^2 + seed) + |l - c|^2 - 2 (r - c) . (l - c)
     // in f32: 3 + 3 operations for the two squares, one add, three fmas.  For the f32 coordinates this is |l - r|^2 + seed
@@ -769,17 +771,30 @@ double dfire_bm_error_bound(double ubound, double lig_extent, bool anm) {
     const double e_lig = std::ldexp(6.0 * reach, -24)          // rounding of the matrix and of the local coordinates
                          + 2.0 * half_ulp(ubound)               // of the stored translation, and of translation - c
                          + 3.0 * half_ulp(ubound / 2 + reach);  // of the three fmas: partial sums below |translation - c| + |kappa R x|
-    const double e_rec = half_ulp(ubound) + half_ulp(128.0);    // the record's rounding, and that of r - c
+    // r - c, c the centre of the receptor subtile's box: below 256 units (32 A) a coordinate in every complex of proteins, where a
+    // subtile spans a few angstrom (and in 1k4c's, whose beads share subtiles 21.7 A in half extent) -- half_ulp(128.0) covers that.
+    // Nothing in the spatial order promises it (a few far-apart atoms, distant ions in a leaf with protein atoms, a ragged last
+    // subtile): bm_accepts measures the widest subtile box, `sub_axis` = its half extent along an axis, `sub_diag` = its half
+    // diagonal (record units), and the two places that assumed a size take them.  Inside the assumptions -- sub_axis < 256,
+    // sub_diag <= 228 -- the bound is what it was, bit for bit (tests/test_host_cpu.py).
+    const double r_axis = std::max(128.0, sub_axis);
+    const double e_rec = half_ulp(ubound) + half_ulp(r_axis);   // the record's rounding, and that of r - c
     double e_d = e_lig + e_rec;
     // Molecules that flex (poses that are not WILD): either atom's deformation d = sum_k fl(a_k) fl(kappa m_k), ten fmas from 0
     // (partial sums below W), then ONE rounded add onto the posed coordinate / onto r - c.
     const double W = kBmWildUnits;
-    if (anm) e_d += 2.0 * bm_flex_error(W * 0.999) + half_ulp(ubound / 2 + reach + W) + half_ulp(128.0 + W);
+    if (anm) e_d += 2.0 * bm_flex_error(W * 0.999) + half_ulp(ubound / 2 + reach + W) + half_ulp(r_axis + W);
     const double span = std::sqrt(3.0 * 1100.0 * kBmCells);     // |du| + |dv| + |dw| <= sqrt(3) |d|, pairs within 1100 units of 4 d2
     // The ten roundings of the distance arithmetic: every operand and partial sum of such a pair is below 2^17
     // (|l - c| <= 16.6 A + a subtile's half extent < 45 A = 362 record units; the seed carries the LUT's offset, < 2^15).
     // (flexing: r - c + d up to 128 + W, l - c up to that + the cutoff's 134 units: their squares bound every operand and partial sum)
-    const double top = anm ? std::max(131072.0, (128.0 + W + 134.0) * (128.0 + W + 134.0)) : 131072.0;
+    double top = anm ? std::max(131072.0, (128.0 + W + 134.0) * (128.0 + W + 134.0)) : 131072.0;
+    // a subtile wider than that: |l - c| <= the cutoff's 134 units + |r - c| <= 134 + sub_diag (flexing: either atom moves up to
+    // sqrt(3) W, and so does the centre of the subtile's box), the largest operand by the same count as above
+    if (sub_diag > 228.0) {
+        const double reach_c = 134.0 + sub_diag + (anm ? 3.0 * std::sqrt(3.0) * W : 0.0);
+        top = std::max(top, reach_c * reach_c);
+    }
     const double eps = 2.0 * e_d * span + 3.0 * e_d * e_d + 10.0 * half_ulp(top * 0.999);
     return 2.0 * eps;  // twice the bound, LUT cells
 }
@@ -962,6 +977,53 @@ static size_t bm_pass_size(size_t tile_pairs) {
     return chunk;
 }
 
+// The widest box of a molecule's 8-atom subtiles in tile order (padding slots: type 0xffffffff): its half extent along an axis and
+// its half diagonal, record units, a little more than the f64 figures (the kernels' boxes are of f32 records, widened by 2^-22).
+void dfire_bm_subtile_extents(const std::vector<double> &x, const std::vector<double> &y, const std::vector<double> &z,
+                              const std::vector<uint32_t> &type, double *sub_axis, double *sub_diag) {
+    const uint32_t kPad = std::numeric_limits<uint32_t>::max();
+    *sub_axis = *sub_diag = 0.0;
+    for (size_t s = 0; s + 8 <= type.size(); s += 8) {
+        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+        for (size_t i = s; i < s + 8; i++) {
+            if (type[i] == kPad) continue;
+            const double c[3] = {x[i], y[i], z[i]};
+            for (int k = 0; k < 3; k++) {
+                lo[k] = std::min(lo[k], c[k]);
+                hi[k] = std::max(hi[k], c[k]);
+            }
+        }
+        if (!(lo[0] <= hi[0])) continue;   // padding only
+        double d2 = 0.0;
+        for (int k = 0; k < 3; k++) {
+            const double half = 0.5 * (hi[k] - lo[k]) * kBmKappa * 1.00001 + 1e-3;
+            *sub_axis = std::max(*sub_axis, half);
+            d2 += half * half;
+        }
+        *sub_diag = std::max(*sub_diag, std::sqrt(d2));
+    }
+}
+
+// The record frame of a complex and the error bound of its LUT (out->anm, centre, ubound, extent, eps); false: the bound reaches
+// 8 cells.  Reads the coordinates only; sub_axis / sub_diag: dfire_bm_subtile_extents of the receptor in tile order.
+bool dfire_bm_frame(const ld_molecule &receptor, const ld_molecule &ligand, bool anm, double sub_axis, double sub_diag, BmFrame *out) {
+    double half;
+    frame_of_receptor(receptor, out->centre, &half);
+    // The frame holds the receptor's box + 16 A: a ligand atom outside it is beyond the cutoff of every receptor atom.
+    // (flexing: a receptor atom of a pose that is not WILD moves less than kBmWildUnits)
+    double ubound = 128.0;
+    while (ubound < kBmKappa * (half + 16.5) + (anm ? (double)kBmWildUnits : 0.0)) ubound *= 2.0;
+    double extent = 0.0;
+    for (size_t i = 0; i < ligand.n_atoms * 3; i++) extent = std::max(extent, std::fabs(ligand.coordinates[i]));
+    out->anm = anm;
+    out->ubound = ubound;
+    out->extent = extent;
+    out->sub_axis = sub_axis;
+    out->sub_diag = sub_diag;
+    out->eps = dfire_bm_error_bound(ubound, extent, anm, sub_axis, sub_diag) * eps_scale_hook();  // LUT cells
+    return out->eps < 8.0;  // false: a complex thousands of angstroms across -- the pose-major kernels
+}
+
 // Does the block-major path take this complex?  Every reason for declining, before anything is uploaded or launched; what the
 // decision derived on the way (frame, error bound, tile spheres, fixed-point scale, pass size) goes to `out`.
 static bool bm_accepts(const RouteInputs &in, BmFrame *out) {
@@ -995,20 +1057,9 @@ static bool bm_accepts(const RouteInputs &in, BmFrame *out) {
         if (!(std::fabs(desc.potential[i]) <= kBmFixLimit)) return false;
         table_vmax = std::max(table_vmax, std::fabs(desc.potential[i]));
     }
-    double half;
-    frame_of_receptor(desc.receptor, out->centre, &half);
-    // The frame holds the receptor's box + 16 A: a ligand atom outside it is beyond the cutoff of every receptor atom.
-    // (flexing: a receptor atom of a pose that is not WILD moves less than kBmWildUnits)
-    double ubound = 128.0;
-    while (ubound < kBmKappa * (half + 16.5) + (anm ? (double)kBmWildUnits : 0.0)) ubound *= 2.0;
-    double extent = 0.0;
-    for (size_t i = 0; i < desc.ligand.n_atoms * 3; i++) extent = std::max(extent, std::fabs(desc.ligand.coordinates[i]));
-    const double eps = dfire_bm_error_bound(ubound, extent, anm) * eps_scale_hook();  // LUT cells
-    if (!(eps < 8.0)) return false;  // a complex thousands of angstroms across: the pose-major kernels
-    out->anm = anm;
-    out->ubound = ubound;
-    out->extent = extent;
-    out->eps = eps;
+    double sub_axis, sub_diag;
+    dfire_bm_subtile_extents(rec.hx, rec.hy, rec.hz, rec.htype, &sub_axis, &sub_diag);
+    if (!dfire_bm_frame(desc.receptor, desc.ligand, anm, sub_axis, sub_diag, out)) return false;
     // the fixed-point scale: 32 pairs of a block stay below 2^49, under the markers, and a (row, ligand tile) sum -- 64 ligand
     // atoms x the receptor atoms one ligand tile can reach -- inside 63 bits (dfire_bm_fix_scale)
     bm_tile_spheres(lig, out->tile_sphere, out->tile_radius);

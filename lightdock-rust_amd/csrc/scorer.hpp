@@ -178,10 +178,19 @@ struct BmWorkspace {
 struct BmFrame {
     bool anm = false;
     double centre[3] = {0, 0, 0}, ubound = 0.0, extent = 0.0, eps = 0.0;   // the record frame; the LUT's error bound (cells)
+    double sub_axis = 0.0, sub_diag = 0.0;         // the receptor's widest subtile box: half extent along an axis, half diagonal (record units)
     std::vector<float> tile_sphere, tile_radius;   // the ligand tiles' bounding spheres: [tile][4] as the culling kernel reads them; radii in angstrom (the reach of the fixed-point scale)
     double fix_scale = 0.0;
     size_t chunk = 0;                              // poses per pass
 };
+// the frame part of bm_accepts(): anm, centre, ubound, extent, eps of the two molecules' coordinates and the receptor's widest
+// subtile box (dfire_bm_subtile_extents of its tile order; record units); false: eps reaches 8 cells
+// kernels/dfire_bm.hpp's dfire_bm_error_bound(ubound, lig_extent, anm) with the widest receptor subtile box in it: its half extent
+// along an axis and its half diagonal, record units (0, 0: nothing wider than the derivation assumes -- the three-argument form)
+double dfire_bm_error_bound(double ubound, double lig_extent, bool anm, double sub_axis, double sub_diag);
+void dfire_bm_subtile_extents(const std::vector<double> &x, const std::vector<double> &y, const std::vector<double> &z,
+                              const std::vector<uint32_t> &type, double *sub_axis, double *sub_diag);
+bool dfire_bm_frame(const ld_molecule &receptor, const ld_molecule &ligand, bool anm, double sub_axis, double sub_diag, BmFrame *out);
 
 class BlockMajorPath {
    public:

@@ -530,6 +530,33 @@ def test_block_major_cell_lut_decides_like_the_reference(pkg, orc, ubound, exten
     assert 20 <= n_flagged <= 21 * (1 + 2 * int(np.ceil(max(eps - 0.5, 0.0)))) + 2 * int(np.ceil(eps)) + 2      # (the last step is the cutoff)
 
 
+# fixture -> (ubound, lig_extent, eps of bm_accepts as a hex float, eps of ld_dfire_bm_lut for that frame), recorded from the library
+# BEFORE the receptor's widest subtile box entered dfire_bm_error_bound; every one of these LUTs had the sha256 below
+_BM_BOUND_BEFORE = {"1ppe": (512.0, 12.111, "0x1.f2175bdc5f6b7p-3", "0x1.f2175bdc5f6b7p-3"),
+                    "1k4c": (1024.0, 37.295, "0x1.be1d134d44a57p-2", "0x1.be1d134d44a57p-2"),
+                    "2uuy": (512.0, 23.372, "0x1.f6fbc7e7eaf2fp-2", "0x1.175e710fc677dp-2")}
+_BM_LUT_BEFORE = "6f3877d3d7299b5bfd5d61a1be9565ea3467e2bf48f589d05cdeb289dd297ad6"
+
+
+@pytest.mark.parametrize("name", sorted(_BM_BOUND_BEFORE))
+def test_block_major_bound_of_the_fixtures_is_what_it_was(pkg, name):
+    """bm_accepts measures the receptor's widest 8-atom subtile and dfire_bm_error_bound takes it into the rounding of r - c and
+    into the bound on the operands of the distance arithmetic.  For every complex inside what the derivation assumed -- a subtile
+    box below 32 A in half extent along an axis and 28.5 A in half diagonal -- eps and the LUT must come out bit for bit what they
+    were: the fixtures and the benchmark's complexes (1k4c: beads share subtiles of 21.7 A half extent, 26.9 A half diagonal)."""
+    import hashlib
+    c, d, rec, lig = case_paths(name)
+    r, l = pkg.model_from_pdb("dfire", rec), pkg.model_from_pdb("dfire", lig)
+    ubound, extent, eps_scorer, eps_lut = _BM_BOUND_BEFORE[name]
+    f = pkg.dfire_route_frames(r["coordinates"], l["coordinates"], anm=c["use_anm"], rec_types=r["dfire_types"])["bm"]
+    assert (f["ubound"], f["lig_extent"], f["takes"]) == (ubound, extent, True)
+    assert float(f["eps"]).hex() == eps_scorer
+    assert 0.0 < f["sub_axis"] < 256.0 and f["sub_axis"] < f["sub_diag"] <= 228.0
+    codes, eps = pkg.dfire_bm_lut(ubound, extent)
+    assert float(eps).hex() == eps_lut
+    assert hashlib.sha256(codes.tobytes()).hexdigest() == _BM_LUT_BEFORE
+
+
 def test_committed_profile_matches_the_kernel_sources():
     """bench.py reports on-chip counter fractions from profiles/traffic.json: an entry is only valid for the build it
     was taken from.  The default workload's entry must carry the hash of the kernel sources at HEAD -- change a kernel,
