@@ -184,6 +184,18 @@ extern "C" {
     pub fn ld_complex_sasa_radii(c: *const ld_complex, side: c_int, radii_out: *mut u32) -> c_int;
     pub fn ld_complex_sasa(c: *mut ld_complex, n: usize, poses: *const f64, stride: usize, probe: f64, sums: *mut u64,
                            free_counts: *mut u8, bound_counts: *mut u8) -> c_int;
+    pub fn ld_complex_saxs_classes(c: *const ld_complex, side: c_int, class_out: *mut u8) -> c_int;
+    pub fn ld_saxs_form_factors(q: *const f64, n_q: usize, f_out: *mut f64) -> c_int;
+    pub fn ld_saxs_sinc(q: *const f64, n_q: usize, width: u32, bins: usize, s_out: *mut f64) -> c_int;
+    pub fn ld_complex_distance_histogram(c: *mut ld_complex, n: usize, poses: *const f64, stride: usize, width: u32, bins: usize,
+                                         counts: *mut u32) -> c_int;
+    pub fn ld_saxs_debye(n: usize, counts: *const u32, width: u32, bins: usize, class_atoms: *const u32, q: *const f64, n_q: usize,
+                         intensity: *mut f64) -> c_int;
+    pub fn ld_complex_saxs(c: *mut ld_complex, n: usize, poses: *const f64, stride: usize, width: u32, bins: usize, q: *const f64,
+                           n_q: usize, intensity: *mut f64, counts: *mut u32) -> c_int;
+    pub fn ld_complex_saxs_chunk(c: *mut ld_complex, poses: usize) -> c_int;
+    pub fn ld_saxs_fit(n: usize, n_q: usize, intensity: *const f64, i_exp: *const f64, sigma: *const f64, scale_out: *mut f64,
+                       chi2_out: *mut f64) -> c_int;
 }
 
 fn last_error() -> String {

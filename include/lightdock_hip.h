@@ -660,6 +660,69 @@ int ld_complex_sasa(ld_complex *c, size_t n, const double *poses, size_t stride,
                     uint64_t *sums /* n x 4 */, uint8_t *free_counts /* n x (n_rec + n_lig), receptor first, file order */,
                     uint8_t *bound_counts /* as free_counts */);
 
+/* Small-angle scattering: for every pose, the histogram of all pair distances by pair class and, from it, the SAXS
+ * profile I(q) by the Debye formula, to be fitted to an experimental curve.  No tool of the reference tree computes a
+ * profile; the rule is this library's own.  The profile is "vacuum minus excluded volume" of the atoms in the files: no
+ * implicit hydrogens and no hydration layer are modelled; hydrogens take part when the files hold them.
+ *   Atoms that take part: every ATOM / HETATM record of the two files, in file order, except residues named MMB (membrane
+ *     beads).  The element is read by the surface's rule (columns 77-78, trimmed and upper-cased, else the first
+ *     alphabetic character of columns 13-16).  Six classes: H (also D) = 0, C = 1, N = 2, O = 3, P = 4, S = 5.  An atom of
+ *     any other element, or of an MMB residue, takes no part and reports class 255.  At most 65536 atoms of a complex may
+ *     take part, so that a bin count fits 32 bits.
+ *   Pair class of classes e <= e': c = 6 e - e (e - 1) / 2 + (e' - e), 21 values: (0,0) .. (0,5) are 0 .. 5, (5,5) is 20.
+ *   Histogram: the posed atoms are the integer thousandths ld_complex_write_pdb prints (posing and rounding as above).
+ *     For every unordered pair a < b of atoms that take part, of either molecule, d^2 = |c_a - c_b|^2 in exact integers
+ *     (a per-axis |d| is clamped at 2^22 - 1, above 1024 x 2000: a clamped pair is beyond the last bin anyway).  The pair
+ *     falls in bin k, the largest integer with (k w)^2 <= d^2; w is the bin width in thousandths, 100 <= w <= 2000.
+ *     counts[pose][c][k] is the number of such pairs, 1 <= bins <= 1024.  A pair with k >= bins refuses the call.
+ *     Rounding follows posing, so the ligand's own pairs change with the pose even without modes; the receptor's own
+ *     pairs do not when the receptor has no modes.
+ *   Form factors at q in 1 / A, u = (q / 4 pi)^2:  f_e(q) = sum_{k=1..4} a_k exp(-b_k u) + c - rho0 V_e exp(-q^2 V_e^(2/3) / (4 pi)),
+ *     rho0 = 0.334, with Cromer-Mann coefficients and Fraser's displaced volumes (A^3):
+ *            a1        a2        a3        a4        b1        b2        b3        b4        c         V
+ *       H    0.489918  0.262003  0.196767  0.049879  20.6593   7.74039   49.5519   2.20159   0.001305  5.15
+ *       C    2.31000   1.02000   1.58860   0.865000  20.8439   10.2075   0.568700  51.6512   0.215600  16.44
+ *       N    12.2126   3.13220   2.01250   1.16630   0.005700  9.89330   28.9975   0.582600  -11.529   2.49
+ *       O    3.04850   2.28680   1.54630   0.867000  13.2771   5.70110   0.323900  32.9089   0.250800  9.13
+ *       P    6.43450   4.17910   1.78000   1.49080   1.90670   27.1570   0.526000  68.1645   1.11490   5.73
+ *       S    6.90530   5.20340   1.43790   1.58630   1.46790   22.2151   0.253600  56.1720   0.866900  19.86
+ *   Debye sum: r_k = (k + 0.5) w / 1000 A, s(x) = 1 if x == 0 else sin(x) / x.  For each pose and q_j:
+ *       G_c = sum over k ascending of (double)counts[c][k] * s(q_j r_k), from 0
+ *       I(q_j) = S_j, then + F_{j,c} * G_c for c ascending
+ *       S_j = sum over e ascending of (double)N_e * (f_e(q_j) * f_e(q_j)), from 0; N_e the atoms of class e
+ *       F_{j,c} = (2 f_e(q_j)) * f_e'(q_j)
+ *     Every product and sum is a separately rounded f64 operation, no fma, no reassociation.  f, s, S and F are made on
+ *     the HOST with libm and handed to the kernel; the device evaluates no sin or exp.  So an intensity is the same bits
+ *     whatever the batch, and a loop over k on ld_saxs_form_factors and ld_saxs_sinc restates it exactly.
+ *     1 <= n_q <= 1024, 0 <= q <= 1.0, finite.
+ *   Fit, per pose, sums sequential over j from 0:
+ *       scale = (sum_j I_exp I / sigma^2) / (sum_j I I / sigma^2), a term being (x * I) / (sigma * sigma)
+ *       chi2 = (sum_j ((I_exp - scale I) / sigma)^2) / n_q
+ * LD_ERR_INVALID, nothing written: width, bins, n_q or q out of range; non-finite poses, a zero quaternion,
+ * stride < pose_len; a pair beyond the last bin; a posed coordinate of an atom that takes part beyond +-1.0e6 A; no atom
+ * taking part, or more than 65536; a side other than 0 / 1; a sigma that is not finite and > 0, a non-finite I_exp or
+ * intensity, a zero denominator of the scale.  n == 0 is LD_OK.  Device workspace: the counts are produced in chunks of
+ * poses, 84 B a bin and 16 B an atom that takes part a pose, within 256 MiB (or one pose). */
+#define LD_SAXS_CLASSES (6)
+#define LD_SAXS_PAIR_CLASSES (21)
+int ld_complex_saxs_classes(const ld_complex *c, int side, uint8_t *class_out /* n_atoms of that side; 255: no part */); /* host only */
+int ld_saxs_form_factors(const double *q, size_t n_q, double *f_out /* n_q x 6 */); /* host only */
+int ld_saxs_sinc(const double *q, size_t n_q, uint32_t width, size_t bins, double *s_out /* n_q x bins */); /* host only */
+/* counts may be NULL.  ld_complex_last_kernel_ms then reports this call's device work. */
+int ld_complex_distance_histogram(ld_complex *c, size_t n, const double *poses, size_t stride, uint32_t width /* 500 */,
+                                  size_t bins, uint32_t *counts /* n x 21 x bins */);
+/* The Debye sum on the caller's counts (GPU; host arrays in and out, like ld_fcc_common); class_atoms: N_e. */
+int ld_saxs_debye(size_t n, const uint32_t *counts /* n x 21 x bins */, uint32_t width, size_t bins,
+                  const uint32_t class_atoms[6], const double *q, size_t n_q, double *intensity /* n x n_q */);
+/* Histogram and Debye sum in one call, the counts staying on the device unless asked for.  Either output may be NULL.
+ * ld_complex_last_kernel_ms then reports this call's device work: posing, histogram and Debye sum of every chunk. */
+int ld_complex_saxs(ld_complex *c, size_t n, const double *poses, size_t stride, uint32_t width /* 500 */, size_t bins,
+                    const double *q, size_t n_q, double *intensity /* n x n_q */, uint32_t *counts /* n x 21 x bins, or NULL */);
+/* Poses a chunk of counts in the two calls above; 0 (the default): as many as 256 MiB hold.  Results do not depend on it. */
+int ld_complex_saxs_chunk(ld_complex *c, size_t poses);
+int ld_saxs_fit(size_t n, size_t n_q, const double *intensity /* n x n_q */, const double *i_exp /* n_q */,
+                const double *sigma /* n_q */, double *scale_out /* n, or NULL */, double *chi2_out /* n, or NULL */); /* host only */
+
 /* ------------------------------------------------------------------------------------
  * Normal modes: the rec_nm.npy / lig_nm.npy a run with `use_anm: true` reads
  * (src/bin/lightdock-rust.rs:216-254 is the consumer; the reference tree cannot produce them,

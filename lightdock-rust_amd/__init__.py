@@ -205,6 +205,14 @@ def load_library():
     lib.ld_sasa_directions.argtypes = [vp]
     lib.ld_complex_sasa_radii.argtypes = [vp, C.c_int, vp]
     lib.ld_complex_sasa.argtypes = [vp, sz, vp, sz, C.c_double, vp, vp, vp]
+    lib.ld_complex_saxs_classes.argtypes = [vp, C.c_int, vp]
+    lib.ld_saxs_form_factors.argtypes = [vp, sz, vp]
+    lib.ld_saxs_sinc.argtypes = [vp, sz, C.c_uint32, sz, vp]
+    lib.ld_complex_distance_histogram.argtypes = [vp, sz, vp, sz, C.c_uint32, sz, vp]
+    lib.ld_saxs_debye.argtypes = [sz, vp, C.c_uint32, sz, vp, vp, sz, vp]
+    lib.ld_complex_saxs.argtypes = [vp, sz, vp, sz, C.c_uint32, sz, vp, sz, vp, vp]
+    lib.ld_complex_saxs_chunk.argtypes = [vp, sz]
+    lib.ld_saxs_fit.argtypes = [sz, sz, vp, vp, vp, vp, vp]
     lib.ld_complex_set_reference.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_double, C.c_double]
     lib.ld_complex_reference_counts.argtypes = [vp, vp]
     lib.ld_complex_native_pairs.argtypes = [vp, vp]
@@ -696,6 +704,17 @@ class GSO:
         _check(self.lib.ld_gso_save_many(self._h, n, ids, dirs, step))
 
 
+SAXS_CLASSES, SAXS_PAIR_CLASSES, SAXS_MAX_BINS = 6, 21, 1024
+
+
+def saxs_width(width):
+    """A bin width in A -> whole thousandths; the library checks the range."""
+    w = int(round(1000.0 * float(width)))
+    if not 0 <= w < 2 ** 32:
+        raise ValueError("width must be 0.1 .. 2.0 A")
+    return w
+
+
 class Complex:
     """LightDock's analysis of a run (ld_complex_*): posed coordinates, BSAS clustering of whole swarms and of one ranked
     list across swarms, top-model PDBs, per-pose interface contacts and residue-pair sets, clustering by common contacts, solvent-accessible
@@ -859,6 +878,47 @@ class Complex:
                                         _ptr(out.get("free")), _ptr(out.get("bound"))))
         return out
 
+    def saxs_classes(self, side):
+        """The scattering class of every atom of a side (0 receptor, 1 ligand): H / D 0, C 1, N 2, O 3, P 4, S 5, and 255
+        for an atom that takes no part: another element, a membrane bead (ld_complex_saxs_classes)."""
+        out = np.zeros(self.num_atoms(side) if side in (0, 1) else 0, dtype=np.uint8)
+        _check(self.lib.ld_complex_saxs_classes(self._h, side, _ptr(out)))
+        return out
+
+    def distance_histogram(self, poses, width=0.5, bins=SAXS_MAX_BINS, chunk=0):
+        """(n, >= pose_len) poses -> (n, 21, bins) uint32: the pairs of atoms that take part, by pair class and by bin of
+        `width` A (a whole number of thousandths, 0.1 .. 2.0) of their distance on the coordinates "%8.3f" prints
+        (ld_complex_distance_histogram; lightdock_hip.h, "Small-angle scattering").  A pair beyond the last bin is an
+        error.  chunk: the poses whose counts are on the device at a time (ld_complex_saxs_chunk), 0 for as many as
+        256 MiB hold; the result does not depend on it."""
+        poses = _f64(poses)
+        if poses.ndim != 2:
+            raise ValueError("poses must be (n, pose_len)")
+        out = np.zeros((poses.shape[0], SAXS_PAIR_CLASSES, bins), dtype=np.uint32)
+        _check(self.lib.ld_complex_saxs_chunk(self._h, chunk))
+        try:
+            _check(self.lib.ld_complex_distance_histogram(self._h, poses.shape[0], _ptr(poses), poses.shape[1], saxs_width(width), bins, _ptr(out)))
+        finally:
+            self.lib.ld_complex_saxs_chunk(self._h, 0)
+        return out
+
+    def saxs(self, poses, q, width=0.5, bins=SAXS_MAX_BINS, counts=False, chunk=0):
+        """(n, >= pose_len) poses, q (n_q,) in 1 / A -> (n, n_q) intensities by the Debye sum over distance_histogram()'s
+        counts, which never leave the device (ld_complex_saxs); counts=True returns (intensities, counts).  chunk as
+        distance_histogram()'s."""
+        poses, q = _f64(poses), _f64(q).ravel()
+        if poses.ndim != 2:
+            raise ValueError("poses must be (n, pose_len)")
+        n = poses.shape[0]
+        out = np.zeros((n, q.size))
+        hist = np.zeros((n, SAXS_PAIR_CLASSES, bins), dtype=np.uint32) if counts else None
+        _check(self.lib.ld_complex_saxs_chunk(self._h, chunk))
+        try:
+            _check(self.lib.ld_complex_saxs(self._h, n, _ptr(poses), poses.shape[1], saxs_width(width), bins, _ptr(q), q.size, _ptr(out), _ptr(hist)))
+        finally:
+            self.lib.ld_complex_saxs_chunk(self._h, 0)
+        return (out, hist) if counts else out
+
     def write_pdb(self, pose, path):
         pose = _f64(pose).ravel()
         if pose.size != self.pose_len:
@@ -957,6 +1017,44 @@ def sasa_area(weighted):
     """Weighted point counts (count x E^2 in thousandths^2: sasa()'s sums, their differences, an atom's count times its
     squared expanded radius) -> A^2: x 4 pi / (128 x 10^6)."""
     return np.asarray(weighted, dtype=np.float64) * (4.0 * np.pi / (SASA_POINTS * 1e6))
+
+
+def saxs_form_factors(q):
+    """q (n_q,) in 1 / A -> (n_q, 6): the form factor of H, C, N, O, P, S less its displaced solvent (ld_saxs_form_factors)."""
+    q = _f64(q).ravel()
+    out = np.zeros((q.size, SAXS_CLASSES))
+    _check(load_library().ld_saxs_form_factors(_ptr(q), q.size, _ptr(out)))
+    return out
+
+
+def saxs_sinc(q, width=0.5, bins=SAXS_MAX_BINS):
+    """(n_q, bins): sin(x) / x at x = q_j r_k, r_k = (k + 0.5) width, and 1 at x == 0 (ld_saxs_sinc)."""
+    q = _f64(q).ravel()
+    out = np.zeros((q.size, bins))
+    _check(load_library().ld_saxs_sinc(_ptr(q), q.size, saxs_width(width), bins, _ptr(out)))
+    return out
+
+
+def saxs_debye(counts, class_atoms, q, width=0.5):
+    """counts (n, 21, bins) uint32, class_atoms (6,) -> (n, n_q): the Debye sum on the GPU (ld_saxs_debye)."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    class_atoms, q = np.ascontiguousarray(class_atoms, dtype=np.uint32), _f64(q).ravel()
+    if counts.ndim != 3 or counts.shape[1] != SAXS_PAIR_CLASSES or class_atoms.shape != (SAXS_CLASSES,):
+        raise ValueError("counts must be (n, 21, bins), class_atoms (6,)")
+    out = np.zeros((counts.shape[0], q.size))
+    _check(load_library().ld_saxs_debye(counts.shape[0], _ptr(counts), saxs_width(width), counts.shape[2], _ptr(class_atoms), _ptr(q), q.size, _ptr(out)))
+    return out
+
+
+def saxs_fit(intensity, i_exp, sigma):
+    """intensity (n, n_q), i_exp and sigma (n_q,) -> (scale (n,), chi2 (n,)) (ld_saxs_fit)."""
+    intensity, i_exp, sigma = _f64(intensity), _f64(i_exp).ravel(), _f64(sigma).ravel()
+    if intensity.ndim != 2 or i_exp.shape != intensity.shape[1:] or sigma.shape != i_exp.shape:
+        raise ValueError("intensity must be (n, n_q), i_exp and sigma (n_q,)")
+    n = intensity.shape[0]
+    scale, chi2 = np.zeros(n), np.zeros(n)
+    _check(load_library().ld_saxs_fit(n, i_exp.size, _ptr(intensity), _ptr(i_exp), _ptr(sigma), _ptr(scale), _ptr(chi2)))
+    return scale, chi2
 
 
 ANM_CUTOFF = 15.0

@@ -26,6 +26,7 @@
 #include "lightdock_hip.h"
 #include "prepare.hpp"
 #include "refine.hpp"
+#include "saxs.hpp"
 #include "scorer.hpp"
 
 namespace {
@@ -631,6 +632,46 @@ int ld_complex_sasa(ld_complex *c, size_t n, const double *poses, size_t stride,
         if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
         c->impl.sasa(n, poses, stride, probe, sums, free_counts, bound_counts);
     });
+}
+int ld_complex_saxs_classes(const ld_complex *c, int side, uint8_t *class_out) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.saxs_classes(side, class_out);
+    });
+}
+int ld_saxs_form_factors(const double *q, size_t n_q, double *f_out) {
+    return guarded([&] { ld::saxs_form_factors(q, n_q, f_out); });
+}
+int ld_saxs_sinc(const double *q, size_t n_q, uint32_t width, size_t bins, double *s_out) {
+    return guarded([&] { ld::saxs_sinc(q, n_q, width, bins, s_out); });
+}
+int ld_complex_distance_histogram(ld_complex *c, size_t n, const double *poses, size_t stride, uint32_t width, size_t bins,
+                                  uint32_t *counts) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.distance_histogram(n, poses, stride, width, bins, counts);
+    });
+}
+int ld_saxs_debye(size_t n, const uint32_t *counts, uint32_t width, size_t bins, const uint32_t class_atoms[6], const double *q,
+                  size_t n_q, double *intensity) {
+    return guarded([&] { ld::saxs_debye_host(n, counts, width, bins, class_atoms, q, n_q, intensity); });
+}
+int ld_complex_saxs(ld_complex *c, size_t n, const double *poses, size_t stride, uint32_t width, size_t bins, const double *q,
+                    size_t n_q, double *intensity, uint32_t *counts) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.saxs(n, poses, stride, width, bins, q, n_q, intensity, counts);
+    });
+}
+int ld_complex_saxs_chunk(ld_complex *c, size_t poses) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.saxs_chunk(poses);
+    });
+}
+int ld_saxs_fit(size_t n, size_t n_q, const double *intensity, const double *i_exp, const double *sigma, double *scale_out,
+                double *chi2_out) {
+    return guarded([&] { ld::saxs_fit(n, n_q, intensity, i_exp, sigma, scale_out, chi2_out); });
 }
 int ld_complex_set_reference(ld_complex *c, const char *ref_receptor_pdb, const char *ref_ligand_pdb, double contact_cutoff,
                              double interface_cutoff) {

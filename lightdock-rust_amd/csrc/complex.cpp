@@ -29,11 +29,7 @@ long long cutoff_thousandths(double cutoff, const char *message) {
     return C;
 }
 
-uint32_t sasa_radius(const char *line, size_t len) {
-    static const struct {
-        const char *element;
-        uint32_t radius;
-    } table[] = {{"C", 1700}, {"N", 1550}, {"O", 1520}, {"F", 1470}, {"P", 1800}, {"S", 1800}, {"CL", 1750}, {"SE", 1900}, {"BR", 1850}, {"I", 1980}};
+std::string record_element(const char *line, size_t len) {
     std::string element;
     if (len >= 78)
         for (size_t k = 76; k < 78; k++)
@@ -41,10 +37,23 @@ uint32_t sasa_radius(const char *line, size_t len) {
     if (element.empty())
         for (size_t k = 12; k < 16 && element.empty(); k++)
             if (std::isalpha((unsigned char)line[k])) element.push_back((char)std::toupper((unsigned char)line[k]));
-    size_t b = 17, e = 20;  // the residue name, blanks trimmed
+    return element;
+}
+
+std::string record_residue_name(const char *line) {
+    size_t b = 17, e = 20;
     while (b < e && line[b] == ' ') b++;
     while (e > b && line[e - 1] == ' ') e--;
-    if (element == "H" || element == "D" || std::string(line + b, e - b) == "MMB") return 0;
+    return std::string(line + b, e - b);
+}
+
+uint32_t sasa_radius(const char *line, size_t len) {
+    static const struct {
+        const char *element;
+        uint32_t radius;
+    } table[] = {{"C", 1700}, {"N", 1550}, {"O", 1520}, {"F", 1470}, {"P", 1800}, {"S", 1800}, {"CL", 1750}, {"SE", 1900}, {"BR", 1850}, {"I", 1980}};
+    const std::string element = record_element(line, len);
+    if (element == "H" || element == "D" || record_residue_name(line) == "MMB") return 0;
     for (const auto &row : table)
         if (element == row.element) return row.radius;
     return 1800;
@@ -111,6 +120,7 @@ Complex::Complex(const char *receptor_pdb, const char *ligand_pdb, const double 
         sasa_.n_part = (int)part_atom.size();
         sasa_.part_atom = arena_.upload(part_atom);
         sasa_.part_radius = arena_.upload(part_radius);
+        init_saxs();
     } catch (...) {
         destroy();  // no destructor runs for a constructor that throws
         throw;

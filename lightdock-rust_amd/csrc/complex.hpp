@@ -14,11 +14,17 @@
 #include "kernels/cluster.hpp"
 #include "kernels/ranked.hpp"
 #include "kernels/sasa.hpp"
+#include "kernels/saxs.hpp"
 
 namespace ld {
 
 // C = llrint(cutoff * 1000), 1 .. 30000, of a contact cutoff in A (lightdock_hip.h, "Interface contacts"); `message` otherwise.
 long long cutoff_thousandths(double cutoff, const char *message);
+// The element of an ATOM / HETATM record: columns 77-78, trimmed and upper-cased; a record too short for them or a blank
+// field: the first alphabetic character of columns 13-16.  `line` has 54 columns at least.
+std::string record_element(const char *line, size_t len);
+// The residue name of a record, columns 18-20, blanks trimmed.
+std::string record_residue_name(const char *line);
 
 class Complex {
    public:
@@ -51,6 +57,12 @@ class Complex {
     // Solvent-accessible surface (lightdock_hip.h, "Solvent-accessible surface")
     void sasa_radii(int side, uint32_t *radii_out) const;  // thousandths, 0 for an atom that takes no part
     void sasa(size_t n, const double *poses, size_t stride, double probe, uint64_t *sums, uint8_t *free_counts, uint8_t *bound_counts);
+    // Small-angle scattering (lightdock_hip.h, "Small-angle scattering"; saxs.cpp)
+    void saxs_classes(int side, uint8_t *class_out) const;  // 0 .. 5, 255 for an atom that takes no part
+    void saxs_chunk(size_t poses) { saxs_chunk_ = poses; }  // poses a chunk of counts; 0: as many as 256 MiB hold
+    void distance_histogram(size_t n, const double *poses, size_t stride, uint32_t width, size_t bins, uint32_t *counts);
+    void saxs(size_t n, const double *poses, size_t stride, uint32_t width, size_t bins, const double *q, size_t n_q, double *intensity,
+              uint32_t *counts);
     // Model quality against a reference complex (lightdock_hip.h, "Model quality")
     void set_reference(const char *ref_receptor_pdb, const char *ref_ligand_pdb, double contact_cutoff, double interface_cutoff);
     void reference_counts(uint32_t *out) const;  // 6: matched rec, matched lig, native pairs, rec fit, lig fit, interface fit
@@ -66,6 +78,9 @@ class Complex {
     void pose_all(size_t n, const double *poses, size_t stride, double *out);  // all atoms of n poses, unrounded
     void finish_timed(const int *d_overflow, const char *what, const char *overflow_message);
     void check_pair_keys() const;
+    void init_saxs();  // the atoms that take part in the scattering, from the constructor
+    void saxs_run(size_t n, const double *poses, size_t stride, uint32_t width, size_t bins, const double *q, size_t n_q,
+                  double *intensity, uint32_t *counts);
     FccCluster::Sets pair_sets(size_t n, const double *poses, size_t stride, long long C, bool fill, size_t cap, int **d_overflow_out);
     void destroy();
 
@@ -78,6 +93,10 @@ class Complex {
     SasaDevice sasa_;                       // probe and e_max are set per call
     std::vector<uint32_t> sasa_radius_[2];  // every atom of a side, 0 for one that takes no part
     int sasa_r_max_ = 0;
+    SaxsDevice saxs_;
+    std::vector<uint8_t> saxs_class_[2];  // every atom of a side, 255 for one that takes no part
+    uint32_t saxs_class_atoms_[kSaxsClasses] = {};
+    size_t saxs_chunk_ = 0;
     // what set_reference derived; `set` only once all of it stands
     struct Reference {
         bool set = false;
