@@ -118,6 +118,25 @@ pub struct ld_complex {
     _private: [u8; 0],
 }
 
+/// `ld_density`: the opaque handle of a quantised density map (include/lightdock_hip.h, "Density fit").
+#[allow(non_camel_case_types)]
+#[repr(C)]
+pub struct ld_density {
+    _private: [u8; 0],
+}
+
+/// `ld_density_sums`: the exact sums of one pose's simulated density against a map.
+#[allow(non_camel_case_types)]
+#[repr(C)]
+pub struct ld_density_sums {
+    pub s: u64,
+    pub ss: u64,
+    pub se: u64,
+    pub inside_sum: u64,
+    pub outside: u32,
+    pub reserved: u32,
+}
+
 pub const LD_SASA_POINTS: usize = 128;
 
 // The decomposition, refinement and residue entry points (ld_scorer_decompose*, ld_scorer_refine*, ld_refine_*, ld_model_*) are declared only: no wrapper uses them yet.
@@ -196,6 +215,18 @@ extern "C" {
     pub fn ld_complex_saxs_chunk(c: *mut ld_complex, poses: usize) -> c_int;
     pub fn ld_saxs_fit(n: usize, n_q: usize, intensity: *const f64, i_exp: *const f64, sigma: *const f64, scale_out: *mut f64,
                        chi2_out: *mut f64) -> c_int;
+    pub fn ld_density_create(rho: *const f32, n: *const u32, origin: *const i32, step: *const u32, threshold: f64) -> *mut ld_density;
+    pub fn ld_density_destroy(d: *mut ld_density);
+    pub fn ld_density_info(d: *const ld_density, n_voxels: *mut u64, s_e: *mut u64, s_ee: *mut u64, scale: *mut f64) -> c_int;
+    pub fn ld_density_voxels(d: *const ld_density, voxels_out: *mut u32) -> c_int;
+    pub fn ld_density_kernel(sigma: u32, table_out: *mut u32, length_out: *mut u32, shift_out: *mut u32) -> c_int;
+    pub fn ld_complex_density_fit(c: *mut ld_complex, d: *mut ld_density, n: usize, poses: *const f64, stride: usize, sigma: u32,
+                                  out: *mut ld_density_sums) -> c_int;
+    pub fn ld_complex_simulate_density(c: *mut ld_complex, d: *mut ld_density, n: usize, poses: *const f64, stride: usize, sigma: u32,
+                                       grid: *mut u32) -> c_int;
+    pub fn ld_density_scores(d: *const ld_density, n: usize, sums: *const ld_density_sums, cc: *mut f64, ccm: *mut f64,
+                             inside: *mut f64) -> c_int;
+    pub fn ld_complex_density_chunk(c: *mut ld_complex, poses: usize) -> c_int;
 }
 
 fn last_error() -> String {

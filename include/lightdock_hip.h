@@ -723,6 +723,78 @@ int ld_complex_saxs_chunk(ld_complex *c, size_t poses);
 int ld_saxs_fit(size_t n, size_t n_q, const double *intensity /* n x n_q */, const double *i_exp /* n_q */,
                 const double *sigma /* n_q */, double *scale_out /* n, or NULL */, double *chi2_out /* n, or NULL */); /* host only */
 
+/* Density fit: for every pose, the density its atoms would show in a cryo-EM map at a given resolution, and the exact
+ * sums from which its correlation with the map follows.  No tool of the reference tree reads a volume; the rule is this
+ * library's own, modelled on Chimera's molmap and "fit in map".  Everything on the device is an integer, so a pose's
+ * words are the same whatever the batch, its place in it or the chunk, and a numpy restatement gives the same words.
+ *   Map: nx x ny x nz voxels, x fastest; the centre of voxel (i, j, k) is origin + (i hx, j hy, k hz), all in integer
+ *     thousandths of an A in the run's frame (that of lightdock_<rec>.pdb).  1 <= n <= 1024 an axis, at most 2^24 voxels,
+ *     200 <= h <= 20000, |origin| <= 10^9.  Values arrive as float.  A value below threshold (>= 0, default 0: negative
+ *     density counts as none) becomes 0; the quantised voxel is E = rint(rho' * (32767.0 / max rho')) in double, so
+ *     0 <= E <= 32767.  A map with a value that is not finite, or with no positive value left, is refused.  Constants of
+ *     a map: N voxels, S_e = sum E, S_ee = sum E^2.
+ *   Atoms: posed and rounded as under "Small-angle scattering" above, and exactly its atoms take part (class != 255).
+ *     The weight w of an atom is the atomic number of its class: H 1, C 6, N 7, O 8, P 15, S 16.  At most 65536 atoms.
+ *   Kernel table, made by the HOST with libm from sigma in thousandths, 300 <= sigma <= 15000 (a tool passes
+ *     sigma = rint(225 * resolution), which is resolution / (pi sqrt 2) to three digits):
+ *       two = 2 sigma^2;  L = floor(two * ln 510) + 1, the first d^2 at which 255 exp(-d^2 / two) rounds to 0;
+ *       s = the smallest shift with ((L - 1) >> s) + 1 <= 4096;  T = ((L - 1) >> s) + 1;
+ *       K[t] = rint(255 * exp(-(((double)t + 0.5) * (double)(1 << s)) / (double)two)),  t < T.
+ *     An atom at the exact integer squared distance d^2 from a voxel's centre adds w * K[d^2 >> s] to that voxel when
+ *     d^2 < T << s, and nothing otherwise.  A voxel outside the grid receives nothing: a support that leaves the map is
+ *     clipped.  The device evaluates no exp.  T << s is below 2^32 for every sigma (2676 << 20 at 15000); d^2 itself may
+ *     pass 32 bits: an axis difference above isqrt((T << s) - 1) decides alone, the rest is summed in 64 bits.
+ *     A call is refused when isqrt(T << s) > 16 * min(hx, hy, hz): the map is far finer than the table needs (bin it).
+ *   Per pose, with rho_s(v) the simulated voxel, exact integers:
+ *       s = sum rho_s;  ss = sum rho_s^2;  se = sum rho_s E;  inside_sum = sum of rho_s over the voxels with E > 0;
+ *       outside = the atoms taking part that lie in no voxel's cell: 2 (x - X[0]) < -hx or 2 (x - X[nx - 1]) >= hx, and
+ *       likewise on y and z.
+ *   Widths: a uint32 voxel cannot wrap (65536 * 16 * 255 < 2^32).  A pose with a voxel >= 2^24 or s >= 2^40 refuses the
+ *     call.  Below those limits ss < 2^24 * s < 2^64 and se <= 32767 * s < 2^55.
+ *   Scores, made by the host in one order of operations; every integer is converted once to double with correct
+ *     rounding, products of the 64-bit sums are taken in 128 bits:
+ *       cc = (double)se / (sqrt((double)ss) * sqrt((double)S_ee)), 0 when ss = 0;
+ *       A = N se - s S_e, B = N ss - s^2, C = N S_ee - S_e^2;
+ *       ccm = (double)A / (sqrt((double)B) * sqrt((double)C)), 0 when B = 0 or C = 0;
+ *       inside = (double)inside_sum / (double)s, 0 when s = 0.
+ *   Without receptor modes the receptor's density is the same for every pose: it is deposited once a call and a pose
+ *     visits only the bricks of 16 x 16 x 4 voxels its ligand's supports reach; with receptor modes every pose deposits all its
+ *     atoms.  The words are the same either way.
+ * LD_ERR_INVALID, nothing written: a map, sigma or threshold out of range; a support wider than 16 voxels; non-finite
+ * poses, a zero quaternion, stride < pose_len; a posed coordinate of an atom that takes part beyond +-1.0e6 A; a voxel
+ * >= 2^24 or s >= 2^40; no atom taking part, or more than 65536; more than 256 MiB of simulated voxels.  n == 0 is LD_OK.
+ * Device workspace: chunks of poses, 16 B an atom and 8 B a brick a pose (and 4 B a voxel when voxels are asked for),
+ * within 256 MiB (or one pose); 4 B a voxel for the receptor's grid. */
+typedef struct ld_density ld_density;
+typedef struct ld_density_sums {
+    uint64_t s;
+    uint64_t ss;
+    uint64_t se;
+    uint64_t inside_sum;
+    uint32_t outside;
+    uint32_t reserved; /* 0 */
+} ld_density_sums;
+/* NULL (ld_last_error) on a refusal.  Host only: the voxels reach the device with the first fit. */
+ld_density *ld_density_create(const float *rho /* nx x ny x nz, x fastest */, const uint32_t n[3], const int32_t origin[3],
+                              const uint32_t step[3], double threshold);
+void ld_density_destroy(ld_density *d);
+/* Any output may be NULL.  scale: 32767.0 / max rho'. */
+int ld_density_info(const ld_density *d, uint64_t *n_voxels, uint64_t *s_e, uint64_t *s_ee, double *scale); /* host only */
+int ld_density_voxels(const ld_density *d, uint32_t *voxels_out /* N: E */); /* host only */
+/* table_out == NULL asks for the length and the shift only. */
+int ld_density_kernel(uint32_t sigma, uint32_t *table_out /* T, or NULL */, uint32_t *length_out, uint32_t *shift_out); /* host only */
+/* ld_complex_last_kernel_ms then reports this call's device work. */
+int ld_complex_density_fit(ld_complex *c, ld_density *d, size_t n, const double *poses, size_t stride, uint32_t sigma,
+                           ld_density_sums *out /* n */);
+/* The simulated voxels themselves, x fastest; refused above 256 MiB of output. */
+int ld_complex_simulate_density(ld_complex *c, ld_density *d, size_t n, const double *poses, size_t stride, uint32_t sigma,
+                                uint32_t *grid /* n x N */);
+/* Any output may be NULL. */
+int ld_density_scores(const ld_density *d, size_t n, const ld_density_sums *sums /* n */, double *cc /* n */, double *ccm /* n */,
+                      double *inside /* n */); /* host only */
+/* Poses a chunk in the two ld_complex_ calls above; 0 (the default): as many as 256 MiB hold.  Results do not depend on it. */
+int ld_complex_density_chunk(ld_complex *c, size_t poses);
+
 /* ------------------------------------------------------------------------------------
  * Normal modes: the rec_nm.npy / lig_nm.npy a run with `use_anm: true` reads
  * (src/bin/lightdock-rust.rs:216-254 is the consumer; the reference tree cannot produce them,

@@ -213,6 +213,16 @@ def load_library():
     lib.ld_complex_saxs.argtypes = [vp, sz, vp, sz, C.c_uint32, sz, vp, sz, vp, vp]
     lib.ld_complex_saxs_chunk.argtypes = [vp, sz]
     lib.ld_saxs_fit.argtypes = [sz, sz, vp, vp, vp, vp, vp]
+    lib.ld_density_create.restype = vp
+    lib.ld_density_create.argtypes = [vp, vp, vp, vp, C.c_double]
+    lib.ld_density_destroy.argtypes = [vp]
+    lib.ld_density_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), dp]
+    lib.ld_density_voxels.argtypes = [vp, vp]
+    lib.ld_density_kernel.argtypes = [C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.ld_complex_density_fit.argtypes = [vp, vp, sz, vp, sz, C.c_uint32, vp]
+    lib.ld_complex_simulate_density.argtypes = [vp, vp, sz, vp, sz, C.c_uint32, vp]
+    lib.ld_density_scores.argtypes = [vp, sz, vp, vp, vp, vp]
+    lib.ld_complex_density_chunk.argtypes = [vp, sz]
     lib.ld_complex_set_reference.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_double, C.c_double]
     lib.ld_complex_reference_counts.argtypes = [vp, vp]
     lib.ld_complex_native_pairs.argtypes = [vp, vp]
@@ -715,10 +725,84 @@ def saxs_width(width):
     return w
 
 
+DENSITY_SUMS = np.dtype([("s", np.uint64), ("ss", np.uint64), ("se", np.uint64), ("inside_sum", np.uint64), ("outside", np.uint32),
+                         ("reserved", np.uint32)])      # ld_density_sums
+
+
+def _thousandths3(v, what):
+    a = np.asarray(v)
+    if a.shape != (3,) or not np.all(np.isfinite(np.asarray(a, dtype=np.float64))) or np.any(a != np.rint(a)) or np.any(np.abs(np.asarray(a, dtype=np.float64)) > 2 ** 31 - 1):
+        raise ValueError("%s must be three whole thousandths of an A" % what)
+    return [int(x) for x in a]
+
+
+class Density:
+    """A density map as the fit reads it (ld_density_*; lightdock_hip.h, "Density fit"): rho (nz, ny, nx) floats, x fastest;
+    origin and step in whole thousandths of an A, the centre of voxel (i, j, k) at origin + (i hx, j hy, k hz) in the run's
+    frame.  Values below threshold become 0, the rest are quantised to 0 .. 32767."""
+
+    def __init__(self, rho, origin, step, threshold=0.0):
+        self.lib = load_library()
+        rho = np.ascontiguousarray(rho, dtype=np.float32)
+        if rho.ndim != 3:
+            raise ValueError("rho must be (nz, ny, nx)")
+        origin, step = _thousandths3(origin, "origin"), _thousandths3(step, "step")
+        if min(step) < 0:
+            raise ValueError("step must be positive")
+        self.shape = rho.shape
+        self.origin, self.step = tuple(origin), tuple(step)
+        n = (C.c_uint32 * 3)(rho.shape[2], rho.shape[1], rho.shape[0])
+        h = self.lib.ld_density_create(_ptr(rho), n, (C.c_int32 * 3)(*origin), (C.c_uint32 * 3)(*step), float(threshold))
+        if not h:
+            raise LightdockError(-1, self.lib.ld_last_error().decode())
+        self._h = C.c_void_p(h)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self.lib.ld_density_destroy(self._h)
+
+    def info(self):
+        """{"n": voxels, "s_e": sum E, "s_ee": sum E^2, "scale": 32767 / max rho'} (ld_density_info)."""
+        n, se, see, scale = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+        _check(self.lib.ld_density_info(self._h, C.byref(n), C.byref(se), C.byref(see), C.byref(scale)))
+        return {"n": n.value, "s_e": se.value, "s_ee": see.value, "scale": scale.value}
+
+    def voxels(self):
+        """(nz, ny, nx) uint32: the quantised voxels E (ld_density_voxels)."""
+        out = np.zeros(self.shape, dtype=np.uint32)
+        _check(self.lib.ld_density_voxels(self._h, _ptr(out)))
+        return out
+
+
+def density_kernel(sigma):
+    """sigma in whole thousandths of an A -> (table (T,) uint32, shift): an atom at squared distance d2 adds
+    weight * table[d2 >> shift] when d2 < T << shift (ld_density_kernel; made on the host with libm)."""
+    lib = load_library()
+    length, shift = C.c_uint32(), C.c_uint32()
+    _check(lib.ld_density_kernel(int(sigma), None, C.byref(length), C.byref(shift)))
+    table = np.zeros(length.value, dtype=np.uint32)
+    _check(lib.ld_density_kernel(int(sigma), _ptr(table), C.byref(length), C.byref(shift)))
+    return table, shift.value
+
+
+def density_scores(density, sums):
+    """sums: density_fit()'s dict, or a DENSITY_SUMS array -> (cc, ccm, inside), each (n,) (ld_density_scores; host only)."""
+    if isinstance(sums, dict):
+        rows = np.zeros(len(sums["s"]), dtype=DENSITY_SUMS)
+        for k in ("s", "ss", "se", "inside_sum", "outside"):
+            rows[k] = sums[k]
+    else:
+        rows = np.ascontiguousarray(sums, dtype=DENSITY_SUMS)
+    n = rows.shape[0]
+    cc, ccm, inside = np.zeros(n), np.zeros(n), np.zeros(n)
+    _check(load_library().ld_density_scores(density._h, n, _ptr(rows), _ptr(cc), _ptr(ccm), _ptr(inside)))
+    return cc, ccm, inside
+
+
 class Complex:
     """LightDock's analysis of a run (ld_complex_*): posed coordinates, BSAS clustering of whole swarms and of one ranked
     list across swarms, top-model PDBs, per-pose interface contacts and residue-pair sets, clustering by common contacts, solvent-accessible
-    and buried surface."""
+    and buried surface, SAXS profiles, the fit to a density map."""
 
     def __init__(self, receptor_pdb, ligand_pdb, rec_nmodes=None, rec_num_anm=0, lig_nmodes=None, lig_num_anm=0):
         self.lib = load_library()
@@ -918,6 +1002,35 @@ class Complex:
         finally:
             self.lib.ld_complex_saxs_chunk(self._h, 0)
         return (out, hist) if counts else out
+
+    def density_fit(self, poses, density, sigma, chunk=0):
+        """(n, >= pose_len) poses, a Density, sigma in whole thousandths -> {"s", "ss", "se", "inside_sum" (n,) uint64,
+        "outside" (n,) uint32}: the exact sums of every pose's simulated density against the map (ld_complex_density_fit).
+        chunk: the poses on the device at a time (ld_complex_density_chunk), 0 for as many as 256 MiB hold; the words do
+        not depend on it."""
+        poses = _f64(poses)
+        if poses.ndim != 2:
+            raise ValueError("poses must be (n, pose_len)")
+        rows = np.zeros(poses.shape[0], dtype=DENSITY_SUMS)
+        _check(self.lib.ld_complex_density_chunk(self._h, chunk))
+        try:
+            _check(self.lib.ld_complex_density_fit(self._h, density._h, poses.shape[0], _ptr(poses), poses.shape[1], int(sigma), _ptr(rows)))
+        finally:
+            self.lib.ld_complex_density_chunk(self._h, 0)
+        return {k: rows[k].copy() for k in ("s", "ss", "se", "inside_sum", "outside")}
+
+    def simulate_density(self, poses, density, sigma, chunk=0):
+        """(n, nz, ny, nx) uint32: the voxels density_fit() sums (ld_complex_simulate_density); at most 256 MiB a call."""
+        poses = _f64(poses)
+        if poses.ndim != 2:
+            raise ValueError("poses must be (n, pose_len)")
+        out = np.zeros((poses.shape[0],) + tuple(density.shape), dtype=np.uint32)
+        _check(self.lib.ld_complex_density_chunk(self._h, chunk))
+        try:
+            _check(self.lib.ld_complex_simulate_density(self._h, density._h, poses.shape[0], _ptr(poses), poses.shape[1], int(sigma), _ptr(out)))
+        finally:
+            self.lib.ld_complex_density_chunk(self._h, 0)
+        return out
 
     def write_pdb(self, pose, path):
         pose = _f64(pose).ravel()

@@ -2,6 +2,7 @@
 //
 // Every call catches ld::Error and turns it into an ld_status plus a thread-local
 // message, which is how this library reports what the reference reports by panicking.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +14,7 @@
 
 #include "anm.hpp"
 #include "complex.hpp"
+#include "emfit.hpp"
 #include "fcc.hpp"
 #include "gso.hpp"
 #include "host/cli.hpp"
@@ -672,6 +674,60 @@ int ld_complex_saxs_chunk(ld_complex *c, size_t poses) {
 int ld_saxs_fit(size_t n, size_t n_q, const double *intensity, const double *i_exp, const double *sigma, double *scale_out,
                 double *chi2_out) {
     return guarded([&] { ld::saxs_fit(n, n_q, intensity, i_exp, sigma, scale_out, chi2_out); });
+}
+ld_density *ld_density_create(const float *rho, const uint32_t n[3], const int32_t origin[3], const uint32_t step[3], double threshold) {
+    ld_density *d = nullptr;
+    int rc = guarded([&] { d = new ld_density(rho, n, origin, step, threshold); });
+    return rc == LD_OK ? d : nullptr;
+}
+void ld_density_destroy(ld_density *d) { delete d; }
+int ld_density_info(const ld_density *d, uint64_t *n_voxels, uint64_t *s_e, uint64_t *s_ee, double *scale) {
+    return guarded([&] {
+        if (!d) throw ld::Error(LD_ERR_INVALID, "null density");
+        if (n_voxels) *n_voxels = d->impl.voxels();
+        if (s_e) *s_e = d->impl.s_e();
+        if (s_ee) *s_ee = d->impl.s_ee();
+        if (scale) *scale = d->impl.scale();
+    });
+}
+int ld_density_voxels(const ld_density *d, uint32_t *voxels_out) {
+    return guarded([&] {
+        if (!d || !voxels_out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        const std::vector<uint16_t> &E = d->impl.E();
+        for (size_t v = 0; v < E.size(); v++) voxels_out[v] = E[v];
+    });
+}
+int ld_density_kernel(uint32_t sigma, uint32_t *table_out, uint32_t *length_out, uint32_t *shift_out) {
+    return guarded([&] {
+        const ld::DensityKernel k = ld::density_kernel(sigma);
+        if (table_out) std::copy(k.table.begin(), k.table.end(), table_out);
+        if (length_out) *length_out = (uint32_t)k.table.size();
+        if (shift_out) *shift_out = k.shift;
+    });
+}
+int ld_complex_density_fit(ld_complex *c, ld_density *d, size_t n, const double *poses, size_t stride, uint32_t sigma, ld_density_sums *out) {
+    return guarded([&] {
+        if (!c || !d) throw ld::Error(LD_ERR_INVALID, "null argument");
+        c->impl.density_fit(d->impl, n, poses, stride, sigma, out);
+    });
+}
+int ld_complex_simulate_density(ld_complex *c, ld_density *d, size_t n, const double *poses, size_t stride, uint32_t sigma, uint32_t *grid) {
+    return guarded([&] {
+        if (!c || !d) throw ld::Error(LD_ERR_INVALID, "null argument");
+        c->impl.simulate_density(d->impl, n, poses, stride, sigma, grid);
+    });
+}
+int ld_density_scores(const ld_density *d, size_t n, const ld_density_sums *sums, double *cc, double *ccm, double *inside) {
+    return guarded([&] {
+        if (!d) throw ld::Error(LD_ERR_INVALID, "null density");
+        d->impl.scores(n, sums, cc, ccm, inside);
+    });
+}
+int ld_complex_density_chunk(ld_complex *c, size_t poses) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.density_chunk(poses);
+    });
 }
 int ld_complex_set_reference(ld_complex *c, const char *ref_receptor_pdb, const char *ref_ligand_pdb, double contact_cutoff,
                              double interface_cutoff) {

@@ -18,6 +18,8 @@
 
 namespace ld {
 
+class Density;
+
 // C = llrint(cutoff * 1000), 1 .. 30000, of a contact cutoff in A (lightdock_hip.h, "Interface contacts"); `message` otherwise.
 long long cutoff_thousandths(double cutoff, const char *message);
 // The element of an ATOM / HETATM record: columns 77-78, trimmed and upper-cased; a record too short for them or a blank
@@ -63,6 +65,10 @@ class Complex {
     void distance_histogram(size_t n, const double *poses, size_t stride, uint32_t width, size_t bins, uint32_t *counts);
     void saxs(size_t n, const double *poses, size_t stride, uint32_t width, size_t bins, const double *q, size_t n_q, double *intensity,
               uint32_t *counts);
+    // Density fit (lightdock_hip.h, "Density fit"; emfit.cpp)
+    void density_chunk(size_t poses) { density_chunk_ = poses; }  // poses a chunk; 0: as many as 256 MiB hold
+    void density_fit(Density &map, size_t n, const double *poses, size_t stride, uint32_t sigma, ld_density_sums *out);
+    void simulate_density(Density &map, size_t n, const double *poses, size_t stride, uint32_t sigma, uint32_t *grid);
     // Model quality against a reference complex (lightdock_hip.h, "Model quality")
     void set_reference(const char *ref_receptor_pdb, const char *ref_ligand_pdb, double contact_cutoff, double interface_cutoff);
     void reference_counts(uint32_t *out) const;  // 6: matched rec, matched lig, native pairs, rec fit, lig fit, interface fit
@@ -81,6 +87,7 @@ class Complex {
     void init_saxs();  // the atoms that take part in the scattering, from the constructor
     void saxs_run(size_t n, const double *poses, size_t stride, uint32_t width, size_t bins, const double *q, size_t n_q,
                   double *intensity, uint32_t *counts);
+    void density_run(Density &map, size_t n, const double *poses, size_t stride, uint32_t sigma, ld_density_sums *out, uint32_t *grid);
     FccCluster::Sets pair_sets(size_t n, const double *poses, size_t stride, long long C, bool fill, size_t cap, int **d_overflow_out);
     void destroy();
 
@@ -97,6 +104,8 @@ class Complex {
     std::vector<uint8_t> saxs_class_[2];  // every atom of a side, 255 for one that takes no part
     uint32_t saxs_class_atoms_[kSaxsClasses] = {};
     size_t saxs_chunk_ = 0;
+    size_t density_chunk_ = 0;
+    DeviceBuffer d_density_;  // density_run's receptor grid and the voxels of a chunk
     // what set_reference derived; `set` only once all of it stands
     struct Reference {
         bool set = false;
