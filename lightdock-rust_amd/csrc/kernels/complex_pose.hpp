@@ -71,6 +71,7 @@ __device__ __forceinline__ double thousandths(double x) {
 }
 
 // round(rmsd, 4) <= cutoff with rmsd = sqrt(S / n) in A, S in thousandths^2.  Non-decreasing in S.
+// Exactly: 400 S < n (2K + 1)^2, K the largest integer with K / 1e4 <= cutoff; only at equality does the rounding here decide.
 __device__ __forceinline__ bool within_cutoff(double S, double n, double cutoff) {
     return rint(sqrt(S * 1e-6 / n) * 1e4) / 1e4 <= cutoff;
 }

@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 
+import bsas_edges
 from test_analysis_cpu import CZY, Restated, analyse_module, czy_restated
 
 pytestmark = pytest.mark.gpu
@@ -95,11 +96,15 @@ def test_knife_edge_decisions_equal_the_restatement(czy_rigid):
     got = czy_rigid.cluster(poses[None], scoring[None], 4.0)
     want_of, want_reps, knife = rs.bsas(poses, scoring, 4.0)
     print("knife-edge comparisons: %d" % knife)
-    same = np.array_equal(got["cluster_of"][0], want_of) and list(got["representatives"][0][:len(want_reps)]) == want_reps
-    assert same or knife > 0
+    # the exact integer rule on the thousandths the tool re-reads (tests/bsas_edges.py): n = 175 admits no tie (16 does not
+    # divide it), so nothing is excused
+    T = np.array([np.rint(rs.backbone_printed(p) * 1000.0).astype(np.int64).ravel() for p in poses])
+    exact_of, exact_reps, ties = bsas_edges.bsas(T, nb, scoring, 4.0)
+    assert ties == 0 and nb % 16 != 0
+    check_swarm(got, 0, exact_of, exact_reps)
     if knife == 0:
         check_swarm(got, 0, want_of, want_reps)
-    assert 1 < len(want_reps)   # the steps do cross the cutoff
+    assert 1 < len(exact_reps)   # the steps do cross the cutoff
 
 
 def test_equal_scores_cluster_in_glowworm_order(czy_rigid):

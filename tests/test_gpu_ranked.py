@@ -10,6 +10,7 @@ import sys
 import numpy as np
 import pytest
 
+import bsas_edges
 from conftest import GOLDEN
 from test_analysis_cpu import CZY, Restated, analyse_module, czy_restated
 from test_gpu_analysis import LIG, REC, perturbed_czy, random_poses
@@ -192,12 +193,15 @@ def test_knife_edge_decisions_equal_the_restatement(czy_rigid, rr_rigid, atoms):
     got = czy_rigid.cluster_ranked(poses, scoring, 4.0, atoms)
     want_of, want_reps, knife = rr_rigid.cluster(poses, scoring, 4.0, atoms)
     print("knife-edge comparisons: %d" % knife)
-    k = len(want_reps)
-    same = (np.array_equal(got["cluster_of"][0], want_of) and int(got["n_clusters"][0]) == k
-            and list(got["representatives"][0][:k]) == want_reps)
-    assert same or knife > 0
+    # the exact integer rule (tests/bsas_edges.py): n = 175 and n = 7 admit no tie (16 divides neither), so nothing is excused
+    n_atoms = len(rr_rigid.atoms[atoms])
+    T = bsas_edges.thousandths_of(rr_rigid.posed(poses, rr_rigid.atoms[atoms])).reshape(len(poses), -1)   # the decimal expansion's
+    exact_of, exact_reps, ties = bsas_edges.bsas(T, n_atoms, scoring, 4.0)
+    assert ties == 0 and n_atoms % 16 != 0
+    check(got, exact_of, exact_reps)
     if knife == 0:
         check(got, want_of, want_reps)
+    k = len(exact_reps)
     assert 1 < k   # the steps do cross the cutoff
     if atoms == "complex":
         assert same_words(got, czy_rigid.cluster(poses[None], scoring[None], 4.0))   # the same predicate, bit for bit
