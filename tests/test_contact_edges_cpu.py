@@ -1,0 +1,411 @@
+"""The cases of tests/contact_edges.py are what they claim (CPU only).  A plain replay of the walk of complex_contacts
+(kernels/cluster.hip) and complex_pair_sets (kernels/fcc.hip) -- the whole ligand's box, then the boxes of the groups of 8 ligand
+residues, then single residue boxes, then 8 x 8 atom tiles in order, stopping at the first hit -- runs on the oracle's integers
+and says, for every pose, at which level the chosen pair was decided, in which tile, and where in the walk the pair stands.  The
+coverage table the file prints has a line for every item the cases are built for, each realised "in" (d^2 == C^2) and "out"."""
+import collections
+import os
+import re
+import time
+
+import numpy as np
+import pytest
+
+import contact_edges as ce
+from test_analysis_cpu import ROOT
+from test_contacts_cpu import ContactsRestated
+
+KERNELS = os.path.join(ROOT, "lightdock-rust_amd", "csrc", "kernels")
+
+
+# ---- the replay -----------------------------------------------------------------------------------------------------------------
+
+def boxes(xyz, start):
+    return np.minimum.reduceat(xyz, start[:-1], axis=0), np.maximum.reduceat(xyz, start[:-1], axis=0)
+
+
+def gap2(lo_a, hi_a, lo_b, hi_b):
+    """The squared distance of two boxes: per axis the gap between the intervals, 0 where they overlap.  int64, no clamp."""
+    g = np.maximum(np.maximum(lo_a - hi_b, lo_b - hi_a), 0)
+    return (g * g).sum(axis=-1)
+
+
+Walk = collections.namedtuple("Walk", "rec lig keys tiles levels")
+
+
+def replay(sh, pose, C, pair=None):
+    """The walk on the posed integers -> Walk: the bits, the ascending keys, {(r, l): first tile with a hit or None} of every residue
+    pair that reached the atoms, and, for `pair` = (R, L), the squared gaps (whole, group, residue) of its three box tests."""
+    rec, lig = ce.posed(sh, pose)
+    C2 = C * C
+    rlo, rhi = boxes(rec, sh.rec_start)
+    llo, lhi = boxes(lig, sh.lig_start)
+    first = np.arange(0, sh.n_lig_res, ce.RES_GROUP)
+    glo, ghi = np.minimum.reduceat(llo, first, axis=0), np.maximum.reduceat(lhi, first, axis=0)
+    wlo, whi = glo.min(axis=0), ghi.max(axis=0)
+    rec_bits, lig_bits = np.zeros(sh.n_rec_res, dtype=bool), np.zeros(sh.n_lig_res, dtype=bool)
+    keys, tiles = [], {}
+    whole = gap2(rlo, rhi, wlo, whi)
+    for r in np.flatnonzero(whole <= C2):
+        a0, a1 = int(sh.rec_start[r]), int(sh.rec_start[r + 1])
+        for g in np.flatnonzero(gap2(rlo[r], rhi[r], glo, ghi) <= C2):
+            ls = np.arange(g * ce.RES_GROUP, min((g + 1) * ce.RES_GROUP, sh.n_lig_res))
+            for l in ls[gap2(rlo[r], rhi[r], llo[ls], lhi[ls]) <= C2]:
+                b0, b1 = int(sh.lig_start[l]), int(sh.lig_start[l + 1])
+                hit = None
+                for ta in range(a0, a1, ce.TILE):
+                    for tb in range(b0, b1, ce.TILE):
+                        d = rec[ta:min(ta + ce.TILE, a1), None, :] - lig[None, tb:min(tb + ce.TILE, b1), :]
+                        if ((d * d).sum(axis=-1) <= C2).any():
+                            hit = (ta - a0, tb - b0)
+                            break
+                    if hit:
+                        break
+                tiles[(int(r), int(l))] = hit
+                if hit:
+                    rec_bits[r] = lig_bits[l] = True
+                    keys.append(int(r) * sh.n_lig_res + int(l))
+    levels = None
+    if pair is not None:
+        R, L = pair
+        g = L // ce.RES_GROUP
+        levels = (int(whole[R]), int(gap2(rlo[R], rhi[R], glo[g], ghi[g])), int(gap2(rlo[R], rhi[R], llo[L], lhi[L])))
+    return Walk(rec_bits, lig_bits, np.array(sorted(keys), dtype=np.int64), tiles, levels)
+
+
+def place_in_walk(R, L):
+    """Where the kernels meet the pair: receptor residue (base + lane) * WAVES + wave; ligand group lg0 + group lane, residue lane."""
+    idx, grp = R // ce.WAVES, L // ce.RES_GROUP
+    return {"wave": R % ce.WAVES, "base": idx // 64 * 64, "lane": idx % 64, "group": grp, "lg0": grp // 64 * 64, "group_lane": grp % 64,
+            "residue_lane": L % ce.RES_GROUP}
+
+
+@pytest.fixture(scope="module")
+def walks():
+    """case name -> [Walk] of every pose, once."""
+    return {c.name: [replay(ce.shape(c.shape), p, c.C, None if p.pair is None else (p.pair[0], p.pair[2])) for p in c.poses]
+            for c in ce.all_cases()}
+
+
+# ---- coverage -------------------------------------------------------------------------------------------------------------------
+
+class Coverage:
+    def __init__(self):
+        self.rows = collections.OrderedDict()
+
+    def add(self, item, kind):
+        self.rows.setdefault(item, {"in": 0, "out": 0})[kind] += 1
+
+    def check(self, items):
+        missing = [(i, k) for i in items for k in ("in", "out") if self.rows.get(i, {"in": 0, "out": 0})[k] == 0]
+        assert not missing, missing
+
+    def show(self, title):
+        print("\n%s\n%-64s %6s %6s" % (title, "item", "in", "out"))
+        for item, n in self.rows.items():
+            print("%-64s %6d %6d" % (item, n["in"], n["out"]))
+
+
+def deciding(sh, pose, ex):
+    """The one atom pair of the pose's two residues at the least d^2: (ia, ib, d^2, vector ligand - receptor)."""
+    R, ia, L, ib = pose.pair
+    near = ex.near
+    assert np.all(sh.rec_of[near[:, 0]] == R) and np.all(sh.lig_of[near[:, 1]] == L), pose   # nothing else within 2 C
+    rec, lig = ce.posed(sh, pose)
+    a0, b0 = int(sh.rec_start[R]), int(sh.lig_start[L])
+    d = rec[a0:int(sh.rec_start[R + 1]), None, :] - lig[None, b0:int(sh.lig_start[L + 1]), :]
+    d2 = (d * d).sum(axis=-1)
+    a, b = np.nonzero(d2 == d2.min())
+    assert len(a) == 1, pose
+    a, b = int(a[0]), int(b[0])
+    assert "far" in pose.tags or [a0 + a, b0 + b, int(d2[a, b])] in near.tolist(), pose
+    return a, b, int(d2[a, b]), tuple(int(x) for x in -d[a, b])
+
+
+def atom_names(size, index):
+    return [name for name, at in (("first", 0), ("8th", 7), ("9th", 8), ("last", size - 1)) if at == index]
+
+
+# ---- tests ----------------------------------------------------------------------------------------------------------------------
+
+def test_the_constants_are_the_kernels():
+    cluster, fcc = open(os.path.join(KERNELS, "cluster.hpp")).read(), open(os.path.join(KERNELS, "fcc.hpp")).read()
+    assert int(re.search(r"kResGroup = (\d+);", cluster).group(1)) == ce.RES_GROUP
+    assert int(re.search(r"kContactThreads = (\d+);", cluster).group(1)) == 64 * ce.WAVES
+    assert int(re.search(r"kPairThreads = (\d+);", fcc).group(1)) == 64 * ce.WAVES == ce.SCAN_CHUNK
+    assert re.search(r"kMaxBoxLdsBytes = 40 << 10;", cluster) and ce.MAX_BOX_LDS_BYTES == 40 << 10
+    assert re.search(r"kCoordBound = 1000000000;", open(os.path.join(KERNELS, "cluster.hip")).read()) and ce.COORD_BOUND == 10 ** 9
+    base, big, motif = ce.shape("base"), ce.shape("big"), ce.shape("motif")
+    assert (base.n_rec_res, base.n_lig_res, base.n_lig_grp, base.n_boxes) == (520, 517, 65, 1102) and base.boxes_in_lds
+    assert base.n_lig_res - 64 * ce.RES_GROUP == 5 and ce.shape("flex").boxes_in_lds
+    assert big.n_boxes == 520 + 1100 + 138 > 1706 and not big.boxes_in_lds
+    assert base.n_rec_res * base.lig_words == 520 * 17 and motif.n_rec_res * motif.lig_words == 648 > ce.SCAN_CHUNK
+
+
+def test_the_files_hold_the_integers_and_posing_is_exact(tmp_path):
+    """The PDB files the builders write, read back and posed in f64 by the suite's restatement of the device's posing: every
+    coordinate of every pose is within 1e-3 thousandths of the integer the oracle computes with, so "%.3f" prints that integer."""
+    n_poses = 0
+    for name in ce.SHAPES:
+        sh = ce.shape(name)
+        rec, lig, modes = ce.write_complex(sh, str(tmp_path))
+        rs = ContactsRestated(rec, lig, modes)
+        assert np.array_equal(rs.rec_of, sh.rec_of) and np.array_equal(rs.lig_of, sh.lig_of)
+        assert len(set(rs.rec_ids)) == sh.n_rec_res and len(set(rs.lig_ids)) == sh.n_lig_res
+        assert np.array_equal(np.rint(rs.rec * 1000.0), sh.rec) and np.array_equal(np.rint(rs.lig * 1000.0), sh.lig)
+        first_lines = [l for l in open(rec)][:2]
+        assert first_lines[0][12:16].strip() == "CA"
+        for case in ce.all_cases():
+            if case.shape != name:
+                continue
+            for pose, row in zip(case.poses, ce.rows(sh, case.poses)):
+                x = rs.pose(row) * 1000.0
+                want = np.concatenate(ce.posed(sh, pose))
+                assert np.abs(x - want).max() < 1e-3, (case.name, pose)
+                n_poses += 1
+    assert n_poses == sum(len(c.poses) for c in ce.all_cases())
+
+
+def test_the_replay_is_the_oracle_on_every_pose(walks):
+    for case in ce.all_cases():
+        for i, (e, w) in enumerate(zip(ce.expected(case.name), walks[case.name])):
+            where = (case.name, i)
+            assert np.array_equal(e.rec, w.rec) and np.array_equal(e.lig, w.lig) and np.array_equal(e.keys, w.keys), where
+            assert np.all(np.diff(e.keys) > 0), where
+            assert set(k for k, hit in w.tiles.items() if hit) == set((int(k) // ce.shape(case.shape).n_lig_res,
+                                                                       int(k) % ce.shape(case.shape).n_lig_res) for k in e.keys), where
+    print("%d cases, %d poses" % (len(ce.CASE_NAMES), sum(len(c.poses) for c in ce.all_cases())))
+
+
+def test_the_oracle_alone_is_quick():
+    """A wall-clock bound: typically 3.6 to 4.8 s on an idle core (about 2e8 atom pairs, int64).  A failure on a loaded machine
+    says nothing about the cases; a failure on an idle one says the case list has grown too heavy for the suite."""
+    ce.expected.cache_clear()
+    t0 = time.perf_counter()
+    n = sum(len(ce.expected(name)) for name in ce.CASE_NAMES)
+    took = time.perf_counter() - t0
+    print("the all-pairs oracle on %d poses of %d cases: %.1f s" % (n, len(ce.CASE_NAMES), took))
+    assert took < 10.0
+
+
+def test_every_pair_is_alone_and_at_its_distance():
+    """The chosen pair is the only one of its residues at the least d^2, that d^2 is the intended integer -- C^2 for "in", above it
+    for "out" -- and nothing else of the pose lies within 2 C; a pose without a pair has no atom pair within 2 C at all."""
+    for case in ce.all_cases():
+        sh, C2 = ce.shape(case.shape), case.C * case.C
+        for pose, ex in zip(case.poses, ce.expected(case.name)):
+            if pose.pair is None:
+                if "motif" not in pose.tags:
+                    assert len(ex.near) == 0 and len(ex.keys) == 0, (case.name, pose)
+                continue
+            ia, ib, d2, v = deciding(sh, pose, ex)
+            assert (ia, ib) == (pose.pair[1], pose.pair[3]) and d2 == pose.S == sum(x * x for x in v), (case.name, pose)
+            if pose.kind == "in":
+                assert (d2 == C2 or (case.C == 1 and d2 == 0)) and list(ex.keys) == [pose.pair[0] * sh.n_lig_res + pose.pair[2]], (case.name, pose)
+                assert int(ex.rec.sum()) == 1 and int(ex.lig.sum()) == 1
+            else:
+                assert pose.kind == "out" and d2 > C2 and len(ex.keys) == 0 and not ex.rec.any() and not ex.lig.any(), (case.name, pose)
+                if "far" not in pose.tags:
+                    assert d2 in (C2 + 1, (case.C + 1) ** 2) or (case.C == 1 and d2 == 3), (case.name, pose)
+
+
+def test_threshold_vectors_in_every_order_and_sign():
+    cov = Coverage()
+    for name, C in (("vectors-base-C5000", 5000), ("vectors-small-C30000", 30000)):
+        case = ce.case_named(name)
+        sh = ce.shape(case.shape)
+        seen = collections.defaultdict(set)
+        for pose, ex in zip(case.poses, ce.expected(name)):
+            v = deciding(sh, pose, ex)[3]
+            axes = sum(x != 0 for x in v)
+            seen[(pose.kind, sum(x * x for x in v), axes)].add(v)
+            cov.add("C = %d: d^2 == C^2 on %d axes / the sum above next to it" % (C, pose.tags[1]), pose.kind)
+        C2 = C * C
+        assert {k: len(s) for k, s in seen.items()} == {("in", C2, 1): 6, ("in", C2, 2): 24, ("in", C2, 3): 48, ("out", C2 + 1, 2): 24,
+                                                        ("out", C2 + 1, 3): 96, ("out", (C + 1) ** 2, 1): 6}
+        for (kind, S, axes), vectors in seen.items():       # every order and every sign of one triple
+            triples = {tuple(sorted(abs(x) for x in v)) for v in vectors}
+            assert len(vectors) == sum(len(ce.arrangements(t)) for t in triples), (kind, S, axes)
+        assert {p.rot for p in case.poses} == set("IXYZ")
+    case = ce.thousandth_case()
+    assert case.C == 1
+    got = collections.defaultdict(set)
+    for pose, ex in zip(case.poses, ce.expected(case.name)):
+        v = deciding(ce.shape("base"), pose, ex)[3]
+        got[pose.kind].add(v)
+        cov.add("C = 1 (cutoff 0.001): (0,0,0), (1,0,0) in; (1,1,0) out", pose.kind)
+    assert got["in"] == {(0, 0, 0)} | set(ce.arrangements((1, 0, 0))) and set(ce.arrangements((1, 1, 0))) <= got["out"]
+    for C in (30000, 5000):
+        case = ce.far_case(C)
+        for pose, ex in zip(case.poses, ce.expected(case.name)):
+            assert not ex.rec.any() and not ex.lig.any()
+            cov.add("far, C = %d: an axis difference of %d" % (C, pose.tags[1]), "out")
+        for d in ce.FAR + (65536,):
+            assert cov.rows["far, C = %d: an axis difference of %d" % (C, d)]["out"] >= 2
+    # the far poses: nothing within 2 C, and the two molecules as far apart as the coordinate bound allows
+    flex = ce.edge_case("flex")
+    pose = [p for p in flex.poses if p.tags == ("far", "1.9e6")][0]
+    rec, lig = ce.posed(ce.shape("flex"), pose)
+    apart = int(lig[:, 2].min() - rec[:, 2].max())
+    assert 1890000000 <= apart < 2 ** 31 and int(np.abs(rec).max()) <= ce.COORD_BOUND and int(np.abs(lig).max()) <= ce.COORD_BOUND
+    cov.add("far: the molecules %.3e A apart (flex)" % (apart / 1000.0), "out")
+    items = [i for i in cov.rows if not i.startswith("far")]
+    cov.check(items)
+    cov.show("threshold vectors (far cases are out by definition)")
+
+
+LEVELS = {"a": "whole, group and residue box all AT the atom distance", "b": "whole box gap 0; group and residue box at equality",
+          "c": "whole and group box gap 0; residue box at equality", "d": "every box gap below C; the atom test decides"}
+
+
+def level_of(gaps, d2, C):
+    """The item a pose realises, from the replay's numbers alone: (level, kind) or None."""
+    C2, beyond = C * C, (C + 1) ** 2
+    whole, group, residue = gaps
+    if d2 == C2:
+        if (whole, group, residue) == (C2, C2, C2):
+            return "a", "in"
+        if whole == 0 and (group, residue) == (C2, C2):
+            return "b", "in"
+        if (whole, group) == (0, 0) and residue == C2:
+            return "c", "in"
+        if max(gaps) < C2:
+            return "d", "in"
+    elif d2 > C2:
+        if whole == beyond:
+            return "a", "out"              # the whole box rejects, one thousandth beyond equality
+        if whole == 0 and group == beyond:
+            return "b", "out"
+        if (whole, group) == (0, 0) and residue == beyond:
+            return "c", "out"
+        if max(gaps) < C2:
+            return "d", "out"
+    return None
+
+
+@pytest.mark.parametrize("shape_name", ["base", "flex", "big"])
+def test_levels_places_and_atoms(walks, shape_name):
+    """The edge case of a shape: the level that decides, the places in the walk, the deciding atom, the scan chunks."""
+    case = ce.edge_case(shape_name)
+    sh, C, C2 = ce.shape(shape_name), case.C, case.C * case.C
+    cov = Coverage()
+    for pose, ex, w in zip(case.poses, ce.expected(case.name), walks[case.name]):
+        if pose.pair is None:
+            cov.add("pair sets: a pose with no key at all", "out")
+            continue
+        R, _, L, _ = pose.pair
+        ia, ib, d2, v = deciding(sh, pose, ex)
+        kind, at = pose.kind, place_in_walk(R, L)
+        # the level, from the replay's numbers; the replay rejects where the numbers say
+        decided = "atoms" if max(w.levels) <= C2 else ("whole", "group", "residue")[[g > C2 for g in w.levels].index(True)]
+        assert ((R, L) in w.tiles) == (decided == "atoms"), pose
+        level = level_of(w.levels, d2, C)
+        if pose.tags[0] == "level":
+            # in the long ligand residues 517 .. 519 of the next row share group 64 with 512 .. 516 and span all of y: 512 is no
+            # longer at the group's end, so the b built on it is a c there; nothing else moves
+            built = "c" if shape_name == "big" and pose.tags[1] == "b" and L == 512 else pose.tags[1]
+            assert level == (built, kind), (pose, w.levels, level)
+            if kind == "out" and level[0] != "d":      # only the box arithmetic separates the twins: the other axes are inside C
+                axis = int(np.argmax(np.abs(v)))
+                assert all(abs(x) <= 1 for k, x in enumerate(v) if k != axis) and abs(v[axis]) == C + 1
+        if level is not None:
+            cov.add("level %s: %s" % (level[0], LEVELS[level[0]]), level[1])
+        cov.add("decided by: %s" % decided, kind)
+        # the place
+        if pose.tags[0] == "walk":
+            if pose.tags[1] in ("R", "both"):
+                cov.add("walk: R = %d (wave %d, base %d, lane %d)" % (R, at["wave"], at["base"], at["lane"]), kind)
+            if pose.tags[1] in ("L", "both"):
+                cov.add("walk: L = %d (lg0 %d, group %d, residue lane %d)" % (L, at["lg0"], at["group"], at["residue_lane"]), kind)
+        if at["base"] > 0:
+            cov.add("the second round of 64 x 8 receptor residues", kind)
+        if at["lg0"] > 0 and decided in ("residue", "atoms"):
+            cov.add("the second round of 64 ligand groups", kind)
+        if at["group"] == sh.n_lig_grp - 1 and sh.n_lig_res % ce.RES_GROUP and decided in ("residue", "atoms"):
+            cov.add("the partial last group", kind)
+        # the atom
+        if decided == "atoms":
+            tile = (ia // ce.TILE * ce.TILE, ib // ce.TILE * ce.TILE)
+            if kind == "in":
+                assert w.tiles[(R, L)] == tile, (pose, w.tiles[(R, L)])
+            else:
+                assert w.tiles[(R, L)] is None
+            for side, n, index in ((0, sh.size(0, R), ia), (1, sh.size(1, L), ib)):
+                if n > 1 and pose.tags[0] == "atom":
+                    for name in atom_names(n, index):
+                        cov.add("atom: the %s of %d, %s" % (name, n, ("receptor", "ligand")[side]), kind)
+                if n % ce.TILE and index // ce.TILE == n // ce.TILE and n > ce.TILE:
+                    cov.add("a last partial tile of the %s holds the deciding atom" % ("receptor", "ligand")[side], kind)
+            if sh.size(0, R) > 1 and sh.size(1, L) > 1:
+                cov.add("atom: both residues of several atoms (%d: %d, %d: %d)" % (sh.size(0, R), ia, sh.size(1, L), ib), kind)
+            if tile[1] > 0:
+                cov.add("the hit is beyond the first ligand tile", kind)
+        # the pair bitmap
+        word = R * sh.lig_words + L // 32
+        if word % ce.SCAN_CHUNK == 0 and word:
+            cov.add("pair sets: the first word of a scan chunk", kind)
+        if word % ce.SCAN_CHUNK == ce.SCAN_CHUNK - 1 or word == sh.n_rec_res * sh.lig_words - 1:
+            cov.add("pair sets: the last word of a scan chunk", kind)
+        cov.add("rotation %s" % pose.rot, kind)
+        if pose.amp:
+            cov.add("a flexed receptor (amplitude not 0)", kind)
+    cov.show("%s: %d poses, %d boxes (%s)" % (case.name, len(case.poses), sh.n_boxes, "LDS" if sh.boxes_in_lds else "global memory"))
+    items = ["level %s: %s" % kv for kv in LEVELS.items()] + ["decided by: atoms"]
+    items += ["the second round of 64 x 8 receptor residues", "the second round of 64 ligand groups",
+              "a last partial tile of the receptor holds the deciding atom", "a last partial tile of the ligand holds the deciding atom",
+              "the hit is beyond the first ligand tile", "pair sets: the first word of a scan chunk", "pair sets: the last word of a scan chunk",
+              "rotation I", "rotation X"]
+    items += ["walk: R = %d (wave %d, base %d, lane %d)" % (R, R % 8, R // 8 // 64 * 64, R // 8 % 64) for R in ce.WALK_R]
+    items += ["walk: L = %d (lg0 %d, group %d, residue lane %d)" % (L, L // 8 // 64 * 64, L // 8, L % 8) for L in ce.WALK_L]
+    for side in ("receptor", "ligand"):
+        items += ["atom: the %s of %d, %s" % (name, n, side) for n, names in ((8, ("first", "8th", "last")), (9, ("first", "8th", "9th", "last")),
+                                                                                 (17, ("first", "8th", "9th", "last"))) for name in names]
+    if shape_name != "big":
+        items.append("the partial last group")
+    if shape_name == "flex":
+        items.append("a flexed receptor (amplitude not 0)")
+    cov.check(items)
+    assert cov.rows["pair sets: a pose with no key at all"]["out"] >= 1
+    for level in ("whole", "group", "residue"):
+        assert cov.rows["decided by: %s" % level]["out"] >= 1 and cov.rows["decided by: %s" % level]["in"] == 0
+    assert sum(1 for i in cov.rows if i.startswith("atom: both residues")) >= 5
+
+
+def test_the_skip_of_complex_contacts(walks):
+    """The six residues of every copy: R1-L1, R2-L2 and R1-L2 touch, so R1-L2 can be met with both bits set; R1-L3 with only the
+    receptor's, R3-L1 with only the ligand's; L3 and R3 touch nothing else.  At rest every one of them is at C exactly."""
+    case, sh = ce.motif_case(), ce.shape("motif")
+    ex = ce.expected(case.name)
+    C2 = case.C * case.C
+    touching = set()
+    for rs, ls in ce.MOTIFS:
+        at = dict(zip(("R1", "R2", "R3"), rs))
+        at.update(zip(("L1", "L2", "L3"), ls))
+        touching |= {(at[r], at[l]) for r, l in ce.MOTIF_PAIRS}
+    want = np.array(sorted(r * sh.n_lig_res + l for r, l in touching), dtype=np.int64)
+    cov = Coverage()
+    for pose, e, w in zip(case.poses, ex, walks[case.name]):
+        pairs = {(int(a), int(b)) for a, b in e.near[:, :2]}          # one atom a residue: atoms are residues
+        if pose.kind is None:
+            assert not pairs and len(e.keys) == 0
+            continue
+        assert pairs == touching                                      # nothing else within 2 C
+        assert set(int(x) for x in e.near[:, 2]) == {C2 if pose.kind == "in" else C2 + 1}
+        assert np.array_equal(e.keys, want if pose.kind == "in" else want[:0])
+        for (rs, ls) in ce.MOTIFS:
+            R1, R2, R3 = rs
+            L1, L2, L3 = ls
+            order = "%s wave, L3 %s" % ("R1 and R3 in one" if R1 % 8 == R3 % 8 else "R1 and R3 in two", "behind a partner of R1" if L3 > min(L1, L2) else "first")
+            cov.add("skip: R1-L2 with R1-L1 and R2-L2 (both bits may stand)", pose.kind)
+            cov.add("skip: R1-L3, L3 touches nothing else; %s" % order, pose.kind)
+            cov.add("skip: R3-L1, R3 touches nothing else; R3 %s R1" % ("behind" if R3 // 8 > R1 // 8 else "before"), pose.kind)
+        if pose.kind == "in":
+            assert sorted(np.flatnonzero(e.rec)) == sorted({r for r, _ in touching}) and sorted(np.flatnonzero(e.lig)) == sorted({l for _, l in touching})
+            words = sorted({r * sh.lig_words + l // 32 for r, l in touching})
+            assert ce.SCAN_CHUNK - 1 in words and ce.SCAN_CHUNK in words and len(e.keys) == 5 * len(ce.MOTIFS)
+            # L3 behind another partner of R1 in R1's own walk: an `||` in the skip loses L3's bit whatever the waves do
+            assert sum(1 for _, (L1, L2, L3) in ce.MOTIFS if L3 > min(L1, L2)) >= 4
+            # R3 behind R1 in R1's wave: an `||` loses R3's bit whatever the waves do
+            assert sum(1 for (R1, _, R3), _ in ce.MOTIFS if R1 % 8 == R3 % 8 and R3 > R1) >= 1
+    cov.check(list(cov.rows))
+    cov.show("motif: %d copies of six residues, %d poses" % (len(ce.MOTIFS), len(case.poses)))
