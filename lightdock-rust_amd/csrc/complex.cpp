@@ -1,5 +1,6 @@
-// complex.cpp -- the host side of the analysis half of a run: argument checks, workspace sizing and chunking, the launch
-// sequences of kernels/cluster.hpp, and ld_complex_write_pdb's text.
+// complex.cpp -- the host side of the analysis half of a run: argument checks, the workspace of every call (each block's
+// layout written once, for a Carver; chunks and slots by chunk_of), the launch sequences of kernels/cluster.hpp between
+// begin_timed and finish_timed, and ld_complex_write_pdb's text.
 #include "complex.hpp"
 
 #include <algorithm>
@@ -27,6 +28,11 @@ long long cutoff_thousandths(double cutoff, const char *message) {
     const long long C = std::llrint(scaled);
     if (C < 1 || C > 30000) throw Error(LD_ERR_INVALID, message);
     return C;
+}
+
+void check_scoring(size_t n, const double *scoring) {
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(scoring[i])) throw Error(LD_ERR_INVALID, "scoring " + std::to_string(i) + " is not finite");
 }
 
 std::string record_element(const char *line, size_t len) {
@@ -174,7 +180,7 @@ void Complex::upload_poses(size_t n, const double *poses, size_t stride) {
 
 void Complex::pose_all(size_t n, const double *poses, size_t stride, double *out) {
     const size_t per_pose = n_atoms() * 3 * sizeof(double);
-    const size_t chunk = std::max<size_t>(1, kClusterWorkspaceBytes / per_pose);
+    const size_t chunk = chunk_of(per_pose, n);
     upload_poses(n, poses, stride);
     for (size_t i0 = 0; i0 < n; i0 += chunk) {
         const size_t m = std::min(chunk, n - i0);
@@ -194,7 +200,11 @@ void Complex::coordinates(size_t n, const double *poses, size_t stride, double *
     if (n) pose_all(n, poses, stride, xyz_out);
 }
 
-// The end of a timed launch sequence (ev0_ was recorded in front of it): the overflow flag, the synchronisation, the time.
+void Complex::begin_timed(int *d_overflow) {
+    hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), stream_), "hipMemset");
+    hip_check(hipEventRecord(ev0_, stream_), "hipEventRecord");
+}
+
 void Complex::finish_timed(const int *d_overflow, const char *what, const char *overflow_message) {
     hip_check(hipEventRecord(ev1_, stream_), "hipEventRecord");
     int overflow = 0;
@@ -215,26 +225,26 @@ void Complex::cluster(size_t n_swarms, size_t n_glowworms, const double *poses, 
     if (!scoring || !cluster_of || !representatives || !n_clusters) throw Error(LD_ERR_INVALID, "null argument");
     const size_t n = n_swarms * n_glowworms;
     check_poses(n, poses, stride);
-    for (size_t i = 0; i < n; i++)
-        if (!std::isfinite(scoring[i])) throw Error(LD_ERR_INVALID, "scoring " + std::to_string(i) + " is not finite");
+    check_scoring(n, scoring);
 
     const int G = (int)n_glowworms, n_bb = (int)backbone_.size();
     const size_t per_swarm = (size_t)G * n_bb * 3 * sizeof(int32_t);
-    const size_t chunk = std::max<size_t>(1, kClusterWorkspaceBytes / per_swarm);
+    const size_t chunk = chunk_of(per_swarm, n_swarms);
     upload_poses(n, poses, stride);
     d_scores_.reserve(n * sizeof(double));
     hip_check(hipMemcpyAsync(d_scores_.ptr, scoring, n * sizeof(double), hipMemcpyHostToDevice, stream_), "hipMemcpy H2D scoring");
-    d_ids_.reserve(2 * n * sizeof(int32_t) + n_swarms * sizeof(uint32_t) + sizeof(int));
-    int32_t *d_cluster = static_cast<int32_t *>(d_ids_.ptr);
-    int32_t *d_reps = d_cluster + n;
-    uint32_t *d_count = reinterpret_cast<uint32_t *>(d_reps + n);
-    int *d_overflow = reinterpret_cast<int *>(d_count + n_swarms);
-    hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), stream_), "hipMemset");
-    d_ws_.reserve(std::min(chunk, n_swarms) * per_swarm);
+    int32_t *d_cluster, *d_reps;
+    uint32_t *d_count;
+    int *d_overflow;
+    carve_into(d_ids_, [&](Carver &c) {
+        d_cluster = c.take<int32_t>(n), d_reps = c.take<int32_t>(n);
+        d_count = c.take<uint32_t>(n_swarms), d_overflow = c.take<int>(1);
+    });
+    d_ws_.reserve(chunk * per_swarm);
     int32_t *d_ws = static_cast<int32_t *>(d_ws_.ptr);
     const double *d_poses = static_cast<const double *>(d_poses_.ptr);
     const double *d_scores = static_cast<const double *>(d_scores_.ptr);
-    hip_check(hipEventRecord(ev0_, stream_), "hipEventRecord");
+    begin_timed(d_overflow);
     for (size_t s0 = 0; s0 < n_swarms; s0 += chunk) {
         const int m = (int)std::min(chunk, n_swarms - s0);
         hip_check(launch_complex_pose_thousandths(dev_, d_poses + s0 * G * stride, stride, m, G, d_backbone_, n_bb, d_ws, d_overflow,
@@ -273,8 +283,7 @@ void Complex::cluster_ranked(size_t n, const double *poses, size_t stride, const
     }
     if (!scoring || !cluster_of || !representatives) throw Error(LD_ERR_INVALID, "null argument");
     check_poses(n, poses, stride);
-    for (size_t i = 0; i < n; i++)
-        if (!std::isfinite(scoring[i])) throw Error(LD_ERR_INVALID, "scoring " + std::to_string(i) + " is not finite");
+    check_scoring(n, scoring);
 
     // (scoring descending, index ascending); everything on the device is indexed by sorted position
     std::vector<int32_t> order(n);
@@ -285,15 +294,15 @@ void Complex::cluster_ranked(size_t n, const double *poses, size_t stride, const
     for (size_t p = 0; p < n; p++) std::copy(poses + (size_t)order[p] * stride, poses + (size_t)order[p] * stride + len, &sorted[p * len]);
 
     upload_poses(n, sorted.data(), len);
-    const size_t walk_bytes = (walk.size() * sizeof(uint32_t) + 7) / 8 * 8;
-    d_ids_.reserve(sizeof(RankedStatus) + walk_bytes + 2 * n * sizeof(int32_t));
-    RankedStatus *d_status = static_cast<RankedStatus *>(d_ids_.ptr);
-    uint32_t *d_walk = reinterpret_cast<uint32_t *>(d_status + 1);
+    RankedStatus *d_status;
+    uint32_t *d_walk;
     RankedLaunch r;
     r.n = (int)n;
     r.n_walk = (int)walk.size();
-    r.status = d_status;
-    r.state = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(d_walk) + walk_bytes);
+    carve_into(d_ids_, [&](Carver &c) {
+        r.status = d_status = c.take<RankedStatus>(1), d_walk = c.take<uint32_t>(walk.size());
+        r.state = c.take<int32_t>(2 * n);  // one array: the ids, then the leaders
+    });
     r.reps = r.state + n;
     d_ranked_ws_.reserve(n * per_pose);
     int32_t *d_ws = static_cast<int32_t *>(d_ranked_ws_.ptr);
@@ -336,18 +345,18 @@ void Complex::contacts(size_t n, const double *poses, size_t stride, double cuto
     if (rw + lw > kMaxContactWords) throw Error(LD_ERR_INVALID, "more than 524288 residues");
     // a workspace slot a workgroup in flight: the atoms, and the boxes when LDS does not hold them
     const size_t per_slot = (size_t)k.n_atoms * sizeof(int4) + (k.boxes_in_lds ? 0 : k.box_bytes());
-    const size_t slots = std::min(n, std::min<size_t>(kContactSlots, std::max<size_t>(1, kClusterWorkspaceBytes / per_slot)));
+    const size_t slots = chunk_of(per_slot, n, kContactSlots);
     upload_poses(n, poses, stride);
-    d_ids_.reserve(n * (rw + lw) * sizeof(uint32_t) + sizeof(int));
-    uint32_t *d_rec = static_cast<uint32_t *>(d_ids_.ptr);
-    uint32_t *d_lig = d_rec + n * rw;
-    int *d_overflow = reinterpret_cast<int *>(d_lig + n * lw);
-    hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), stream_), "hipMemset");
-    d_ws_.reserve(slots * per_slot);
-    int4 *d_atoms = static_cast<int4 *>(d_ws_.ptr);
-    hip_check(hipEventRecord(ev0_, stream_), "hipEventRecord");
+    uint32_t *d_rec, *d_lig;
+    int *d_overflow, *d_boxes;
+    int4 *d_atoms;
+    carve_into(d_ids_, [&](Carver &c) { d_rec = c.take<uint32_t>(n * rw), d_lig = c.take<uint32_t>(n * lw), d_overflow = c.take<int>(1); });
+    carve_into(d_ws_, [&](Carver &c) {
+        d_atoms = c.take<int4>(slots * k.n_atoms), d_boxes = c.take<int>(k.boxes_in_lds ? 0 : slots * 6 * (size_t)k.n_boxes());
+    });
+    begin_timed(d_overflow);
     hip_check(launch_complex_contacts(dev_, k, static_cast<const double *>(d_poses_.ptr), stride, n, (uint32_t)(C * C), slots, d_atoms,
-                                      reinterpret_cast<int *>(d_atoms + slots * k.n_atoms), d_rec, d_lig, d_overflow, stream_),
+                                      d_boxes, d_rec, d_lig, d_overflow, stream_),
               "complex_contacts launch");
     finish_timed(d_overflow, "complex_contacts", "a posed coordinate is beyond +-1.0e6 A");
     if (rec_bits) hip_check(hipMemcpy(rec_bits, d_rec, n * rw * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy D2H");
@@ -374,24 +383,24 @@ void Complex::sasa(size_t n, const double *poses, size_t stride, double probe, u
     d.e_max = sasa_r_max_ + d.probe;
     const bool atoms = free_counts || bound_counts;
     const size_t n_all = n_atoms(), per_slot = sasa_slot_bytes(d.n_part);
-    const size_t slots = std::min(n, std::min<size_t>(kSasaSlots, std::max<size_t>(1, kClusterWorkspaceBytes / per_slot)));
+    const size_t slots = chunk_of(per_slot, n, kSasaSlots);
     // per-atom counts leave in chunks of poses; nothing reaches the caller before the overflow flag is known
-    const size_t chunk = atoms ? std::min(n, std::max<size_t>(1, kClusterWorkspaceBytes / (2 * n_all))) : n;
-    const size_t counts_bytes = atoms ? (chunk * n_all + 15) / 16 * 16 : 0;
+    const size_t chunk = atoms ? chunk_of(2 * n_all, n) : n, counts = atoms ? chunk * n_all : 0;
     std::vector<uint8_t> h_free(atoms ? n * n_all : 0), h_bound(atoms ? n * n_all : 0);
     upload_poses(n, poses, stride);
-    d_ids_.reserve(n * 4 * sizeof(uint64_t) + 16 + 2 * counts_bytes);
-    unsigned long long *d_sums = static_cast<unsigned long long *>(d_ids_.ptr);
-    int *d_overflow = reinterpret_cast<int *>(d_sums + n * 4);
-    uint8_t *d_free = atoms ? reinterpret_cast<uint8_t *>(d_sums + n * 4) + 16 : nullptr;
-    uint8_t *d_bound = atoms ? d_free + counts_bytes : nullptr;
-    hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), stream_), "hipMemset");
-    d_ws_.reserve(slots * per_slot);
+    unsigned long long *d_sums;
+    int *d_overflow;
+    uint8_t *d_free, *d_bound;  // null without `atoms`
+    carve_into(d_ids_, [&](Carver &c) {
+        d_sums = c.take<unsigned long long>(n * 4), d_overflow = c.take<int>(1);
+        d_free = c.take<uint8_t>(counts), d_bound = c.take<uint8_t>(counts);  // neighbours on purpose: one memset clears both
+    });
+    d_ws_.reserve(slots * per_slot);  // launch_complex_sasa lays out its slots itself
     const double *d_poses = static_cast<const double *>(d_poses_.ptr);
-    hip_check(hipEventRecord(ev0_, stream_), "hipEventRecord");
+    begin_timed(d_overflow);
     for (size_t i0 = 0; i0 < n; i0 += chunk) {
         const size_t m = std::min(chunk, n - i0);
-        if (atoms) hip_check(hipMemsetAsync(d_free, 0, 2 * counts_bytes, stream_), "hipMemset");  // atoms that take no part stay 0
+        if (atoms) hip_check(hipMemsetAsync(d_free, 0, (size_t)(d_bound - d_free) + counts, stream_), "hipMemset");  // atoms that take no part stay 0
         hip_check(launch_complex_sasa(dev_, d, d_poses + i0 * stride, stride, m, std::min(slots, m), d_ws_.ptr, d_sums + i0 * 4, d_free,
                                       d_bound, d_overflow, stream_),
                   "complex_sasa launch");
@@ -605,18 +614,19 @@ void Complex::assess(size_t n, const double *poses, size_t stride, uint32_t *kep
     // a chunk of poses a launch pair: its sums, and a workspace slot of used atoms a workgroup in flight
     const size_t chunk = std::min(n, kAssessChunkPoses);
     const size_t sums_bytes = chunk * kAssessWords * sizeof(long long), per_slot = (size_t)d.n_used * sizeof(int4);
-    const size_t slots = std::min(chunk, std::min<size_t>(kAssessSlots, std::max<size_t>(1, (kClusterWorkspaceBytes - sums_bytes) / per_slot)));
+    const size_t slots = chunk_of(per_slot, chunk, kAssessSlots, kClusterWorkspaceBytes - sums_bytes);
     upload_poses(n, poses, stride);
-    d_ids_.reserve(n * (2 * sizeof(double) + sizeof(uint32_t)) + sizeof(int));
-    double *d_lrmsd = static_cast<double *>(d_ids_.ptr), *d_irmsd = d_lrmsd + n;
-    uint32_t *d_kept = reinterpret_cast<uint32_t *>(d_irmsd + n);
-    int *d_overflow = reinterpret_cast<int *>(d_kept + n);
-    hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), stream_), "hipMemset");
-    d_ws_.reserve(slots * per_slot + sums_bytes);
-    int4 *d_atoms = static_cast<int4 *>(d_ws_.ptr);
-    long long *d_sums = reinterpret_cast<long long *>(d_atoms + slots * d.n_used);
+    double *d_lrmsd, *d_irmsd;
+    uint32_t *d_kept;
+    int *d_overflow;
+    int4 *d_atoms;
+    long long *d_sums;
+    carve_into(d_ids_, [&](Carver &c) {
+        d_lrmsd = c.take<double>(n), d_irmsd = c.take<double>(n), d_kept = c.take<uint32_t>(n), d_overflow = c.take<int>(1);
+    });
+    carve_into(d_ws_, [&](Carver &c) { d_atoms = c.take<int4>(slots * d.n_used), d_sums = c.take<long long>(chunk * kAssessWords); });
     const double *d_poses = static_cast<const double *>(d_poses_.ptr);
-    hip_check(hipEventRecord(ev0_, stream_), "hipEventRecord");
+    begin_timed(d_overflow);
     for (size_t i0 = 0; i0 < n; i0 += chunk) {
         const size_t m = std::min(chunk, n - i0);
         hip_check(launch_complex_assess_sums(dev_, d, d_poses + i0 * stride, stride, m, ref_.C2, std::min(slots, m), d_atoms, d_sums,

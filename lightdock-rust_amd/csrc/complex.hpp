@@ -1,8 +1,11 @@
 // complex.hpp -- the object behind an `ld_complex*`: a receptor and a ligand as their PDB files give them, device-resident,
 // and the workspace of the analysis kernels (kernels/cluster.hpp).  What lightdock_hip.h says of ld_complex_*
-// holds for the methods of the same names; refusals are ld::Error.
+// holds for the methods of the same names; refusals are ld::Error.  Every block that holds more than one array is laid out
+// once, through device_memory.hpp's Carver (carve_into); a chunk or a slot count is chunk_of(); a timed launch sequence
+// stands between begin_timed() and finish_timed().
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -27,6 +30,12 @@ long long cutoff_thousandths(double cutoff, const char *message);
 std::string record_element(const char *line, size_t len);
 // The residue name of a record, columns 18-20, blanks trimmed.
 std::string record_residue_name(const char *line);
+// How many of n items of `per_item` bytes go at a time: what `budget` holds, one at least, n and `cap` at most.
+inline size_t chunk_of(size_t per_item, size_t n, size_t cap = SIZE_MAX, size_t budget = kClusterWorkspaceBytes) {
+    return std::min(std::min(n, cap), std::max<size_t>(1, budget / per_item));
+}
+// Refuses a scoring that is not finite.
+void check_scoring(size_t n, const double *scoring);
 
 class Complex {
    public:
@@ -82,6 +91,9 @@ class Complex {
     void check_poses(size_t n, const double *poses, size_t stride) const;
     void upload_poses(size_t n, const double *poses, size_t stride);  // n rows of `stride` doubles, copied as they are
     void pose_all(size_t n, const double *poses, size_t stride, double *out);  // all atoms of n poses, unrounded
+    // A timed launch sequence: after the uploads begin_timed clears the overflow word and records ev0_; finish_timed
+    // records ev1_, reads the word, synchronises, refuses with `overflow_message` if it is set and keeps the time.
+    void begin_timed(int *d_overflow);
     void finish_timed(const int *d_overflow, const char *what, const char *overflow_message);
     void check_pair_keys() const;
     void init_saxs();  // the atoms that take part in the scattering, from the constructor
@@ -116,6 +128,7 @@ class Complex {
         AssessSolve solve;
     } ref_;
     DeviceBuffer d_ref_atoms_, d_ref_xyz_, d_ref_native_;  // behind ref_.dev: a later reference reuses them
+    // grow-only and shared by the methods; a call carves what it needs of d_out_, d_ws_ and d_ids_ anew (carve_into)
     DeviceBuffer d_poses_, d_scores_, d_out_, d_ws_, d_ids_;
     DeviceBuffer d_pair_keys_;  // the keys of pair_sets
     FccCluster fcc_;            // cluster_fcc's workspace

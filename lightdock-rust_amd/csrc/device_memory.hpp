@@ -52,4 +52,41 @@ struct DeviceBuffer {
     void release();
 };
 
+// Lays typed arrays one after another in a block, every array on a 16-byte boundary.  The layout of a block is written
+// once, as a function of a Carver&: constructed without a base the carver only measures (every address it returns is
+// null), constructed on the block it places; carve_into() below does both around the reservation, so a block's size and
+// its pointers cannot disagree.  bytes() is the end of the last array, not rounded.  An array of no elements takes no room
+// and has no address (null).  A byte count beyond size_t is refused, never wrapped.
+// The two carved blocks outside this rule: refine.cpp's (its layout is RefinePlan's, public through ld_refine_plan) and
+// decompose.cpp's (decompose_pose_bytes, in a kernel header).
+class Carver {
+   public:
+    Carver() = default;
+    explicit Carver(void *base) : base_(static_cast<char *>(base)) {}
+    template <typename T>
+    T *take(size_t count) {
+        static_assert(alignof(T) <= 16, "an array starts on a 16-byte boundary, no wider one");
+        if (count == 0) return nullptr;
+        const size_t start = (end_ + 15) / 16 * 16;  // end_ <= SIZE_MAX - 15, below
+        if (count > (SIZE_MAX - 15 - start) / sizeof(T)) throw Error(LD_ERR_INVALID, "the bytes of a workspace overflow");
+        end_ = start + count * sizeof(T);
+        return base_ ? reinterpret_cast<T *>(base_ + start) : nullptr;
+    }
+    size_t bytes() const { return end_; }
+
+   private:
+    char *base_ = nullptr;
+    size_t end_ = 0;
+};
+
+// Reserves what `layout` (a function of a Carver&) measures, then runs it again on the buffer.
+template <typename Layout>
+void carve_into(DeviceBuffer &buffer, Layout &&layout) {
+    Carver measure;
+    layout(measure);
+    buffer.reserve(measure.bytes());
+    Carver place(buffer.ptr);
+    layout(place);
+}
+
 }  // namespace ld

@@ -1,6 +1,7 @@
 // emfit.cpp -- the host side of the density fit (lightdock_hip.h, "Density fit"): the quantised map, the
 // kernel table made with libm, the scores, and for a complex (Complex::density_fit, Complex::simulate_density) the
-// argument checks, the chunking and the launch sequence of kernels/emfit.hpp.
+// argument checks, the chunking (chunk_of), the workspace (every block laid out through device_memory.hpp's Carver) and
+// the launch sequence of kernels/emfit.hpp.
 #include "emfit.hpp"
 
 #include <algorithm>
@@ -10,19 +11,6 @@
 #include "complex.hpp"
 
 namespace ld {
-
-namespace {
-
-template <typename T>
-T *carve(char *&at, size_t count) {
-    T *p = reinterpret_cast<T *>(at);
-    at += (count * sizeof(T) + 15) / 16 * 16;
-    return p;
-}
-
-size_t carved(size_t count, size_t size) { return (count * size + 15) / 16 * 16; }
-
-}  // namespace
 
 uint32_t isqrt64(unsigned long long v) {
     unsigned long long r = (unsigned long long)std::sqrt((double)v);
@@ -138,30 +126,30 @@ void Complex::density_run(Density &map, size_t n, const double *poses, size_t st
     b.map = map.device();
     const size_t n_bricks = b.map.n_bricks();
     const size_t per_pose = atom_bytes + n_bricks * sizeof(uint2) + sizeof(ld_density_sums) + sizeof(EmfitBox) + (grid ? N * sizeof(uint32_t) : 0);
-    size_t chunk = density_chunk_ ? density_chunk_ : std::max<size_t>(1, kClusterWorkspaceBytes / per_pose);
-    chunk = std::min(std::min(chunk, n), (size_t)65535);
+    const size_t chunk = density_chunk_ ? std::min(density_chunk_, std::min<size_t>(n, 65535)) : chunk_of(per_pose, n, 65535);
     std::vector<ld_density_sums> h_rows(n);
     std::vector<uint32_t> h_grid(grid ? n * N : 0);
     std::vector<uint8_t> table(kernel.table.begin(), kernel.table.end());
 
     upload_poses(n, poses, stride);
-    d_ws_.reserve(chunk * atom_bytes + (rigid ? carved((size_t)d.n_part_rec, sizeof(int4)) : 0));
-    d_out_.reserve(carved(chunk + 1, sizeof(ld_density_sums)) + carved(chunk + 1, sizeof(EmfitBox)) + carved((chunk + 1) * n_bricks, sizeof(uint2)) + 64 +
-                   carved(table.size(), 1) + (rigid ? carved(n_bricks * 4, sizeof(unsigned long long)) : 0));
-    d_density_.reserve((rigid ? carved(N, sizeof(uint32_t)) : 0) + (grid ? chunk * N * sizeof(uint32_t) : 0) + 16);
-    int4 *d_atoms = static_cast<int4 *>(d_ws_.ptr), *d_rec_atoms = d_atoms + chunk * (size_t)std::max(count, 1);
-    char *at = static_cast<char *>(d_out_.ptr);
-    ld_density_sums *d_rows = carve<ld_density_sums>(at, chunk + 1), *d_base_row = d_rows + chunk;
-    EmfitBox *d_boxes = carve<EmfitBox>(at, chunk + 1), *d_base_box = d_boxes + chunk;
-    uint2 *d_items = carve<uint2>(at, (chunk + 1) * n_bricks);
-    int *d_overflow = carve<int>(at, 1);
-    uint32_t *d_n_items = carve<uint32_t>(at, 1);
-    uint8_t *d_table = carve<uint8_t>(at, table.size());
-    unsigned long long *d_base_sums = rigid ? carve<unsigned long long>(at, n_bricks * 4) : nullptr;
-    char *at_grid = static_cast<char *>(d_density_.ptr);
-    uint32_t *d_base = rigid ? carve<uint32_t>(at_grid, N) : nullptr;
-    uint32_t *d_grid = grid ? reinterpret_cast<uint32_t *>(at_grid) : nullptr;
-    hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), stream_), "hipMemset");
+    int4 *d_atoms, *d_rec_atoms;
+    ld_density_sums *d_rows;
+    EmfitBox *d_boxes;
+    uint2 *d_items;
+    int *d_overflow;
+    uint32_t *d_n_items, *d_base, *d_grid;
+    uint8_t *d_table;
+    unsigned long long *d_base_sums;
+    // what only a rigid receptor or only `grid` needs has no elements, and so is null, without it
+    carve_into(d_ws_, [&](Carver &c) { d_atoms = c.take<int4>(chunk * (size_t)std::max(count, 1)), d_rec_atoms = c.take<int4>(rigid ? (size_t)d.n_part_rec : 0); });
+    carve_into(d_out_, [&](Carver &c) {
+        d_rows = c.take<ld_density_sums>(chunk + 1), d_boxes = c.take<EmfitBox>(chunk + 1);  // row and box `chunk` are the base's
+        d_items = c.take<uint2>((chunk + 1) * n_bricks), d_overflow = c.take<int>(1), d_n_items = c.take<uint32_t>(1);
+        d_table = c.take<uint8_t>(table.size()), d_base_sums = c.take<unsigned long long>(rigid ? n_bricks * 4 : 0);
+    });
+    carve_into(d_density_, [&](Carver &c) { d_base = c.take<uint32_t>(rigid ? N : 0), d_grid = c.take<uint32_t>(grid ? chunk * N : 0); });
+    ld_density_sums *d_base_row = d_rows + chunk;
+    EmfitBox *d_base_box = d_boxes + chunk;
     hip_check(hipMemcpyAsync(d_table, table.data(), table.size(), hipMemcpyHostToDevice, stream_), "hipMemcpy H2D table");
     const double *d_poses = static_cast<const double *>(d_poses_.ptr);
     b.table.shift = kernel.shift;
@@ -173,7 +161,7 @@ void Complex::density_run(Density &map, size_t n, const double *poses, size_t st
     b.n_items = d_n_items;
     b.overflow = d_overflow;
     auto groups = [&](size_t m) { return std::min<size_t>(m * n_bricks, (size_t)kEmfitMaxGroups); };
-    hip_check(hipEventRecord(ev0_, stream_), "hipEventRecord");
+    begin_timed(d_overflow);
     if (rigid) {
         // the receptor once: its voxels into the base grid, its sums brick by brick into the table, their totals into the base row
         hip_check(hipMemsetAsync(d_base, 0, N * sizeof(uint32_t), stream_), "hipMemset");

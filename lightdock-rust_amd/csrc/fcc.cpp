@@ -1,5 +1,6 @@
-// fcc.cpp -- the host side of clustering by common contacts: argument checks, workspace sizing and the launch sequences of
-// kernels/fcc.hpp, for a complex (Complex::pair_contacts, Complex::cluster_fcc) and for sets the caller gives.
+// fcc.cpp -- the host side of clustering by common contacts: argument checks, the workspace (blocks of several arrays laid
+// out through device_memory.hpp's Carver) and the launch sequences of kernels/fcc.hpp, for a complex
+// (Complex::pair_contacts, Complex::cluster_fcc) and for sets the caller gives.
 #include "fcc.hpp"
 
 #include <algorithm>
@@ -13,15 +14,6 @@ namespace ld {
 namespace {
 
 thread_local double g_last_kernel_ms = 0.0;
-
-template <typename T>
-T *carve(char *&at, size_t count) {
-    T *p = reinterpret_cast<T *>(at);
-    at += (count * sizeof(T) + 15) / 16 * 16;
-    return p;
-}
-
-size_t carved(size_t count, size_t size) { return (count * size + 15) / 16 * 16; }
 
 // Offsets from 0 that ascend, keys strictly ascending inside a set -> the smallest key and the span of all keys.
 void check_sets(size_t n, const uint32_t *offsets, const uint32_t *keys, uint32_t *key_lo, uint64_t *key_span) {
@@ -138,11 +130,13 @@ void FccCluster::cluster(const Sets &s, const double *scoring, uint32_t T, uint3
     std::stable_sort(order.begin(), order.end(), [scoring](uint32_t a, uint32_t b) { return scoring[a] > scoring[b]; });
     for (size_t p = 0; p < n; p++) row_of[order[p]] = (uint32_t)p;
 
-    work_.reserve(carved(n, sizeof(uint32_t)) + 2 * carved(n, sizeof(int)) + 2 * carved(n, sizeof(int32_t)));
-    char *at = static_cast<char *>(work_.ptr);
-    uint32_t *d_row_of = carve<uint32_t>(at, n);
-    int *d_deg = carve<int>(at, n), *d_members = carve<int>(at, n);
-    int32_t *d_cluster = carve<int32_t>(at, n), *d_centres = carve<int32_t>(at, n);
+    uint32_t *d_row_of;
+    int *d_deg, *d_members;
+    int32_t *d_cluster, *d_centres;
+    carve_into(work_, [&](Carver &c) {
+        d_row_of = c.take<uint32_t>(n), d_deg = c.take<int>(n), d_members = c.take<int>(n);
+        d_cluster = c.take<int32_t>(n), d_centres = c.take<int32_t>(n);
+    });
     hip_check(hipMemcpyAsync(d_row_of, row_of.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, stream), "hipMemcpy H2D rows");
     const size_t W = build_rows(s, d_row_of, stream);
 
@@ -215,8 +209,7 @@ void fcc_cluster_host(size_t n, const uint32_t *offsets, const uint32_t *keys, c
         return;
     }
     if (!scoring || !cluster_of || !centres) throw Error(LD_ERR_INVALID, "null argument");
-    for (size_t i = 0; i < n; i++)
-        if (!std::isfinite(scoring[i])) throw Error(LD_ERR_INVALID, "scoring " + std::to_string(i) + " is not finite");
+    check_scoring(n, scoring);
     Uploaded u;
     upload_sets(n, offsets, keys, u);
     FccCluster f;
@@ -233,26 +226,27 @@ void fcc_cluster_host(size_t n, const uint32_t *offsets, const uint32_t *keys, c
 // --- a complex's pair sets ---------------------------------------------------------------------------------------------
 
 // Count pass, scan and, with `fill`, the keys: the sets of n checked poses as CSR on the device (offsets in d_ids_, keys in
-// d_pair_keys_).  ev0_ is recorded in front of the first launch; the caller ends the timing with finish_timed(*d_overflow).
+// d_pair_keys_).  begin_timed stands in front of the first launch; the caller ends the timing with finish_timed(*d_overflow).
 FccCluster::Sets Complex::pair_sets(size_t n, const double *poses, size_t stride, long long C, bool fill, size_t cap, int **d_overflow_out) {
     const ContactsDevice &k = contacts_;
     const size_t lw = ((size_t)k.n_lig_res + 31) / 32, pair_words = (size_t)k.n_rec_res * lw;
     const size_t per_slot = (size_t)k.n_atoms * sizeof(int4) + (k.boxes_in_lds ? 0 : k.box_bytes()) + pair_words * sizeof(uint32_t);
-    const size_t slots = std::min(n, std::min<size_t>(kPairSlots, std::max<size_t>(1, kClusterWorkspaceBytes / per_slot)));
+    const size_t slots = chunk_of(per_slot, n, kPairSlots);
     upload_poses(n, poses, stride);
-    d_ids_.reserve(carved(1, sizeof(FccStatus)) + carved(1, sizeof(int)) + carved(n, sizeof(uint32_t)) + carved(n + 1, sizeof(uint32_t)));
-    char *at = static_cast<char *>(d_ids_.ptr);
-    FccStatus *d_status = carve<FccStatus>(at, 1);
-    int *d_overflow = carve<int>(at, 1);
-    uint32_t *d_counts = carve<uint32_t>(at, n), *d_offsets = carve<uint32_t>(at, n + 1);
-    hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), stream_), "hipMemset");
-    d_ws_.reserve(slots * per_slot);
-    int4 *d_atoms = static_cast<int4 *>(d_ws_.ptr);
-    int *d_boxes = reinterpret_cast<int *>(d_atoms + slots * k.n_atoms);
-    uint32_t *d_pairs = reinterpret_cast<uint32_t *>(d_boxes + (k.boxes_in_lds ? 0 : slots * 6 * (size_t)k.n_boxes()));
+    FccStatus *d_status;
+    int *d_overflow, *d_boxes;
+    uint32_t *d_counts, *d_offsets, *d_pairs;
+    int4 *d_atoms;
+    carve_into(d_ids_, [&](Carver &c) {
+        d_status = c.take<FccStatus>(1), d_overflow = c.take<int>(1), d_counts = c.take<uint32_t>(n), d_offsets = c.take<uint32_t>(n + 1);
+    });
+    carve_into(d_ws_, [&](Carver &c) {
+        d_atoms = c.take<int4>(slots * k.n_atoms), d_boxes = c.take<int>(k.boxes_in_lds ? 0 : slots * 6 * (size_t)k.n_boxes());
+        d_pairs = c.take<uint32_t>(slots * pair_words);
+    });
     const double *d_poses = static_cast<const double *>(d_poses_.ptr);
     const char *beyond = "a posed coordinate is beyond +-1.0e6 A";
-    hip_check(hipEventRecord(ev0_, stream_), "hipEventRecord");
+    begin_timed(d_overflow);
     hip_check(launch_complex_pair_sets(dev_, k, d_poses, stride, n, (uint32_t)(C * C), slots, d_atoms, d_boxes, d_pairs, nullptr, d_counts,
                                        nullptr, d_overflow, stream_),
               "complex_pair_sets launch");
@@ -324,8 +318,7 @@ void Complex::cluster_fcc(size_t n, const double *poses, size_t stride, const do
     }
     if (!scoring || !cluster_of || !centres) throw Error(LD_ERR_INVALID, "null argument");
     check_poses(n, poses, stride);
-    for (size_t i = 0; i < n; i++)
-        if (!std::isfinite(scoring[i])) throw Error(LD_ERR_INVALID, "scoring " + std::to_string(i) + " is not finite");
+    check_scoring(n, scoring);
     int *d_overflow = nullptr;
     const FccCluster::Sets s = pair_sets(n, poses, stride, C, true, SIZE_MAX, &d_overflow);
     FccCluster::Result r;

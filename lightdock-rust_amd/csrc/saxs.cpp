@@ -1,6 +1,7 @@
 // saxs.cpp -- the host side of the SAXS profiles (lightdock_hip.h, "Small-angle scattering"): the classes
-// of a complex's atoms, the tables made with libm, argument checks, chunking and the launch sequences of kernels/saxs.hpp,
-// for a complex (Complex::distance_histogram, Complex::saxs) and for counts the caller gives (saxs_debye_host), and the fit.
+// of a complex's atoms, the tables made with libm, argument checks, chunking (chunk_of), the workspace (every block laid out
+// through device_memory.hpp's Carver) and the launch sequences of kernels/saxs.hpp, for a complex
+// (Complex::distance_histogram, Complex::saxs) and for counts the caller gives (saxs_debye_host), and the fit.
 #include "saxs.hpp"
 
 #include <algorithm>
@@ -54,32 +55,21 @@ double sinc_at(double q, size_t k, uint32_t width) {
     return x == 0.0 ? 1.0 : std::sin(x) / x;
 }
 
-template <typename T>
-T *carve(char *&at, size_t count) {
-    T *p = reinterpret_cast<T *>(at);
-    at += (count * sizeof(T) + 15) / 16 * 16;
-    return p;
-}
-
-size_t carved(size_t count, size_t size) { return (count * size + 15) / 16 * 16; }
-
-// The tables behind a Debye launch, in one device buffer.
+// The tables behind a Debye launch, in the block the carver walks.
 struct DeviceTables {
-    const double *sinc_t = nullptr, *self = nullptr, *cross = nullptr;
+    double *sinc_t = nullptr, *self = nullptr, *cross = nullptr;
 };
 
-size_t table_bytes(size_t n_q, size_t bins) {
-    return carved(bins * n_q, sizeof(double)) + carved(n_q, sizeof(double)) + carved(n_q * kSaxsPairClasses, sizeof(double));
+DeviceTables take_tables(const SaxsTables &t, Carver &c) {
+    DeviceTables d;
+    d.sinc_t = c.take<double>(t.sinc_t.size()), d.self = c.take<double>(t.self.size()), d.cross = c.take<double>(t.cross.size());
+    return d;
 }
 
-DeviceTables upload_tables(const SaxsTables &t, char *&at, hipStream_t stream) {
-    DeviceTables d;
-    double *sinc_t = carve<double>(at, t.sinc_t.size()), *self = carve<double>(at, t.self.size()), *cross = carve<double>(at, t.cross.size());
-    hip_check(hipMemcpyAsync(sinc_t, t.sinc_t.data(), t.sinc_t.size() * sizeof(double), hipMemcpyHostToDevice, stream), "hipMemcpy H2D sinc");
-    hip_check(hipMemcpyAsync(self, t.self.data(), t.self.size() * sizeof(double), hipMemcpyHostToDevice, stream), "hipMemcpy H2D");
-    hip_check(hipMemcpyAsync(cross, t.cross.data(), t.cross.size() * sizeof(double), hipMemcpyHostToDevice, stream), "hipMemcpy H2D");
-    d.sinc_t = sinc_t, d.self = self, d.cross = cross;
-    return d;
+void upload_tables(const SaxsTables &t, const DeviceTables &d, hipStream_t stream) {
+    hip_check(hipMemcpyAsync(d.sinc_t, t.sinc_t.data(), t.sinc_t.size() * sizeof(double), hipMemcpyHostToDevice, stream), "hipMemcpy H2D sinc");
+    hip_check(hipMemcpyAsync(d.self, t.self.data(), t.self.size() * sizeof(double), hipMemcpyHostToDevice, stream), "hipMemcpy H2D");
+    hip_check(hipMemcpyAsync(d.cross, t.cross.data(), t.cross.size() * sizeof(double), hipMemcpyHostToDevice, stream), "hipMemcpy H2D");
 }
 
 }  // namespace
@@ -137,13 +127,13 @@ void saxs_debye_host(size_t n, const uint32_t *counts, uint32_t width, size_t bi
     if (!counts || !intensity) throw Error(LD_ERR_INVALID, "null argument");
     const SaxsTables t = saxs_tables(q, n_q, width, bins, class_atoms);
     const size_t row_words = (size_t)kSaxsPairClasses * bins, row_bytes = row_words * sizeof(uint32_t);
-    const size_t chunk = std::min(n, std::max<size_t>(1, kClusterWorkspaceBytes / row_bytes));
+    const size_t chunk = chunk_of(row_bytes, n);
     DeviceBuffer d_counts, d_rest;
     d_counts.reserve(chunk * row_bytes);
-    d_rest.reserve(table_bytes(n_q, bins) + carved(n * n_q, sizeof(double)));
-    char *at = static_cast<char *>(d_rest.ptr);
-    const DeviceTables tables = upload_tables(t, at, nullptr);
-    double *d_intensity = carve<double>(at, n * n_q);
+    DeviceTables tables;
+    double *d_intensity;
+    carve_into(d_rest, [&](Carver &c) { tables = take_tables(t, c), d_intensity = c.take<double>(n * n_q); });
+    upload_tables(t, tables, nullptr);
     SaxsDebye d;
     d.bins = (int)bins;
     d.n_q = (int)n_q;
@@ -247,26 +237,23 @@ void Complex::saxs_run(size_t n, const double *poses, size_t stride, uint32_t wi
     // without receptor modes the receptor's own pairs are the same for every pose: one base row a call
     const bool base = dev_.anm_rec == 0 && d.n_part_rec >= 2;
     const int first_b = base ? d.n_part_rec : 0;
-    size_t chunk = saxs_chunk_ ? saxs_chunk_ : std::max<size_t>(1, kClusterWorkspaceBytes / (row_bytes + atom_bytes));
-    chunk = std::min(std::min(chunk, n), (size_t)65535);
+    const size_t chunk = saxs_chunk_ ? std::min(saxs_chunk_, std::min<size_t>(n, 65535)) : chunk_of(row_bytes + atom_bytes, n, 65535);
     SaxsTables tables;
     if (debye) tables = saxs_tables(q, n_q, width, bins, saxs_class_atoms_);
     std::vector<uint32_t> h_counts(counts ? n * row_words : 0);
 
     upload_poses(n, poses, stride);
-    d_ws_.reserve(chunk * atom_bytes + (base ? carved((size_t)d.n_part_rec, sizeof(int4)) : 0));
-    d_out_.reserve((chunk + 1) * row_bytes);
-    d_ids_.reserve(16 + (debye ? table_bytes(n_q, bins) + carved(n * n_q, sizeof(double)) : 0));
-    int4 *d_atoms = static_cast<int4 *>(d_ws_.ptr), *d_rec_atoms = d_atoms + chunk * (size_t)d.n_part;
+    int4 *d_atoms, *d_rec_atoms;  // the receptor's own atoms: null without `base`
+    int *d_overflow;
+    DeviceTables t;
+    double *d_intensity;  // without q: n_q is 0 and the tables are empty, so these are null
+    carve_into(d_ws_, [&](Carver &c) { d_atoms = c.take<int4>(chunk * (size_t)d.n_part), d_rec_atoms = c.take<int4>(base ? (size_t)d.n_part_rec : 0); });
+    d_out_.reserve((chunk + 1) * row_bytes);  // one array: the rows of a chunk, then the base row
     uint32_t *d_counts = static_cast<uint32_t *>(d_out_.ptr), *d_base = d_counts + chunk * row_words;
-    char *at = static_cast<char *>(d_ids_.ptr);
-    int *d_overflow = carve<int>(at, 1);
-    hip_check(hipMemsetAsync(d_overflow, 0, sizeof(int), stream_), "hipMemset");
+    carve_into(d_ids_, [&](Carver &c) { d_overflow = c.take<int>(1), t = take_tables(tables, c), d_intensity = c.take<double>(n * n_q); });
     SaxsDebye sum;
-    double *d_intensity = nullptr;
     if (debye) {
-        const DeviceTables t = upload_tables(tables, at, stream_);
-        d_intensity = carve<double>(at, n * n_q);
+        upload_tables(tables, t, stream_);
         sum.bins = (int)bins;
         sum.n_q = (int)n_q;
         sum.counts = d_counts;
@@ -277,7 +264,7 @@ void Complex::saxs_run(size_t n, const double *poses, size_t stride, uint32_t wi
     h.width = width;
     h.bins = (int)bins;
     h.overflow = d_overflow;
-    hip_check(hipEventRecord(ev0_, stream_), "hipEventRecord");
+    begin_timed(d_overflow);
     if (base) {
         hip_check(launch_saxs_pose(dev_, d, d_poses, stride, 1, 0, d.n_part_rec, d_rec_atoms, (size_t)d.n_part_rec, d_overflow, stream_), "saxs_pose launch");
         hip_check(launch_saxs_rows(nullptr, d_base, 1, row_words, stream_), "saxs_rows launch");

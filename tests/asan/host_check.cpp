@@ -14,6 +14,7 @@
 
 #define CHECK_PROGRAM "host_check"
 #include "check.hpp"
+#include "device_memory.hpp"     // the carver is checked directly
 #include "kernels/cluster.hpp"   // the analysis section sizes its inputs from the constants; every call goes through the C ABI
 
 extern "C" size_t ld_stub_device_allocations(void);   // tests/asan/hip_stub.cpp
@@ -46,6 +47,60 @@ static int cli(std::vector<std::string> args) {
     for (auto &a : args) argv.push_back(&a[0]);
     argv.push_back(nullptr);
     return ld_cli_main((int)args.size(), argv.data());
+}
+
+// ---- the carver every block of the analysis half is laid out with (device_memory.hpp) -------------------------------------------
+struct CarvedBlock {
+    int *a = nullptr;
+    double *none = nullptr, *b = nullptr;
+    uint8_t *odd = nullptr;
+    uint64_t *last = nullptr;
+};
+
+static void carved_layout(ld::Carver &c, CarvedBlock &p) {
+    p.a = c.take<int>(4);   // ends on a boundary: what follows starts at its past-the-end element
+    p.none = c.take<double>(0);
+    p.b = c.take<double>(3);
+    p.odd = c.take<uint8_t>(5);
+    p.last = c.take<uint64_t>(2);
+}
+
+static void carver() {
+    CarvedBlock measured, placed;
+    ld::Carver measure;
+    carved_layout(measure, measured);
+    // measuring hands out no address; 16 + 24 -> 40, 5 bytes at 48 -> 53, 16 bytes at 64: the extent is the last array's end
+    CHECK(!measured.a && !measured.none && !measured.b && !measured.odd && !measured.last && measure.bytes() == 80);
+    ld::DeviceBuffer buffer;
+    ld::carve_into(buffer, [&](ld::Carver &c) { carved_layout(c, placed); });
+    CHECK(buffer.bytes >= 80 && (void *)placed.a == buffer.ptr);
+    ld::Carver place(buffer.ptr);
+    carved_layout(place, placed);
+    CHECK(place.bytes() == measure.bytes());
+    for (const void *p : {(const void *)placed.a, (const void *)placed.b, (const void *)placed.odd, (const void *)placed.last})
+        CHECK(p != nullptr && (uintptr_t)p % 16 == 0);
+    // an array of no elements: no room, no address -- not the past-the-end element of `a`, which is where `b` starts
+    CHECK(placed.none == nullptr && (void *)placed.b == (void *)(placed.a + 4));
+    // both ends of every array lie inside what was reserved (the growth headroom behind it is poisoned in this build)
+    placed.a[0] = placed.a[3] = 1;
+    placed.b[0] = placed.b[2] = 1.0;
+    placed.odd[0] = placed.odd[4] = 1;
+    placed.last[0] = placed.last[1] = 1;
+    ld::Carver empty;
+    CHECK(empty.take<int>(0) == nullptr && empty.bytes() == 0);
+    // a byte count beyond size_t is refused, in the product and in the sum, and leaves the extent as it was
+    for (int what = 0; what < 2; what++) {
+        ld::Carver c;
+        c.take<int>(1);
+        bool refused = false;
+        try {
+            if (what == 0) c.take<uint64_t>(SIZE_MAX / 4);
+            if (what == 1) c.take<uint8_t>(SIZE_MAX - 16);
+        } catch (const ld::Error &e) {
+            refused = e.code() == LD_ERR_INVALID;
+        }
+        CHECK(refused && c.bytes() == 4);
+    }
 }
 
 // ---- the analysis half (complex.cpp, host/pdb_file.cpp; ld_complex_*) ---------------------------------------------------------
@@ -470,6 +525,7 @@ int main(int argc, char **argv) {
     CHECK(ld_scorer_create_from_pdb(7, rec1.c_str(), lig1.c_str(), nullptr, 0, nullptr, 0, nullptr, 0, 0, nullptr, 0, nullptr, 0,
                                     nullptr, 0, 0, 0, table.data()) == nullptr);
 
+    carver();
     analysis(rec1, lig1, scratch);
 
     // ---- the CLI (src/bin/lightdock-rust.rs:77-333): usage errors return 0, panics 101 ---------------

@@ -9,7 +9,8 @@ available -- GPU AddressSanitizer is not, on this pool).
     the file-order PDB reader on "\r\n" files and records of exactly 54 columns, coordinates / write_pdb /
     contacts (residue boxes in and out of LDS, more poses than workspace slots) / cluster (more swarms
     than one workspace chunk holds) with launch stubs that touch both ends of every buffer a kernel
-    reads or writes, and every refusal of ld_complex_* by status;
+    reads or writes, and every refusal of ld_complex_* by status; and the carver those blocks are laid out
+    with (csrc/device_memory.hpp), directly: measuring against placing, alignment, an empty array, overflow;
   * the oracle CLI, same flags, a few GSO steps of the 1azp example.
 """
 import os
