@@ -203,6 +203,9 @@ extern "C" {
     pub fn ld_complex_sasa_radii(c: *const ld_complex, side: c_int, radii_out: *mut u32) -> c_int;
     pub fn ld_complex_sasa(c: *mut ld_complex, n: usize, poses: *const f64, stride: usize, probe: f64, sums: *mut u64,
                            free_counts: *mut u8, bound_counts: *mut u8) -> c_int;
+    pub fn ld_ccs_frames(out: *mut i32) -> c_int;
+    pub fn ld_complex_ccs(c: *mut ld_complex, n: usize, poses: *const f64, stride: usize, what: c_int, probe: f64, cell: f64,
+                          counts: *mut u32, sums: *mut u64) -> c_int;
     pub fn ld_complex_saxs_classes(c: *const ld_complex, side: c_int, class_out: *mut u8) -> c_int;
     pub fn ld_saxs_form_factors(q: *const f64, n_q: usize, f_out: *mut f64) -> c_int;
     pub fn ld_saxs_sinc(q: *const f64, n_q: usize, width: u32, bins: usize, s_out: *mut f64) -> c_int;

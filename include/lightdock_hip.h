@@ -660,6 +660,41 @@ int ld_complex_sasa(ld_complex *c, size_t n, const double *poses, size_t stride,
                     uint64_t *sums /* n x 4 */, uint8_t *free_counts /* n x (n_rec + n_lig), receptor first, file order */,
                     uint8_t *bound_counts /* as free_counts */);
 
+/* Collision cross-section: for every pose, the orientation-averaged projected area of the receptor, of the posed ligand or
+ * of the complex -- the number an ion-mobility measurement of native mass spectrometry gives -- by the projection
+ * approximation (PA).  No tool of the reference tree computes one; the rule is this library's own: discs on a lattice, all
+ * integers, in thousandths of an angstrom as "%8.3f" prints a coordinate.
+ *   Atoms and radii: exactly the surface's (above): the atoms that take part and their radii R_a are those of
+ *     ld_complex_sasa_radii; H, D and MMB residues take no part.  Probe: 0 <= probe <= 2.0 A, p = llrint(1000 * probe),
+ *     E_a = R_a + p.  The default probe of 1.0 A is a parameter of the method, not a measurement.
+ *   Selection `what`: 0 the receptor alone, 1 the ligand alone (posed), 2 the complex.
+ *   Views: LD_CCS_VIEWS = 64 directions, the upper hemisphere of the surface's spiral (a projection along u and along -u
+ *     has the same area).  For v = 0 .. 63: z = 1 - (2v + 1) / 128, r = sqrt(1 - z^2), g = pi (3 - sqrt 5), c = cos(v g),
+ *     s = sin(v g); the in-plane axes e1 = (-s, c, 0), e2 = (-z c, -z s, r); the integer frames A[v] = rint(2^20 * e1),
+ *     B[v] = rint(2^20 * e2), a fixed table (ld_ccs_frames).  No component is within 1e-3 of a rounding tie.
+ *   Projection of a posed atom c_a (posing as above; the integer thousandths ld_complex_write_pdb prints):
+ *     a = (A[v] . c_a + 2^19) >> 20 and b = (B[v] . c_a + 2^19) >> 20, the dot products in 64 bits, the shifts arithmetic.
+ *   Lattice: h = llrint(1000 * cell), 100 <= h <= 2000, default 500.  The lattice points of every view are (i h, j h) for
+ *     all integers i, j: anchored at the frame's origin, so the lattice does not depend on the batch.  Point (i, j) is
+ *     covered by atom a iff (i h - a)^2 + (j h - b)^2 <= E_a^2, inclusively, in exact integers.  N[pose][v] is the number
+ *     of lattice points covered by at least one selected atom.
+ *   Outputs: counts, n x 64 uint32, N itself; sums[pose] = sum over v of N[pose][v], uint64.  The area of a view in A^2 is
+ *     N h^2 / 1e6 and CCS_PA = sums h^2 / (64e6).
+ *   Bounds: a posed coordinate of a selected atom beyond +-1.0e6 A refuses the call, as the surface does.  In any view,
+ *     with I and J the counts of lattice columns and rows that the box [min(a - E), max(a + E)] x [min(b - E), max(b + E)]
+ *     of the selected atoms touches, I * J > 2^28 refuses the call; a count then fits 32 bits.
+ *   Every result is the same bits whatever the batch, a pose's place in it, the slot count, or how the plane is cut into
+ *     pieces; without receptor modes the receptor's discs are rasterised once a call, to the same bits.
+ * LD_ERR_INVALID, nothing written: a probe or a cell out of range or not finite; `what` not in 0 .. 2; non-finite poses, a
+ * zero quaternion, stride < pose_len; no selected atom takes part; the two bounds.  Device workspace: one slot of 32 B a
+ * selected atom per workgroup in flight, at most 1024 slots and 256 MiB (or one slot); up to 64 MiB for a rigid receptor's
+ * bitmaps; the counts leave in chunks of poses within 256 MiB. */
+#define LD_CCS_VIEWS (64)
+int ld_ccs_frames(int32_t *out /* LD_CCS_VIEWS x 2 x 3: A then B */); /* host only */
+/* Any output may be NULL; n == 0 is LD_OK.  ld_complex_last_kernel_ms then reports this call's device work. */
+int ld_complex_ccs(ld_complex *c, size_t n, const double *poses, size_t stride, int what, double probe /* 1.0 */,
+                   double cell /* 0.5 */, uint32_t *counts /* n x LD_CCS_VIEWS */, uint64_t *sums /* n */);
+
 /* Small-angle scattering: for every pose, the histogram of all pair distances by pair class and, from it, the SAXS
  * profile I(q) by the Debye formula, to be fitted to an experimental curve.  No tool of the reference tree computes a
  * profile; the rule is this library's own.  The profile is "vacuum minus excluded volume" of the atoms in the files: no

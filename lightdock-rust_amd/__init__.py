@@ -205,6 +205,8 @@ def load_library():
     lib.ld_sasa_directions.argtypes = [vp]
     lib.ld_complex_sasa_radii.argtypes = [vp, C.c_int, vp]
     lib.ld_complex_sasa.argtypes = [vp, sz, vp, sz, C.c_double, vp, vp, vp]
+    lib.ld_ccs_frames.argtypes = [vp]
+    lib.ld_complex_ccs.argtypes = [vp, sz, vp, sz, C.c_int, C.c_double, C.c_double, vp, vp]
     lib.ld_complex_saxs_classes.argtypes = [vp, C.c_int, vp]
     lib.ld_saxs_form_factors.argtypes = [vp, sz, vp]
     lib.ld_saxs_sinc.argtypes = [vp, sz, C.c_uint32, sz, vp]
@@ -962,6 +964,24 @@ class Complex:
                                         _ptr(out.get("free")), _ptr(out.get("bound"))))
         return out
 
+    def ccs(self, poses, what=2, probe=1.0, cell=0.5, views=False):
+        """(n, >= pose_len) poses -> {"ccs": (n,) float64 A^2, "sums": (n,) uint64}: the collision cross-section by the
+        projection approximation of the receptor alone (what=0), the posed ligand alone (1) or the complex (2), and the
+        covered lattice points summed over the 64 views it is made of, ccs = sums x h^2 / (64 x 10^6) (ld_complex_ccs;
+        lightdock_hip.h, "Collision cross-section").  views=True adds "counts", (n, 64) uint32: the points of every view;
+        ccs_area() turns them into A^2."""
+        poses = _f64(poses)
+        if poses.ndim != 2:
+            raise ValueError("poses must be (n, pose_len)")
+        n = poses.shape[0]
+        out = {"sums": np.zeros(n, dtype=np.uint64)}
+        if views:
+            out["counts"] = np.zeros((n, CCS_VIEWS), dtype=np.uint32)
+        _check(self.lib.ld_complex_ccs(self._h, n, _ptr(poses), poses.shape[1], int(what), C.c_double(probe), C.c_double(cell),
+                                       _ptr(out.get("counts")), _ptr(out["sums"])))
+        out["ccs"] = ccs_area(out["sums"], cell) / CCS_VIEWS
+        return out
+
     def saxs_classes(self, side):
         """The scattering class of every atom of a side (0 receptor, 1 ligand): H / D 0, C 1, N 2, O 3, P 4, S 5, and 255
         for an atom that takes no part: another element, a membrane bead (ld_complex_saxs_classes)."""
@@ -1130,6 +1150,22 @@ def sasa_area(weighted):
     """Weighted point counts (count x E^2 in thousandths^2: sasa()'s sums, their differences, an atom's count times its
     squared expanded radius) -> A^2: x 4 pi / (128 x 10^6)."""
     return np.asarray(weighted, dtype=np.float64) * (4.0 * np.pi / (SASA_POINTS * 1e6))
+
+
+CCS_VIEWS = 64
+
+
+def ccs_frames():
+    """The (64, 2, 3) int32 table of the cross-section rule: rint(2^20 x in-plane axis), A then B of every view (ld_ccs_frames)."""
+    out = np.zeros((CCS_VIEWS, 2, 3), dtype=np.int32)
+    _check(load_library().ld_ccs_frames(_ptr(out)))
+    return out
+
+
+def ccs_area(points, cell=0.5):
+    """Covered lattice points of a view (ccs()'s counts) -> the view's area in A^2: x h^2 / 10^6, h = rint(1000 cell)."""
+    h = int(np.rint(1000.0 * cell))
+    return np.asarray(points, dtype=np.float64) * float(h * h) / 1e6
 
 
 def saxs_form_factors(q):

@@ -25,6 +25,7 @@
 #include "host/prepare_pdb.hpp"
 #include "host/refine_plan.hpp"
 #include "host/spatial_order.hpp"
+#include "kernels/ccs.hpp"
 #include "lightdock_hip.h"
 #include "prepare.hpp"
 #include "refine.hpp"
@@ -633,6 +634,19 @@ int ld_complex_sasa(ld_complex *c, size_t n, const double *poses, size_t stride,
     return guarded([&] {
         if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
         c->impl.sasa(n, poses, stride, probe, sums, free_counts, bound_counts);
+    });
+}
+int ld_ccs_frames(int32_t *out) {
+    return guarded([&] {
+        if (!out) throw ld::Error(LD_ERR_INVALID, "null argument");
+        std::memcpy(out, ld::kCcsFrames, sizeof ld::kCcsFrames);
+    });
+}
+int ld_complex_ccs(ld_complex *c, size_t n, const double *poses, size_t stride, int what, double probe, double cell, uint32_t *counts,
+                   uint64_t *sums) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.ccs(n, poses, stride, what, probe, cell, counts, sums);
     });
 }
 int ld_complex_saxs_classes(const ld_complex *c, int side, uint8_t *class_out) {
