@@ -9,22 +9,13 @@
 
 #include "complex.hpp"
 #include "kernels/ccs.hpp"
+#include "kernels/complex_rule.hpp"
 
 namespace ld {
 
 namespace {
 
 const char *const kCcsOverflow = "a posed coordinate is beyond +-1.0e6 A, or a view's box holds more than 2^28 lattice points";
-
-// complex_pose.hpp's thousandths on the host: the integer "%.3f" prints, the same operations in the same order.
-double thousandths_host(double x) {
-    const double p = x * 1000.0, e = std::fma(x, 1000.0, -p), f = std::floor(p);
-    if (p - f == 0.5) {
-        if (e > 0.0) return f + 1.0;
-        if (e < 0.0) return f;
-    }
-    return std::rint(p);
-}
 
 }  // namespace
 
@@ -58,8 +49,8 @@ void Complex::ccs(size_t n, const double *poses, size_t stride, int what, double
             if (sasa_radius_[0][a] == 0) continue;
             int v[3];
             for (int k = 0; k < 3; k++) {
-                const double c = thousandths_host(rec_.xyz[3 * a + k]);
-                if (!(std::fabs(c) <= (double)kCcsCoordBound)) throw Error(LD_ERR_INVALID, kCcsOverflow);
+                const double c = thousandths(rec_.xyz[3 * a + k]);  // an unposed atom: the rounding alone
+                if (!(std::fabs(c) <= (double)kComplexCoordBound)) throw Error(LD_ERR_INVALID, kCcsOverflow);
                 v[k] = (int)c;
             }
             rec_atoms.push_back(make_int4(v[0], v[1], v[2], (int)sasa_radius_[0][a] + d.probe));

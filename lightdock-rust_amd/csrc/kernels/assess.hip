@@ -72,13 +72,8 @@ __global__ void __launch_bounds__(kAssessThreads, 4) complex_assess_sums(Complex
             const int u1 = half == 0 ? d.n_used_rec : d.n_used;
 #pragma unroll 1
             for (int u = (half == 0 ? 0 : d.n_used_rec) + tid; u < u1; u += kAssessThreads) {
-                const P3 p = pose_atom(m, row, d.used_atom[u]);
-                const double c[3] = {thousandths(p.x), thousandths(p.y), thousandths(p.z)};
                 int v[3];
-                for (int k = 0; k < 3; k++) {
-                    if (!(fabs(c[k]) <= (double)kAssessBound)) *overflow = 1;
-                    v[k] = (int)fmax(-(double)kAssessBound, fmin((double)kAssessBound, c[k]));  // clamped: nothing later can wrap
-                }
+                if (!posed_thousandths(m, row, d.used_atom[u], kAssessBound, v)) *overflow = 1;
                 A[u] = make_int4(v[0], v[1], v[2], 0);
                 const int4 ref = d.used_ref[u];
                 add_atom(side, v, ref, ref.w & 1);

@@ -3,7 +3,7 @@
 // Discs on a lattice, on the thousandths "%8.3f" prints, all integers.
 //   complex_ccs: one workgroup a pose at a time (a launch has at most kCcsSlots workgroups, each with a workspace slot it
 //   reuses for pose blockIdx, blockIdx + gridDim, ...):
-//     1. every selected atom is posed once (complex_pose.hpp), rounded and kept as int4 (x, y, z, E) in the slot;
+//     1. every selected atom is posed once (complex_rule.hpp), rounded and kept as int4 (x, y, z, E) in the slot;
 //     2. for each of the 64 views the atoms are projected to (a, b, E, first row) into the slot's second half and the
 //        extremes of a -+ E, b -+ E are folded by wave into LDS: the view's box of lattice columns and rows;
 //     3. the box is cut into pieces of at most kCcsBitmapWords words of LDS, whole rows of 32-column words where a row
@@ -95,15 +95,10 @@ __global__ void __launch_bounds__(kCcsThreads) complex_ccs(ComplexDevice m, CcsD
         __syncthreads();
 #pragma unroll 1
         for (int a = tid; a < d.count; a += kCcsThreads) {
-            const P3 p = pose_atom(m, row, d.part_atom[d.first + a]);
-            const double c[3] = {thousandths(p.x), thousandths(p.y), thousandths(p.z)};
             int v[3];
-            for (int k = 0; k < 3; k++) {
-                if (!(fabs(c[k]) <= (double)kCcsCoordBound)) {
-                    atomicOr(overflow, 1);
-                    s_bad = 1;
-                }
-                v[k] = (int)fmax(-(double)kCcsCoordBound, fmin((double)kCcsCoordBound, c[k]));  // clamped: nothing later can wrap
+            if (!posed_thousandths(m, row, d.part_atom[d.first + a], kComplexCoordBound, v)) {
+                atomicOr(overflow, 1);
+                s_bad = 1;
             }
             P[a] = make_int4(v[0], v[1], v[2], (int)d.part_radius[d.first + a] + d.probe);
         }

@@ -22,7 +22,6 @@ constexpr int kCcsBitmapWords = 12288;       // a workgroup's bitmap: 48 KiB of 
 constexpr int kCcsMinCell = 100, kCcsMaxCell = 2000;  // thousandths
 constexpr int kCcsMaxE = kSasaMaxRadius + kSasaMaxProbe;
 constexpr long long kCcsMaxBox = 1ll << 28;  // lattice points of a view's box: a count fits 32 bits
-constexpr int kCcsCoordBound = 1000000000;   // thousandths: +-1.0e6 A; a projection then fits an int32 (|a| < 1.74e9)
 constexpr size_t kCcsRigidBytes = size_t(64) << 20;  // the rigid receptor's 64 bitmaps at most; beyond it every pose rasterises it
 
 // --- the rule, on integers (thousandths) ------------------------------------------------------------------------------

@@ -7,7 +7,7 @@
 //                              pass one representative at a time;
 //   complex_contacts:          one workgroup a pose: which receptor and which ligand residues touch (ld_complex_contacts;
 //                              what lgd_filter_restraints.py and lgd_filter_membrane.py ask of a model's PDB file).
-// Posing, the thousandths and the RMSD test: kernels/complex_pose.hpp, shared with kernels/assess.hip and kernels/ranked.hip.  Workspace: the thousandths of a
+// Posing and the thousandths: kernels/complex_rule.hpp; the RMSD test: kernels/complex_pose.hpp, shared with kernels/ranked.hip.  Workspace: the thousandths of a
 // chunk of swarms, at most kClusterWorkspaceBytes (or one swarm's n_glowworms x n_backbone x 12 B if more; 1czy: 420 KB a
 // swarm); ld_complex_coordinates poses in chunks of that bound.
 #include "kernels/cluster.hpp"
@@ -48,12 +48,9 @@ __global__ void __launch_bounds__(kPoseThreads) complex_pose_thousandths(Complex
         const size_t sb = t / G;  // s * n_bb + b
         const int b = (int)(sb % n_bb);
         const size_t s = sb / n_bb;
-        const P3 p = pose_atom(m, poses + (s * G + g) * stride, backbone[b]);
-        const double c[3] = {thousandths(p.x), thousandths(p.y), thousandths(p.z)};
-        for (int k = 0; k < 3; k++) {
-            if (!(fabs(c[k]) <= 2147483647.0)) *overflow = 1;
-            ws[(sb * 3 + k) * G + g] = (int32_t)fmax(-2147483647.0, fmin(2147483647.0, c[k]));
-        }
+        int v[3];
+        if (!posed_thousandths(m, poses + (s * G + g) * stride, backbone[b], INT_MAX, v)) *overflow = 1;
+        for (int k = 0; k < 3; k++) ws[(sb * 3 + k) * G + g] = v[k];
     }
 }
 
@@ -169,9 +166,7 @@ unsigned grid_for(size_t total) {
 //      and a surviving residue pair is walked 8 x 8 atoms at a time, stopping at the first contact.  (Groups of
 //      consecutive RECEPTOR residues cull nothing on 1k4c: its membrane beads follow each other in the file, not in space.)
 //   4. bits are ORed in LDS and every output word is stored once.
-// Every coordinate is within +-kCoordBound (the call fails otherwise), so the difference of any two fits an int32.
-
-constexpr int kCoordBound = 1000000000;        // thousandths: +-1.0e6 A
+// Every coordinate is within +-kComplexCoordBound (the call fails otherwise), so the difference of any two fits an int32.
 
 // The boxes and their exact distance test: kernels/complex_pose.hpp, shared with kernels/fcc.hip.
 
@@ -199,13 +194,10 @@ __global__ void __launch_bounds__(kContactThreads, 8) complex_contacts(ComplexDe
         // every atom is posed once; its residue's box falls out of the same pass (min / max are order-free)
 #pragma unroll 1
         for (int a = tid; a < d.n_atoms; a += kContactThreads) {
-            const P3 p = pose_atom(m, row, (uint32_t)a);
-            const double c[3] = {thousandths(p.x), thousandths(p.y), thousandths(p.z)};
-            const int r = (int)d.res_of_atom[a];
             int v[3];
+            if (!posed_thousandths(m, row, (uint32_t)a, kComplexCoordBound, v)) *overflow = 1;
+            const int r = (int)d.res_of_atom[a];
             for (int k = 0; k < 3; k++) {
-                if (!(fabs(c[k]) <= (double)kCoordBound)) *overflow = 1;
-                v[k] = (int)fmax(-(double)kCoordBound, fmin((double)kCoordBound, c[k]));  // clamped: nothing later can wrap
                 atomicMin(&box[k * n_boxes + r], v[k]);
                 atomicMax(&box[(3 + k) * n_boxes + r], v[k]);
             }

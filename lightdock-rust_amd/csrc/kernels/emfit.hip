@@ -3,7 +3,7 @@
 // Everything is integers on the thousandths "%8.3f" prints; the device evaluates no exp.
 //   emfit_init: every pose's row of sums starts from the base row (the rigid receptor's) or 0, its box empty.
 //   emfit_fill: every pose's output grid starts from the base grid or 0 (ld_complex_simulate_density only).
-//   emfit_pose: a thread an atom that takes part and a pose: posed (complex_pose.hpp), rounded, kept as int4 (x, y, z,
+//   emfit_pose: a thread an atom that takes part and a pose: posed (complex_rule.hpp), rounded, kept as int4 (x, y, z,
 //     weight).  The workgroup's box and its count of atoms in no voxel's cell meet in LDS and go out as one atomic each.
 //   emfit_list: a workgroup a pose turns the pose's box, widened by the table's reach, into a box of bricks and appends
 //     (pose, brick) items to one list.  The list, not the grid, sizes the work that follows.
@@ -25,7 +25,7 @@ namespace ld {
 namespace {
 
 static_assert(kEmfitThreads == 256, "four waves; the reduction below counts on it");
-static_assert(2ll * kSaxsCoordBound + 2ll * kEmfitMaxAxis * kEmfitMaxStep < (1ll << 31), "a coordinate less a voxel's centre fits an int32");
+static_assert(2ll * kComplexCoordBound + 2ll * kEmfitMaxAxis * kEmfitMaxStep < (1ll << 31), "a coordinate less a voxel's centre fits an int32");
 
 __global__ void __launch_bounds__(256) emfit_init(ld_density_sums *rows, EmfitBox *boxes, const ld_density_sums *from, size_t n) {
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -53,13 +53,10 @@ __global__ void __launch_bounds__(kEmfitPoseThreads) emfit_pose(ComplexDevice m,
     if (threadIdx.x == 3) s_outside = 0;
     __syncthreads();
     if (a < count) {
-        const P3 p = pose_atom(m, poses + pose * stride, d.part_atom[first + a]);
-        const double c[3] = {thousandths(p.x), thousandths(p.y), thousandths(p.z)};
         int v[3];
+        if (!posed_thousandths(m, poses + pose * stride, d.part_atom[first + a], kComplexCoordBound, v)) *overflow = 1;
         bool outside = false;
         for (int k = 0; k < 3; k++) {
-            if (!(fabs(c[k]) <= (double)kSaxsCoordBound)) *overflow = 1;
-            v[k] = (int)fmax(-(double)kSaxsCoordBound, fmin((double)kSaxsCoordBound, c[k]));  // clamped: nothing later can wrap
             atomicMin(&s_lo[k], v[k]);
             atomicMax(&s_hi[k], v[k]);
             outside |= emfit_axis_outside(v[k], map.origin[k], map.step[k], map.n[k]);

@@ -21,8 +21,6 @@ namespace ld {
 
 namespace {
 
-constexpr int kPairCoordBound = 1000000000;  // thousandths: +-1.0e6 A, as complex_contacts
-
 template <typename T>
 __device__ __forceinline__ T wave_inclusive_scan(T v, int lane) {
     for (int s = 1; s < 64; s <<= 1) {
@@ -85,13 +83,10 @@ __global__ void __launch_bounds__(kPairThreads, 8) complex_pair_sets(ComplexDevi
         __syncthreads();
 #pragma unroll 1
         for (int a = tid; a < d.n_atoms; a += kPairThreads) {
-            const P3 p = pose_atom(m, row, (uint32_t)a);
-            const double c[3] = {thousandths(p.x), thousandths(p.y), thousandths(p.z)};
-            const int r = (int)d.res_of_atom[a];
             int v[3];
+            if (!posed_thousandths(m, row, (uint32_t)a, kComplexCoordBound, v)) *overflow = 1;
+            const int r = (int)d.res_of_atom[a];
             for (int k = 0; k < 3; k++) {
-                if (!(fabs(c[k]) <= (double)kPairCoordBound)) *overflow = 1;
-                v[k] = (int)fmax(-(double)kPairCoordBound, fmin((double)kPairCoordBound, c[k]));
                 atomicMin(&box[k * n_boxes + r], v[k]);
                 atomicMax(&box[(3 + k) * n_boxes + r], v[k]);
             }

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <climits>
 
 namespace ld {
 
@@ -69,12 +70,9 @@ __global__ void __launch_bounds__(kPoseThreads) ranked_pose(ComplexDevice m, con
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
         const size_t a = t / n;
         const size_t p = t - a * n;
-        const P3 v = pose_atom(m, poses + p * stride, walk[a]);
-        const double c[3] = {thousandths(v.x), thousandths(v.y), thousandths(v.z)};
-        for (int k = 0; k < 3; k++) {
-            if (!(fabs(c[k]) <= 2147483647.0)) status->overflow = 1;
-            ws[(a * 3 + k) * n + p] = (int32_t)fmax(-2147483647.0, fmin(2147483647.0, c[k]));
-        }
+        int v[3];
+        if (!posed_thousandths(m, poses + p * stride, walk[a], INT_MAX, v)) status->overflow = 1;
+        for (int k = 0; k < 3; k++) ws[(a * 3 + k) * n + p] = v[k];
     }
 }
 

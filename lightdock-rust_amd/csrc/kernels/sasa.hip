@@ -3,7 +3,7 @@
 // complex.cpp.  Shrake-Rupley on the thousandths "%8.3f" prints, all integers.
 //   complex_sasa: one workgroup a pose at a time (a launch has at most kSasaSlots workgroups, each with a workspace slot it
 //   reuses for pose blockIdx, blockIdx + gridDim, ...):
-//     1. every atom that takes part is posed once (complex_pose.hpp), rounded and kept as int4 (x, y, z, E) in the slot;
+//     1. every atom that takes part is posed once (complex_rule.hpp), rounded and kept as int4 (x, y, z, E) in the slot;
 //        the same pass folds it into the int32 box of its molecule in LDS;
 //     2. a cell grid PER MOLECULE over that molecule's own box: the edge is the smallest multiple of 2 E_max + 2 at which
 //        the grid has at most kSasaCells cells, so a huge extent coarsens the grid and never overflows the LDS offsets.
@@ -28,7 +28,6 @@ namespace ld {
 
 namespace {
 
-constexpr int kCoordBound = 1000000000;  // thousandths: +-1.0e6 A; the difference of two coordinates fits an int32
 constexpr int kWaves = kSasaThreads / 64;
 constexpr int kScanRun = 2 * kSasaCells / kSasaThreads;  // offsets a thread scans
 static_assert(kScanRun * kSasaThreads == 2 * kSasaCells, "the scan deals the offsets evenly");
@@ -161,13 +160,10 @@ __global__ void __launch_bounds__(kSasaThreads) complex_sasa(ComplexDevice m, Sa
         __syncthreads();
 #pragma unroll 1
         for (int a = tid; a < d.n_part; a += kSasaThreads) {
-            const P3 p = pose_atom(m, row, d.part_atom[a]);
-            const double c[3] = {thousandths(p.x), thousandths(p.y), thousandths(p.z)};
-            int *box = s_box[a >= d.n_part_rec];
             int v[3];
+            if (!posed_thousandths(m, row, d.part_atom[a], kComplexCoordBound, v)) *overflow = 1;
+            int *box = s_box[a >= d.n_part_rec];
             for (int k = 0; k < 3; k++) {
-                if (!(fabs(c[k]) <= (double)kCoordBound)) *overflow = 1;
-                v[k] = (int)fmax(-(double)kCoordBound, fmin((double)kCoordBound, c[k]));  // clamped: nothing later can wrap
                 atomicMin(&box[k], v[k]);
                 atomicMax(&box[3 + k], v[k]);
             }

@@ -1,7 +1,7 @@
 // saxs.hip -- K3h: the pair-distance histogram of every pose by pair class, and the Debye sum over it (gfx950; DESIGN §5
 // K3h; lightdock_hip.h, "Small-angle scattering").  The kernels and their launchers (kernels/saxs.hpp); the host side is
 // saxs.cpp.  The histogram is exact integers on the thousandths "%8.3f" prints; the Debye sum is f64 in a fixed order.
-//   saxs_pose: a thread an atom that takes part and a pose: posed (complex_pose.hpp), rounded, kept as int4 (x, y, z, class).
+//   saxs_pose: a thread an atom that takes part and a pose: posed (complex_rule.hpp), rounded, kept as int4 (x, y, z, class).
 //   saxs_rows: every pose's row of counts starts from the base row (the receptor's own pairs when it has no modes) or 0.
 //   saxs_histogram: a workgroup takes one pose and a range of the tile pairs (ta <= tb, tb-major, tiles of kSaxsTile
 //     atoms).  Its 21 x bins words are in LDS.  The b-tile is in LDS; a lane of either half of the workgroup holds one
@@ -26,20 +26,15 @@ namespace {
 
 static_assert(kSaxsThreads == 2 * kSaxsTile, "two halves, an a-atom a lane of each");
 static_assert((unsigned long long)kSaxsMaxBins * kSaxsMaxWidth < kSaxsAxisClamp, "a clamped axis is beyond the last bin");
-static_assert(2ll * kSaxsCoordBound < (1ll << 31), "the difference of two coordinates fits an int32");
+static_assert(2ll * kComplexCoordBound < (1ll << 31), "the difference of two coordinates fits an int32");
 
 __global__ void __launch_bounds__(kSaxsPoseThreads) saxs_pose(ComplexDevice m, SaxsDevice d, const double *poses, size_t stride,
                                                               int first, int count, int4 *out, size_t out_stride, int *overflow) {
     const int a = blockIdx.x * kSaxsPoseThreads + threadIdx.x;
     if (a >= count) return;
     const size_t pose = blockIdx.y;
-    const P3 p = pose_atom(m, poses + pose * stride, d.part_atom[first + a]);
-    const double c[3] = {thousandths(p.x), thousandths(p.y), thousandths(p.z)};
     int v[3];
-    for (int k = 0; k < 3; k++) {
-        if (!(fabs(c[k]) <= (double)kSaxsCoordBound)) *overflow = 1;
-        v[k] = (int)fmax(-(double)kSaxsCoordBound, fmin((double)kSaxsCoordBound, c[k]));  // clamped: nothing later can wrap
-    }
+    if (!posed_thousandths(m, poses + pose * stride, d.part_atom[first + a], kComplexCoordBound, v)) *overflow = 1;
     out[pose * out_stride + a] = make_int4(v[0], v[1], v[2], (int)d.part_class[first + a]);
 }
 

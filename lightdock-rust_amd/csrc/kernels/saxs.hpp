@@ -27,7 +27,6 @@ constexpr int kSaxsPoseThreads = 256;
 constexpr int kSaxsDebyeThreads = 256;
 constexpr int kSaxsTargetGroups = 2048;      // workgroups the histogram launch aims at: 256 CUs x up to 3 resident, and a tail
 constexpr uint32_t kSaxsAxisClamp = (1u << 22) - 1;  // > 1024 x 2000: a clamped pair is beyond the last bin anyway
-constexpr int kSaxsCoordBound = 1000000000;  // thousandths: +-1.0e6 A; the difference of two coordinates fits an int32
 // The kernel's f32 estimate of d / w: the differences are exact in f32 below 2^24, the sum of three squares takes three
 // roundings (relative error 3 u, u = 2^-24), v_sqrt_f32 halves that and adds its 1 ulp (2 u), 1 / w and the product add
 // u each: 5.5 u in all, so below 2^-10 / 5.5 u = 2978 bins the estimate is within 2^-10 of d / w.  Its floor is the bin

@@ -21,6 +21,7 @@
 #include "kernels/gso_step.hpp"
 #include "kernels/pose_energy.hpp"
 #include "lightdock_hip.h"
+#include "stub_access.hpp"
 
 extern "C" {
 hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
@@ -63,20 +64,7 @@ const char *hipGetErrorString(hipError_t) { return "hip stub"; }
 
 namespace ld {
 // kernel launch entry points: the arguments are touched, nothing runs
-// touch / peek: the first and the last element of a buffer a kernel writes / reads, the extent as the kernel indexes it
-template <typename T>
-static void touch(T *base, size_t count) {
-    if (!count) return;
-    base[0] = T();
-    base[count - 1] = T();
-}
-template <typename T>
-static void peek(const T *base, size_t count) {
-    if (!count) return;
-    volatile T first = base[0], last = base[count - 1];
-    (void)first;
-    (void)last;
-}
+// touch / peek (stub_access.hpp): the first and the last element of a buffer a kernel writes / reads, the extent as the kernel indexes it
 size_t pair_kernel_lds_bytes(const PairLaunch &) { return 0; }
 const char *pair_kernel_name(int method) { return method == 0 ? "pose_energy_pairs<0" : "pose_energy_pairs<1"; }
 static void peek_molecule(const DeviceMolecule &m, bool dfire) {
@@ -190,13 +178,6 @@ hipError_t launch_bm_gather(const BmLaunch &t, hipStream_t) {
 }
 // The analysis launches (kernels/cluster.hpp) likewise: the first and the last element of every buffer a kernel reads or writes,
 // the extents from the launch arguments as the kernels of cluster.hip index them, not from complex.cpp's sizing.
-static void peek_complex(const ComplexDevice &m, const double *poses, size_t stride, size_t n_poses) {
-    peek(m.rec_xyz, 3 * (size_t)m.n_rec);
-    peek(m.lig_xyz, 3 * (size_t)m.n_lig);
-    peek(m.rec_modes, (size_t)m.anm_rec * m.n_rec * 3);
-    peek(m.lig_modes, (size_t)m.anm_lig * m.n_lig * 3);
-    if (n_poses) peek(poses, (n_poses - 1) * stride + 7 + m.anm_rec + m.anm_lig);   // row i: poses + i * stride
-}
 hipError_t launch_complex_pose_xyz(const ComplexDevice &m, const double *poses, size_t stride, size_t n, double *out, hipStream_t) {
     peek_complex(m, poses, stride, n);
     std::memset(out, 0, n * (size_t)(m.n_rec + m.n_lig) * 3 * sizeof(double));   // ld_complex_write_pdb prints these

@@ -8,23 +8,9 @@
 #include <cstring>
 
 #include "kernels/assess.hpp"
+#include "stub_access.hpp"
 
 namespace ld {
-
-template <typename T>
-static void touch(T *base, size_t count) {
-    if (!count) return;
-    std::memset(&base[0], 0, sizeof(T));
-    std::memset(&base[count - 1], 0, sizeof(T));
-}
-template <typename T>
-static void peek(const T *base, size_t count) {
-    if (!count) return;
-    volatile unsigned char first = *reinterpret_cast<const unsigned char *>(&base[0]);
-    volatile unsigned char last = reinterpret_cast<const unsigned char *>(&base[count - 1])[sizeof(T) - 1];
-    (void)first;
-    (void)last;
-}
 
 static void add_atom(long long *w, const long long m[3], const long long r[3]) {
     for (int a = 0; a < 3; a++) {
@@ -40,11 +26,7 @@ hipError_t launch_complex_assess_sums(const ComplexDevice &m, const AssessDevice
     if (C2 < 1 || C2 > 900000000u) return hipErrorInvalidValue;   // C <= 30000: the clamped 32-bit test
     if (d.n_used < 1 || (size_t)d.n_used > kAssessMaxUsed || d.n_used_rec < 0 || d.n_used_rec > d.n_used || d.n_native < 1)
         return hipErrorInvalidValue;
-    peek(m.rec_xyz, 3 * (size_t)m.n_rec);
-    peek(m.lig_xyz, 3 * (size_t)m.n_lig);
-    peek(m.rec_modes, (size_t)m.anm_rec * m.n_rec * 3);
-    peek(m.lig_modes, (size_t)m.anm_lig * m.n_lig * 3);
-    peek(poses, (n - 1) * stride + 7 + m.anm_rec + m.anm_lig);   // row i: poses + i * stride
+    peek_complex(m, poses, stride, n);
     peek(d.used_atom, (size_t)d.n_used);
     peek(d.used_ref, (size_t)d.n_used);
     peek(d.native, (size_t)d.n_native);

@@ -2,7 +2,7 @@
 // launches of kernels/ccs.hpp, beside tests/asan/hip_stub.cpp which stands in for the HIP runtime and every other kernel.
 // Device memory is host memory there, so ASan checks every extent below against what ccs.cpp allocated.  The launches do
 // their kernels' work in plain C++ from the rule both sides share (ccs_project, ccs_row_span, ccs_box, kCcsFrames: host code
-// too): posing and rounding restated in f64 with the kernel's operation order, then every view row by row -- the atoms'
+// too): posing and rounding by the kernel's own kernels/complex_rule.hpp, then every view row by row -- the atoms'
 // column intervals of a row merged and counted, the rigid receptor's bits of that row added where no interval holds them.
 // No pieces and no LDS bitmap, so a disagreement with the kernel's structure would show.
 #include <algorithm>
@@ -13,58 +13,11 @@
 #include <utility>
 #include <vector>
 
+#include "kernels/complex_rule.hpp"
 #include "kernels/ccs.hpp"
+#include "stub_access.hpp"
 
 namespace ld {
-
-template <typename T>
-static void touch(T *base, size_t count) {
-    if (!count) return;
-    std::memset(&base[0], 0, sizeof(T));
-    std::memset(&base[count - 1], 0, sizeof(T));
-}
-template <typename T>
-static void peek(const T *base, size_t count) {
-    if (!count) return;
-    volatile unsigned char first = *reinterpret_cast<const unsigned char *>(&base[0]);
-    volatile unsigned char last = reinterpret_cast<const unsigned char *>(&base[count - 1])[sizeof(T) - 1];
-    (void)first;
-    (void)last;
-}
-
-// complex_pose.hpp's pose_atom and thousandths, on the host
-static void pose_atom_host(const ComplexDevice &m, const double *row, uint32_t atom, double out[3]) {
-    if ((int)atom < m.n_rec) {
-        for (int c = 0; c < 3; c++) out[c] = m.rec_xyz[3 * (size_t)atom + c];
-        for (int k = 0; k < m.anm_rec; k++)
-            for (int c = 0; c < 3; c++) out[c] += m.rec_modes[((size_t)k * m.n_rec + atom) * 3 + c] * row[7 + k];
-        return;
-    }
-    const uint32_t a = atom - (uint32_t)m.n_rec;
-    double v[3];
-    for (int c = 0; c < 3; c++) v[c] = m.lig_xyz[3 * (size_t)a + c];
-    for (int k = 0; k < m.anm_lig; k++)
-        for (int c = 0; c < 3; c++) v[c] += m.lig_modes[((size_t)k * m.n_lig + a) * 3 + c] * row[7 + m.anm_rec + k];
-    const double qw = row[3], qx = row[4], qy = row[5], qz = row[6], vx = v[0], vy = v[1], vz = v[2];
-    const double aw = qw * 0.0 - qx * vx - qy * vy - qz * vz;
-    const double ax = qw * vx + qx * 0.0 + qy * vz - qz * vy;
-    const double ay = qw * vy - qx * vz + qy * 0.0 + qz * vx;
-    const double az = qw * vz + qx * vy - qy * vx + qz * 0.0;
-    const double n2 = qw * qw + qx * qx + qy * qy + qz * qz;
-    const double bw = qw / n2, bx = -qx / n2, by = -qy / n2, bz = -qz / n2;
-    out[0] = aw * bx + ax * bw + ay * bz - az * by + row[0];
-    out[1] = aw * by - ax * bz + ay * bw + az * bx + row[1];
-    out[2] = aw * bz + ax * by - ay * bx + az * bw + row[2];
-}
-
-static double thousandths_host(double x) {
-    const double p = x * 1000.0, e = std::fma(x, 1000.0, -p), f = std::floor(p);
-    if (p - f == 0.5) {
-        if (e > 0.0) return f + 1.0;
-        if (e < 0.0) return f;
-    }
-    return std::rint(p);
-}
 
 typedef std::map<int, std::vector<std::pair<int, int>>> Rows;   // row j -> the column intervals of the atoms
 
@@ -116,11 +69,7 @@ hipError_t launch_complex_ccs(const ComplexDevice &m, const CcsDevice &d, const 
     if ((d.rec_views == nullptr) != (d.rec_bits == nullptr)) return hipErrorInvalidValue;
     const bool rigid = d.rec_bits != nullptr;
     if (rigid && m.anm_rec != 0) return hipErrorInvalidValue;
-    peek(m.rec_xyz, 3 * (size_t)m.n_rec);
-    peek(m.lig_xyz, 3 * (size_t)m.n_lig);
-    peek(m.rec_modes, (size_t)m.anm_rec * m.n_rec * 3);
-    peek(m.lig_modes, (size_t)m.anm_lig * m.n_lig * 3);
-    peek(poses, (n - 1) * stride + 7 + m.anm_rec + m.anm_lig);   // row i: poses + i * stride
+    peek_complex(m, poses, stride, n);
     peek(d.part_atom + d.first, (size_t)d.count);
     peek(d.part_radius + d.first, (size_t)d.count);
     touch(static_cast<char *>(ws), slots * ccs_slot_bytes(d.count));   // ws + blockIdx * ccs_slot_bytes
@@ -139,14 +88,8 @@ hipError_t launch_complex_ccs(const ComplexDevice &m, const CcsDevice &d, const 
         const double *row = poses + i * stride;
         bool bad = false;
         for (int a = 0; a < d.count; a++) {
-            double p[3];
             int v[3];
-            pose_atom_host(m, row, d.part_atom[d.first + a], p);
-            for (int k = 0; k < 3; k++) {
-                const double c = thousandths_host(p[k]);
-                if (!(std::fabs(c) <= (double)kCcsCoordBound)) *overflow |= 1, bad = true;
-                v[k] = (int)std::fmax(-(double)kCcsCoordBound, std::fmin((double)kCcsCoordBound, c));
-            }
+            if (!posed_thousandths(m, row, d.part_atom[d.first + a], kComplexCoordBound, v)) *overflow |= 1, bad = true;
             atoms[a] = make_int4(v[0], v[1], v[2], (int)d.part_radius[d.first + a] + d.probe);
         }
         unsigned long long total = 0;

@@ -9,24 +9,9 @@
 #include "kernels/decompose.hpp"
 #include "kernels/decompose_pair.hpp"
 #include "kernels/pose_energy.hpp"
+#include "stub_access.hpp"
 
 namespace ld {
-
-template <typename T>
-static void touch(T *base, size_t count) {
-    if (!count) return;
-    T first = base[0], last = base[count - 1];
-    base[0] = first;
-    base[count - 1] = last;
-}
-template <typename T>
-static void peek(const T *base, size_t count) {
-    if (!count) return;
-    volatile unsigned char first = *reinterpret_cast<const unsigned char *>(&base[0]);
-    volatile unsigned char last = reinterpret_cast<const unsigned char *>(&base[count - 1])[sizeof(T) - 1];
-    (void)first;
-    (void)last;
-}
 
 static void peek_molecule(const DecomposeMolecule &m, bool dfire) {
     const size_t n_pad = (size_t)m.n_pad;
@@ -66,8 +51,8 @@ hipError_t launch_decompose_pose(const DecomposeLaunch &d, hipStream_t) {
     if (!sane(d)) return hipErrorInvalidValue;
     peek_inputs(d);
     const size_t P = (size_t)d.n_poses;
-    touch(d.lig_xyz, P * 3 * d.lig.n_pad);
-    if (d.rec_xyz) touch(d.rec_xyz, P * 3 * d.rec.n_pad);
+    peek(d.lig_xyz, P * 3 * d.lig.n_pad);
+    if (d.rec_xyz) peek(d.rec_xyz, P * 3 * d.rec.n_pad);
     for (size_t p = 0; p < P; p++) {
         const double *row = d.poses + p * d.stride;
         for (int side = 0; side < 2; side++) {
@@ -97,9 +82,9 @@ hipError_t launch_decompose_side(const DecomposeLaunch &d, int side, hipStream_t
     uint32_t *pairs = side ? d.lig_pairs : d.rec_pairs, *flag = side ? d.lig_flag : d.rec_flag;
     peek(d.lig_xyz, P * 3 * nl);
     if (d.rec_xyz) peek(d.rec_xyz, P * 3 * nr);
-    touch(sum, P * 2 * no);
-    touch(pairs, P * no);
-    touch(flag, P * no);
+    peek(sum, P * 2 * no);
+    peek(pairs, P * no);
+    peek(flag, P * no);
     for (size_t p = 0; p < P; p++) {
         const double *rx = d.rec_xyz ? d.rec_xyz + p * 3 * nr : d.rec.x, *ry = d.rec_xyz ? rx + nr : d.rec.y, *rz = d.rec_xyz ? ry + nr : d.rec.z;
         const double *lx = d.lig_xyz + p * 3 * nl, *ly = lx + nl, *lz = ly + nl;
@@ -140,9 +125,9 @@ hipError_t launch_decompose_groups(const DecomposeLaunch &d, int side, const Dec
     const int n = side ? d.lig.n : d.rec.n;
     peek(g.offsets, G + 1);
     peek(g.atoms, (size_t)g.offsets[G]);
-    if (g.sums) touch(g.sums, P * G * 2);
-    if (g.pairs) touch(g.pairs, P * G);
-    if (g.iface) touch(g.iface, P * G);
+    if (g.sums) peek(g.sums, P * G * 2);
+    if (g.pairs) peek(g.pairs, P * G);
+    if (g.iface) peek(g.iface, P * G);
     const double *sum = side ? d.lig_sum : d.rec_sum;
     const uint32_t *pairs = side ? d.lig_pairs : d.rec_pairs, *flag = side ? d.lig_flag : d.rec_flag;
     for (size_t p = 0; p < P; p++)
@@ -185,7 +170,7 @@ hipError_t launch_decompose_terms(const DecomposeLaunch &d, const DecomposeTail 
     peek(t.lig_offsets, (size_t)t.n_lig_groups + 1);
     peek(t.lig_atoms, (size_t)t.lig_offsets[t.n_lig_groups]);
     peek(t.membrane, (size_t)t.n_membrane);
-    touch(terms, P);
+    peek(terms, P);
     for (size_t p = 0; p < P; p++) {
         const double *sum = d.rec_sum + p * 2 * nr;
         const uint32_t *rflag = d.rec_flag + p * nr, *lflag = d.lig_flag + p * nl;

@@ -2,7 +2,7 @@
 // launches of kernels/emfit.hpp, beside tests/asan/hip_stub.cpp which stands in for the HIP runtime and every other kernel.
 // Device memory is host memory there, so ASan checks every extent below against what emfit.cpp allocated.  The launches do
 // their kernels' work in plain C++ from the rule both sides share (emfit_weight, emfit_index, emfit_axis_outside,
-// emfit_axis_range: host code too): posing and rounding restated in f64 with the kernel's operation order, then for every
+// emfit_axis_range: host code too): posing and rounding by the kernel's own kernels/complex_rule.hpp, then for every
 // listed brick every voxel against every atom -- no tiles, no hit list, no columns, so a disagreement with the kernel's
 // structure would show.
 #include <climits>
@@ -10,58 +10,11 @@
 #include <cstring>
 #include <vector>
 
+#include "kernels/complex_rule.hpp"
 #include "kernels/emfit.hpp"
+#include "stub_access.hpp"
 
 namespace ld {
-
-template <typename T>
-static void touch(T *base, size_t count) {
-    if (!count) return;
-    std::memset(&base[0], 0, sizeof(T));
-    std::memset(&base[count - 1], 0, sizeof(T));
-}
-template <typename T>
-static void peek(const T *base, size_t count) {
-    if (!count) return;
-    volatile unsigned char first = *reinterpret_cast<const unsigned char *>(&base[0]);
-    volatile unsigned char last = reinterpret_cast<const unsigned char *>(&base[count - 1])[sizeof(T) - 1];
-    (void)first;
-    (void)last;
-}
-
-// complex_pose.hpp's pose_atom and thousandths, on the host
-static void pose_atom_host(const ComplexDevice &m, const double *row, uint32_t atom, double out[3]) {
-    if ((int)atom < m.n_rec) {
-        for (int c = 0; c < 3; c++) out[c] = m.rec_xyz[3 * (size_t)atom + c];
-        for (int k = 0; k < m.anm_rec; k++)
-            for (int c = 0; c < 3; c++) out[c] += m.rec_modes[((size_t)k * m.n_rec + atom) * 3 + c] * row[7 + k];
-        return;
-    }
-    const uint32_t a = atom - (uint32_t)m.n_rec;
-    double v[3];
-    for (int c = 0; c < 3; c++) v[c] = m.lig_xyz[3 * (size_t)a + c];
-    for (int k = 0; k < m.anm_lig; k++)
-        for (int c = 0; c < 3; c++) v[c] += m.lig_modes[((size_t)k * m.n_lig + a) * 3 + c] * row[7 + m.anm_rec + k];
-    const double qw = row[3], qx = row[4], qy = row[5], qz = row[6], vx = v[0], vy = v[1], vz = v[2];
-    const double aw = qw * 0.0 - qx * vx - qy * vy - qz * vz;
-    const double ax = qw * vx + qx * 0.0 + qy * vz - qz * vy;
-    const double ay = qw * vy - qx * vz + qy * 0.0 + qz * vx;
-    const double az = qw * vz + qx * vy - qy * vx + qz * 0.0;
-    const double n2 = qw * qw + qx * qx + qy * qy + qz * qz;
-    const double bw = qw / n2, bx = -qx / n2, by = -qy / n2, bz = -qz / n2;
-    out[0] = aw * bx + ax * bw + ay * bz - az * by + row[0];
-    out[1] = aw * by - ax * bz + ay * bw + az * bx + row[1];
-    out[2] = aw * bz + ax * by - ay * bx + az * bw + row[2];
-}
-
-static double thousandths_host(double x) {
-    const double p = x * 1000.0, e = std::fma(x, 1000.0, -p), f = std::floor(p);
-    if (p - f == 0.5) {
-        if (e > 0.0) return f + 1.0;
-        if (e < 0.0) return f;
-    }
-    return std::rint(p);
-}
 
 static bool map_ok(const EmfitMap &map) {
     for (int k = 0; k < 3; k++)
@@ -107,14 +60,10 @@ hipError_t launch_emfit_pose(const ComplexDevice &m, const SaxsDevice &d, const 
     for (size_t i = 0; i < n; i++)
         for (int a = 0; a < count; a++) {
             if (d.part_class[first + a] >= kSaxsClasses) return hipErrorInvalidValue;
-            double p[3];
-            pose_atom_host(m, poses + i * stride, d.part_atom[first + a], p);
             int v[3];
+            if (!posed_thousandths(m, poses + i * stride, d.part_atom[first + a], kComplexCoordBound, v)) *overflow = 1;
             bool outside = false;
             for (int k = 0; k < 3; k++) {
-                const double c = thousandths_host(p[k]);
-                if (!(std::fabs(c) <= (double)kSaxsCoordBound)) *overflow = 1;
-                v[k] = (int)std::fmax(-(double)kSaxsCoordBound, std::fmin((double)kSaxsCoordBound, c));
                 if (v[k] < boxes[i].lo[k]) boxes[i].lo[k] = v[k];
                 if (v[k] > boxes[i].hi[k]) boxes[i].hi[k] = v[k];
                 outside = outside || emfit_axis_outside(v[k], map.origin[k], map.step[k], map.n[k]);

@@ -2,65 +2,18 @@
 // launches of kernels/fcc.hpp, beside tests/asan/hip_stub.cpp which stands in for the HIP runtime and every other kernel.
 // Device memory is host memory there, so ASan checks every extent below against what fcc.cpp allocated.  The launches do
 // their kernels' work in plain C++ from the rule both sides share (fcc_neighbours is host code too): posing and rounding
-// restated in f64 with the kernel's operation order, every atom pair of every residue pair -- no boxes, no bitmap of a slot --
+// by the kernel's own kernels/complex_rule.hpp, every atom pair of every residue pair -- no boxes, no bitmap of a slot --
 // and sets compared key by key, not as bit rows' words, so a disagreement with the kernels' structure would show.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "kernels/complex_rule.hpp"
 #include "kernels/fcc.hpp"
+#include "stub_access.hpp"
 
 namespace ld {
-
-template <typename T>
-static void touch(T *base, size_t count) {
-    if (!count) return;
-    std::memset(&base[0], 0, sizeof(T));
-    std::memset(&base[count - 1], 0, sizeof(T));
-}
-template <typename T>
-static void peek(const T *base, size_t count) {
-    if (!count) return;
-    volatile unsigned char first = *reinterpret_cast<const unsigned char *>(&base[0]);
-    volatile unsigned char last = reinterpret_cast<const unsigned char *>(&base[count - 1])[sizeof(T) - 1];
-    (void)first;
-    (void)last;
-}
-
-// complex_pose.hpp's pose_atom and thousandths, on the host
-static void pose_atom_host(const ComplexDevice &m, const double *row, uint32_t atom, double out[3]) {
-    if ((int)atom < m.n_rec) {
-        for (int c = 0; c < 3; c++) out[c] = m.rec_xyz[3 * (size_t)atom + c];
-        for (int k = 0; k < m.anm_rec; k++)
-            for (int c = 0; c < 3; c++) out[c] += m.rec_modes[((size_t)k * m.n_rec + atom) * 3 + c] * row[7 + k];
-        return;
-    }
-    const uint32_t a = atom - (uint32_t)m.n_rec;
-    double v[3];
-    for (int c = 0; c < 3; c++) v[c] = m.lig_xyz[3 * (size_t)a + c];
-    for (int k = 0; k < m.anm_lig; k++)
-        for (int c = 0; c < 3; c++) v[c] += m.lig_modes[((size_t)k * m.n_lig + a) * 3 + c] * row[7 + m.anm_rec + k];
-    const double qw = row[3], qx = row[4], qy = row[5], qz = row[6], vx = v[0], vy = v[1], vz = v[2];
-    const double aw = qw * 0.0 - qx * vx - qy * vy - qz * vz;
-    const double ax = qw * vx + qx * 0.0 + qy * vz - qz * vy;
-    const double ay = qw * vy - qx * vz + qy * 0.0 + qz * vx;
-    const double az = qw * vz + qx * vy - qy * vx + qz * 0.0;
-    const double n2 = qw * qw + qx * qx + qy * qy + qz * qz;
-    const double bw = qw / n2, bx = -qx / n2, by = -qy / n2, bz = -qz / n2;
-    out[0] = aw * bx + ax * bw + ay * bz - az * by + row[0];
-    out[1] = aw * by - ax * bz + ay * bw + az * bx + row[1];
-    out[2] = aw * bz + ax * by - ay * bx + az * bw + row[2];
-}
-
-static double thousandths_host(double x) {
-    const double p = x * 1000.0, e = std::fma(x, 1000.0, -p), f = std::floor(p);
-    if (p - f == 0.5) {
-        if (e > 0.0) return f + 1.0;
-        if (e < 0.0) return f;
-    }
-    return std::rint(p);
-}
 
 hipError_t launch_complex_pair_sets(const ComplexDevice &m, const ContactsDevice &d, const double *poses, size_t stride, size_t n,
                                     uint32_t C2, size_t slots, int4 *atoms_ws, int *boxes_ws, uint32_t *pairs_ws,
@@ -69,11 +22,7 @@ hipError_t launch_complex_pair_sets(const ComplexDevice &m, const ContactsDevice
     if (slots < 1 || slots > (size_t)kPairSlots || slots > n) return hipErrorInvalidValue;
     if ((kPairThreads / 64) * sizeof(uint32_t) + (d.boxes_in_lds ? n_boxes * 6 * sizeof(int) : 0) > 160 * 1024) return hipErrorInvalidValue;
     if ((uint64_t)d.n_rec_res * (uint64_t)d.n_lig_res >= (uint64_t(1) << 32) || d.n_atoms != m.n_rec + m.n_lig) return hipErrorInvalidValue;
-    peek(m.rec_xyz, 3 * (size_t)m.n_rec);
-    peek(m.lig_xyz, 3 * (size_t)m.n_lig);
-    peek(m.rec_modes, (size_t)m.anm_rec * m.n_rec * 3);
-    peek(m.lig_modes, (size_t)m.anm_lig * m.n_lig * 3);
-    peek(poses, (n - 1) * stride + 7 + m.anm_rec + m.anm_lig);   // row i: poses + i * stride
+    peek_complex(m, poses, stride, n);
     peek(d.res_start, (size_t)d.n_rec_res + d.n_lig_res + 1);
     peek(d.res_of_atom, (size_t)d.n_atoms);
     touch(atoms_ws, slots * d.n_atoms);                            // atoms_ws + blockIdx * n_atoms
@@ -84,13 +33,9 @@ hipError_t launch_complex_pair_sets(const ComplexDevice &m, const ContactsDevice
     std::vector<long long> xyz(3 * (size_t)d.n_atoms);
     for (size_t i = 0; i < n; i++) {
         for (int a = 0; a < d.n_atoms; a++) {
-            double p[3];
-            pose_atom_host(m, poses + i * stride, (uint32_t)a, p);
-            for (int k = 0; k < 3; k++) {
-                const double c = thousandths_host(p[k]);
-                if (!(std::fabs(c) <= 1.0e9)) *overflow = 1;
-                xyz[3 * (size_t)a + k] = (long long)std::fmax(-1.0e9, std::fmin(1.0e9, c));
-            }
+            int v[3];
+            if (!posed_thousandths(m, poses + i * stride, (uint32_t)a, kComplexCoordBound, v)) *overflow = 1;
+            for (int k = 0; k < 3; k++) xyz[3 * (size_t)a + k] = v[k];
         }
         uint32_t count = 0;
         size_t at = offsets ? offsets[i] : 0;

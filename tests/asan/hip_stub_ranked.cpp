@@ -9,24 +9,9 @@
 
 #include "kernels/ranked.hpp"
 #include "ranked_host.hpp"
+#include "stub_access.hpp"
 
 namespace ld {
-
-template <typename T>
-static void touch(T *base, size_t count) {
-    if (!count) return;
-    T first = base[0], last = base[count - 1];
-    base[0] = first;
-    base[count - 1] = last;
-}
-template <typename T>
-static void peek(const T *base, size_t count) {
-    if (!count) return;
-    volatile unsigned char first = *reinterpret_cast<const unsigned char *>(&base[0]);
-    volatile unsigned char last = reinterpret_cast<const unsigned char *>(&base[count - 1])[sizeof(T) - 1];
-    (void)first;
-    (void)last;
-}
 
 static bool sane(const RankedLaunch &r) { return r.n >= 1 && r.n_walk >= 1 && r.state && r.reps && r.status; }
 
@@ -55,13 +40,9 @@ hipError_t launch_ranked_begin(const RankedLaunch &r, double cutoff, double n_at
 hipError_t launch_ranked_pose(const ComplexDevice &m, const double *poses, size_t stride, int n, const uint32_t *walk, int n_walk,
                               int32_t *ws, RankedStatus *status, hipStream_t) {
     if (n < 1 || n_walk < 1) return hipErrorInvalidValue;
-    peek(m.rec_xyz, 3 * (size_t)m.n_rec);
-    peek(m.lig_xyz, 3 * (size_t)m.n_lig);
-    peek(m.rec_modes, (size_t)m.anm_rec * m.n_rec * 3);
-    peek(m.lig_modes, (size_t)m.anm_lig * m.n_lig * 3);
-    peek(poses, ((size_t)n - 1) * stride + 7 + m.anm_rec + m.anm_lig);   // row p: poses + p * stride
+    peek_complex(m, poses, stride, (size_t)n);
     peek(walk, (size_t)n_walk);
-    touch(ws, (size_t)n_walk * 3 * n);
+    peek(ws, (size_t)n_walk * 3 * n);
     for (int a = 0; a < n_walk; a++) {
         if (walk[a] >= (uint32_t)(m.n_rec + m.n_lig)) return hipErrorInvalidValue;
         for (int p = 0; p < n; p++) {
@@ -94,8 +75,8 @@ static bool near(const RankedLaunch &r, const int32_t *ws, int p, int q) {
 hipError_t launch_ranked_pick(const RankedLaunch &r, const int32_t *ws, hipStream_t) {
     if (!sane(r)) return hipErrorInvalidValue;
     peek(ws, (size_t)r.n_walk * 3 * r.n);
-    touch(r.state, (size_t)r.n);
-    touch(r.reps, (size_t)r.n);
+    peek(r.state, (size_t)r.n);
+    peek(r.reps, (size_t)r.n);
     RankedStatus *st = r.status;
     if (st->cursor < 0 || st->cursor > r.n || st->n_clusters < 0 || st->n_clusters > st->cursor) return hipErrorInvalidValue;
     int cand[kRankedBlock], lid[kRankedBlock], nc = 0;
@@ -133,7 +114,7 @@ hipError_t launch_ranked_sweep(const RankedLaunch &r, const int32_t *ws, int fro
     const RankedStatus *st = r.status;
     if (from > st->cursor) return hipErrorInvalidValue;   // `from` is a lower bound of the cursor: nothing behind it is skipped
     peek(ws, (size_t)r.n_walk * 3 * r.n);
-    touch(r.state, (size_t)r.n);
+    peek(r.state, (size_t)r.n);
     for (int p = st->cursor; p < r.n; p++) {
         if (r.state[p] != -1) continue;
         for (int l = 0; l < st->n_leaders; l++)

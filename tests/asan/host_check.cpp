@@ -5,6 +5,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +17,7 @@
 #include "check.hpp"
 #include "device_memory.hpp"     // the carver is checked directly
 #include "kernels/cluster.hpp"   // the analysis section sizes its inputs from the constants; every call goes through the C ABI
+#include "kernels/complex_rule.hpp"   // the shared posing rule is checked directly
 
 extern "C" size_t ld_stub_device_allocations(void);   // tests/asan/hip_stub.cpp
 extern "C" size_t ld_stub_device_allocations_of(size_t bytes);
@@ -100,6 +102,58 @@ static void carver() {
             refused = e.code() == LD_ERR_INVALID;
         }
         CHECK(refused && c.bytes() == 4);
+    }
+}
+
+// ---- the posing-and-rounding rule the analysis kernels, ccs.cpp and the stubs share (kernels/complex_rule.hpp), on the host --------
+static bool posed_is(const ld::ComplexDevice &m, const double *row, uint32_t atom, int bound, bool want_ok, int x, int y, int z) {
+    int v[3] = {-1, -1, -1};
+    return ld::posed_thousandths(m, row, atom, bound, v) == want_ok && v[0] == x && v[1] == y && v[2] == z;
+}
+
+static void complex_rule() {
+    // what "%.3f" prints of each, tests/test_contacts_cpu.py's pinned values
+    const double x[7] = {0.0005, -0.0004, 1.2345, -1.2346, 4.9995, -0.0, 123.4565}, want[7] = {1, 0, 1234, -1235, 5000, 0, 123457};
+    for (int i = 0; i < 7; i++) CHECK(ld::thousandths(x[i]) == want[i]);
+    CHECK(ld::thousandths(2.0) == 2000.0 && ld::thousandths(-12.3456) == -12346.0);
+
+    const int B = ld::kComplexCoordBound;
+    static_assert(ld::kComplexCoordBound == 1000000000 && 2ll * ld::kComplexCoordBound < (1ll << 31), "the difference of two coordinates fits an int32");
+    const double identity[7] = {0, 0, 0, 1, 0, 0, 0};
+    double rec[3] = {0, 0, 0}, lig[3] = {0, 0, 0};
+    ld::ComplexDevice m;
+    m.n_rec = 1, m.rec_xyz = rec;
+    // a one-atom receptor at the bound's edge, on every axis and sign: +-1 000 000.000 A fits, one thousandth more does not
+    for (int k = 0; k < 3; k++)
+        for (int sign = -1; sign <= 1; sign += 2) {
+            int at[3] = {0, 0, 0};
+            rec[0] = rec[1] = rec[2] = 0.0;
+            rec[k] = sign * 1000000.0, at[k] = sign * B;
+            CHECK(posed_is(m, identity, 0, B, true, at[0], at[1], at[2]));
+            rec[k] = sign * 1000000.001;
+            CHECK(ld::thousandths(rec[k]) == sign * (B + 1.0) && posed_is(m, identity, 0, B, false, at[0], at[1], at[2]));   // clamped
+            CHECK(posed_is(m, identity, 0, INT_MAX, true, at[0] + (k == 0) * sign, at[1] + (k == 1) * sign, at[2] + (k == 2) * sign));
+            rec[k] = std::nan("");
+            at[k] = B;
+            CHECK(posed_is(m, identity, 0, B, false, at[0], at[1], at[2]));   // a NaN clamps to +bound; UBSan sees the conversion
+            at[k] = INT_MAX;
+            CHECK(posed_is(m, identity, 0, INT_MAX, false, at[0], at[1], at[2]));
+        }
+    rec[0] = 3.0e6, rec[1] = -3.0e6, rec[2] = 0.0;   // beyond an int32 in thousandths
+    CHECK(posed_is(m, identity, 0, INT_MAX, false, INT_MAX, -INT_MAX, 0));
+    // a ligand atom: identity rotation plus translation; the quaternion scaled by 2 divides by its norm^2 and gives the same integers
+    m.n_lig = 1, m.lig_xyz = lig;
+    for (double scale : {1.0, 2.0}) {
+        double row[7] = {0, 0, 0, scale, 0, 0, 0};
+        lig[0] = 1.2345, lig[1] = -1.2346, lig[2] = 4.9995;
+        CHECK(posed_is(m, row, 1, B, true, 1234, -1235, 5000));
+        lig[0] = 1.5, lig[1] = -2.25, lig[2] = 3.125;
+        row[0] = 10.0, row[1] = 20.0, row[2] = -30.0;
+        CHECK(posed_is(m, row, 1, B, true, 11500, 17750, -26875));
+        const ld::P3 p = ld::pose_atom(m, row, 1);
+        CHECK(p.x == 11.5 && p.y == 17.75 && p.z == -26.875);
+        row[1] = 1000000.0 + 2.25, row[2] = -1000000.0 - 3.125 - 0.001;   // the ligand at the edge, and one thousandth past it
+        CHECK(posed_is(m, row, 1, B, false, 11500, B, -B));
     }
 }
 
@@ -526,6 +580,7 @@ int main(int argc, char **argv) {
                                     nullptr, 0, 0, 0, table.data()) == nullptr);
 
     carver();
+    complex_rule();
     analysis(rec1, lig1, scratch);
 
     // ---- the CLI (src/bin/lightdock-rust.rs:77-333): usage errors return 0, panics 101 ---------------

@@ -1,6 +1,6 @@
 // ranked_host.hpp -- TEST INFRASTRUCTURE of the sanitizer build around the ranked clustering (`make asan-ranked`): the posing
-// of one atom, the thousandths "%8.3f" prints and the clustering's RMSD test in plain C++, as kernels/complex_pose.hpp
-// states them for the device.  tests/asan/hip_stub_ranked.cpp poses with it in place of the kernel, and the driver
+// of one atom, the thousandths "%8.3f" prints and the clustering's RMSD test in plain C++, as kernels/complex_rule.hpp and kernels/complex_pose.hpp
+// state them for the device.  tests/asan/hip_stub_ranked.cpp poses with it in place of the kernel, and the driver
 // (tests/asan/ranked_check.cpp) poses with it for its sequential loop, so what the two compare is the clustering.
 #pragma once
 

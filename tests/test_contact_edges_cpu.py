@@ -134,7 +134,8 @@ def test_the_constants_are_the_kernels():
     assert int(re.search(r"kContactThreads = (\d+);", cluster).group(1)) == 64 * ce.WAVES
     assert int(re.search(r"kPairThreads = (\d+);", fcc).group(1)) == 64 * ce.WAVES == ce.SCAN_CHUNK
     assert re.search(r"kMaxBoxLdsBytes = 40 << 10;", cluster) and ce.MAX_BOX_LDS_BYTES == 40 << 10
-    assert re.search(r"kCoordBound = 1000000000;", open(os.path.join(KERNELS, "cluster.hip")).read()) and ce.COORD_BOUND == 10 ** 9
+    assert re.search(r"kComplexCoordBound = 1000000000;", open(os.path.join(KERNELS, "complex_rule.hpp")).read()) and ce.COORD_BOUND == 10 ** 9
+    assert "kComplexCoordBound, v)" in open(os.path.join(KERNELS, "cluster.hip")).read()   # what complex_contacts poses with
     base, big, motif = ce.shape("base"), ce.shape("big"), ce.shape("motif")
     assert (base.n_rec_res, base.n_lig_res, base.n_lig_grp, base.n_boxes) == (520, 517, 65, 1102) and base.boxes_in_lds
     assert base.n_lig_res - 64 * ce.RES_GROUP == 5 and ce.shape("flex").boxes_in_lds
