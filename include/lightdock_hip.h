@@ -695,6 +695,51 @@ int ld_ccs_frames(int32_t *out /* LD_CCS_VIEWS x 2 x 3: A then B */); /* host on
 int ld_complex_ccs(ld_complex *c, size_t n, const double *poses, size_t stride, int what, double probe /* 1.0 */,
                    double cell /* 0.5 */, uint32_t *counts /* n x LD_CCS_VIEWS */, uint64_t *sums /* n */);
 
+/* Cross-links: for every pose and every link of a list (a, b) of atoms that a chemical cross-linker of known length has
+ * joined (XL-MS), the straight distance of the two atoms and the length of the shortest path between them that stays in the
+ * solvent -- the solvent-accessible surface distance (SASD) of Xwalk and Jwalk.  No tool of the reference tree computes a
+ * cross-link distance; the rule is this library's own: shortest paths on a lattice, all integers, in thousandths of an
+ * angstrom as "%8.3f" prints a coordinate.
+ *   Posed atoms: c_x, posing and rounding as above (the ligand's modes in the ligand frame; the integer thousandths
+ *     ld_complex_write_pdb prints).
+ *   Links: L pairs (a, b) of complex atom indices -- receptor atoms first, then ligand atoms, in file order --
+ *     1 <= L <= 4096.  An anchor may be any atom, a hydrogen or an atom that takes no part in the surface too; both anchors
+ *     may lie on the same molecule; a == b is allowed.
+ *   Straight distance: straight2[pose][l] = |c_a - c_b|^2, uint64, exact.
+ *   Blockers: the atoms that take part in the surface and their radii R_x, exactly those of ld_complex_sasa_radii.  Probe:
+ *     0 <= probe <= 2.0 A, p = llrint(1000 * probe), E_x = R_x + p.  The default 0.0 is a parameter of the method.
+ *   Lattice: h = llrint(1000 * cell), 500 <= h <= 2000, default 1000.  The nodes are (i h, j h, k h) for all integers i, j,
+ *     k: anchored at the frame's origin, so the lattice depends neither on the batch nor on the link.  A node q is blocked
+ *     iff some blocker x has |q - c_x|^2 < E_x^2, strictly, in exact integers; otherwise it is free.
+ *   Moves: from a free node to any free node among its 26 neighbours, of weight w1 = h along an axis, w2 = isqrt(2 h^2)
+ *     across a face, w3 = isqrt(3 h^2) across a cube; isqrt is the floor of the square root, in exact integers.
+ *   Reach: rho = llrint(1000 * reach), 1 <= rho <= 6000, default 3000.  The doors of an anchor a are the free nodes q with
+ *     |q - c_a|^2 <= rho^2, inclusively; the hop from a to its door q is s_a(q) = isqrt(|q - c_a|^2).  Atoms do not block a
+ *     hop: it stands for the side chain.
+ *   Path: D(a, b) = the minimum over the doors q of a, the doors q' of b and the lattice paths from q to q' over free nodes
+ *     of s_a(q) + (the sum of the moves' weights) + s_b(q').  A path of no moves is allowed (q = q').
+ *   Cap: M = llrint(1000 * max_length), h <= M <= 60000, default 35000, and floor(M / h) <= 80: a search looks at no more
+ *     than 162^3 nodes (161^3 where h divides M).
+ *   Outputs: path[pose][l] = D as a uint32 if D <= M, else LD_XLINK_NO_PATH: an anchor without a door, an anchor sealed in
+ *     by blocked nodes, or a path longer than M.
+ *   D is symmetric in (a, b).  Every result is the same bits whatever the batch, a pose's place in it, the slot count, the
+ *     order or the repetition of the links, or the schedule of the search: on integer nodes with integer weights the field of
+ *     shortest distances is a unique fixed point.
+ *   A path over the 26 neighbours of a lattice overestimates the true geodesic by a few percent, most in the directions
+ *     farthest from an axis, a face diagonal and a cube diagonal -- the approximation Xwalk and Jwalk make.
+ * LD_ERR_INVALID, nothing written: a probe, a cell, a reach or a max_length out of range or not finite; n_links 0 or above
+ * 4096; an atom index >= the number of atoms of the complex; non-finite poses, a zero quaternion, stride < pose_len; a posed
+ * anchor beyond +-1.0e6 A, or, when `path` is asked for, a posed blocker beyond it; `path` asked for in a complex of which
+ * no atom takes part.  Device workspace: with `path` one slot per workgroup in flight -- 16 B a blocker, 2 B a node of
+ * (2 floor(M / h) + 4)^3 at most and, beyond 48 KiB of them, its bits -- at most 512 slots and 256 MiB (or one slot); without
+ * `path` none.  The outputs leave in chunks of poses within 256 MiB. */
+#define LD_XLINK_NO_PATH (0xFFFFFFFFu)
+/* Either output may be NULL; n == 0 is LD_OK.  ld_complex_last_kernel_ms then reports this call's device work. */
+int ld_complex_crosslinks(ld_complex *c, size_t n, const double *poses, size_t stride, size_t n_links,
+                          const uint32_t *links /* n_links x 2 */, double probe /* 0.0 */, double cell /* 1.0 */,
+                          double reach /* 3.0 */, double max_length /* 35.0 */, uint64_t *straight2 /* n x n_links */,
+                          uint32_t *path /* n x n_links */);
+
 /* Small-angle scattering: for every pose, the histogram of all pair distances by pair class and, from it, the SAXS
  * profile I(q) by the Debye formula, to be fitted to an experimental curve.  No tool of the reference tree computes a
  * profile; the rule is this library's own.  The profile is "vacuum minus excluded volume" of the atoms in the files: no

@@ -207,6 +207,7 @@ def load_library():
     lib.ld_complex_sasa.argtypes = [vp, sz, vp, sz, C.c_double, vp, vp, vp]
     lib.ld_ccs_frames.argtypes = [vp]
     lib.ld_complex_ccs.argtypes = [vp, sz, vp, sz, C.c_int, C.c_double, C.c_double, vp, vp]
+    lib.ld_complex_crosslinks.argtypes = [vp, sz, vp, sz, sz, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
     lib.ld_complex_saxs_classes.argtypes = [vp, C.c_int, vp]
     lib.ld_saxs_form_factors.argtypes = [vp, sz, vp]
     lib.ld_saxs_sinc.argtypes = [vp, sz, C.c_uint32, sz, vp]
@@ -982,6 +983,27 @@ class Complex:
         out["ccs"] = ccs_area(out["sums"], cell) / CCS_VIEWS
         return out
 
+    def crosslinks(self, poses, links, probe=0.0, cell=1.0, reach=3.0, max_length=35.0, paths=True):
+        """(n, >= pose_len) poses, (L, 2) complex atom indices (receptor atoms first, then ligand atoms) -> {"straight2":
+        (n, L) uint64 thousandths^2, "straight": (n, L) float64 A, "path": (n, L) uint32 thousandths}: the straight distance of
+        every link's two atoms and the length of the shortest path between them over the free nodes of a lattice of step
+        `cell`, XLINK_NO_PATH where none of max_length at most exists (ld_complex_crosslinks; lightdock_hip.h, "Cross-links").
+        paths=False leaves "path" out and runs no search."""
+        poses = _f64(poses)
+        if poses.ndim != 2:
+            raise ValueError("poses must be (n, pose_len)")
+        links = np.ascontiguousarray(links, dtype=np.uint32)
+        if links.ndim != 2 or links.shape[1] != 2:
+            raise ValueError("links must be (L, 2)")
+        n, L = poses.shape[0], links.shape[0]
+        out = {"straight2": np.zeros((n, L), dtype=np.uint64)}
+        if paths:
+            out["path"] = np.zeros((n, L), dtype=np.uint32)
+        _check(self.lib.ld_complex_crosslinks(self._h, n, _ptr(poses), poses.shape[1], L, _ptr(links), C.c_double(probe), C.c_double(cell),
+                                              C.c_double(reach), C.c_double(max_length), _ptr(out["straight2"]), _ptr(out.get("path"))))
+        out["straight"] = np.sqrt(out["straight2"].astype(np.float64)) / 1000.0
+        return out
+
     def saxs_classes(self, side):
         """The scattering class of every atom of a side (0 receptor, 1 ligand): H / D 0, C 1, N 2, O 3, P 4, S 5, and 255
         for an atom that takes no part: another element, a membrane bead (ld_complex_saxs_classes)."""
@@ -1151,6 +1173,8 @@ def sasa_area(weighted):
     squared expanded radius) -> A^2: x 4 pi / (128 x 10^6)."""
     return np.asarray(weighted, dtype=np.float64) * (4.0 * np.pi / (SASA_POINTS * 1e6))
 
+
+XLINK_NO_PATH = 0xffffffff             # LD_XLINK_NO_PATH
 
 CCS_VIEWS = 64
 

@@ -649,6 +649,13 @@ int ld_complex_ccs(ld_complex *c, size_t n, const double *poses, size_t stride, 
         c->impl.ccs(n, poses, stride, what, probe, cell, counts, sums);
     });
 }
+int ld_complex_crosslinks(ld_complex *c, size_t n, const double *poses, size_t stride, size_t n_links, const uint32_t *links, double probe,
+                          double cell, double reach, double max_length, uint64_t *straight2, uint32_t *path) {
+    return guarded([&] {
+        if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");
+        c->impl.crosslinks(n, poses, stride, n_links, links, probe, cell, reach, max_length, straight2, path);
+    });
+}
 int ld_complex_saxs_classes(const ld_complex *c, int side, uint8_t *class_out) {
     return guarded([&] {
         if (!c) throw ld::Error(LD_ERR_INVALID, "null complex");

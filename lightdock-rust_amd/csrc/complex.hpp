@@ -70,6 +70,9 @@ class Complex {
     void sasa(size_t n, const double *poses, size_t stride, double probe, uint64_t *sums, uint8_t *free_counts, uint8_t *bound_counts);
     // Collision cross-section (lightdock_hip.h, "Collision cross-section"; ccs.cpp)
     void ccs(size_t n, const double *poses, size_t stride, int what, double probe, double cell, uint32_t *counts, uint64_t *sums);
+    // Cross-links (lightdock_hip.h, "Cross-links"; xlink.cpp)
+    void crosslinks(size_t n, const double *poses, size_t stride, size_t n_links, const uint32_t *links, double probe, double cell,
+                    double reach, double max_length, uint64_t *straight2, uint32_t *path);
     // Small-angle scattering (lightdock_hip.h, "Small-angle scattering"; saxs.cpp)
     void saxs_classes(int side, uint8_t *class_out) const;  // 0 .. 5, 255 for an atom that takes no part
     void saxs_chunk(size_t poses) { saxs_chunk_ = poses; }  // poses a chunk of counts; 0: as many as 256 MiB hold
@@ -121,6 +124,7 @@ class Complex {
     size_t density_chunk_ = 0;
     DeviceBuffer d_density_;  // density_run's receptor grid and the voxels of a chunk
     DeviceBuffer d_ccs_;      // ccs's rigid receptor: its atoms, the layout and the bitmaps of its 64 views
+    DeviceBuffer d_xlink_;    // crosslinks's links and their grouping by source anchor
     // what set_reference derived; `set` only once all of it stands
     struct Reference {
         bool set = false;
