@@ -446,6 +446,8 @@ int ld_gso_save_many(ld_gso *g, size_t n, const size_t *swarms, const char *cons
  *   ligand atom a:    rotate(q, L_a + sum_m lig_ext[m] * lig_mode[m][a]) + t   (src/qt.rs:48-61)
  * LD_ERR_INVALID, nothing written: non-finite poses or scores, a zero quaternion, modes whose
  * length is not num_anm x atoms x 3, no atom named CA or P (clustering), n_glowworms 0 or > 4096.
+ * What a call on a handle returns does not depend on what the handle ran or refused before, whichever of the calls
+ * below (tests/test_gpu_handle_history.py; tests/asan/history_check.cpp for the host side).
  * ---------------------------------------------------------------------------------- */
 typedef struct ld_complex ld_complex;
 

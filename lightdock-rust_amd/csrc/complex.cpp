@@ -174,7 +174,7 @@ void Complex::check_poses(size_t n, const double *poses, size_t stride) const {
 }
 
 void Complex::upload_poses(size_t n, const double *poses, size_t stride) {
-    d_poses_.reserve(n * stride * sizeof(double));
+    reserve_exact(d_poses_, n * stride * sizeof(double));
     hip_check(hipMemcpyAsync(d_poses_.ptr, poses, n * stride * sizeof(double), hipMemcpyHostToDevice, stream_), "hipMemcpy H2D poses");
 }
 
@@ -184,7 +184,7 @@ void Complex::pose_all(size_t n, const double *poses, size_t stride, double *out
     upload_poses(n, poses, stride);
     for (size_t i0 = 0; i0 < n; i0 += chunk) {
         const size_t m = std::min(chunk, n - i0);
-        d_out_.reserve(m * per_pose);
+        reserve_exact(d_out_, m * per_pose);
         hip_check(launch_complex_pose_xyz(dev_, static_cast<const double *>(d_poses_.ptr) + i0 * stride, stride, m,
                                           static_cast<double *>(d_out_.ptr), stream_),
                   "complex_pose_xyz launch");
@@ -231,7 +231,7 @@ void Complex::cluster(size_t n_swarms, size_t n_glowworms, const double *poses, 
     const size_t per_swarm = (size_t)G * n_bb * 3 * sizeof(int32_t);
     const size_t chunk = chunk_of(per_swarm, n_swarms);
     upload_poses(n, poses, stride);
-    d_scores_.reserve(n * sizeof(double));
+    reserve_exact(d_scores_, n * sizeof(double));
     hip_check(hipMemcpyAsync(d_scores_.ptr, scoring, n * sizeof(double), hipMemcpyHostToDevice, stream_), "hipMemcpy H2D scoring");
     int32_t *d_cluster, *d_reps;
     uint32_t *d_count;
@@ -240,7 +240,7 @@ void Complex::cluster(size_t n_swarms, size_t n_glowworms, const double *poses, 
         d_cluster = c.take<int32_t>(n), d_reps = c.take<int32_t>(n);
         d_count = c.take<uint32_t>(n_swarms), d_overflow = c.take<int>(1);
     });
-    d_ws_.reserve(chunk * per_swarm);
+    reserve_exact(d_ws_, chunk * per_swarm);
     int32_t *d_ws = static_cast<int32_t *>(d_ws_.ptr);
     const double *d_poses = static_cast<const double *>(d_poses_.ptr);
     const double *d_scores = static_cast<const double *>(d_scores_.ptr);
@@ -304,7 +304,7 @@ void Complex::cluster_ranked(size_t n, const double *poses, size_t stride, const
         r.state = c.take<int32_t>(2 * n);  // one array: the ids, then the leaders
     });
     r.reps = r.state + n;
-    d_ranked_ws_.reserve(n * per_pose);
+    reserve_exact(d_ranked_ws_, n * per_pose);
     int32_t *d_ws = static_cast<int32_t *>(d_ranked_ws_.ptr);
     hip_check(hipMemcpyAsync(d_walk, walk.data(), walk.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_), "hipMemcpy H2D walk");
     hip_check(hipEventRecord(ev0_, stream_), "hipEventRecord");
@@ -393,14 +393,17 @@ void Complex::sasa(size_t n, const double *poses, size_t stride, double probe, u
     uint8_t *d_free, *d_bound;  // null without `atoms`
     carve_into(d_ids_, [&](Carver &c) {
         d_sums = c.take<unsigned long long>(n * 4), d_overflow = c.take<int>(1);
-        d_free = c.take<uint8_t>(counts), d_bound = c.take<uint8_t>(counts);  // neighbours on purpose: one memset clears both
+        d_free = c.take<uint8_t>(counts), d_bound = c.take<uint8_t>(counts);
     });
-    d_ws_.reserve(slots * per_slot);  // launch_complex_sasa lays out its slots itself
+    reserve_exact(d_ws_, slots * per_slot);  // launch_complex_sasa lays out its slots itself
     const double *d_poses = static_cast<const double *>(d_poses_.ptr);
     begin_timed(d_overflow);
     for (size_t i0 = 0; i0 < n; i0 += chunk) {
         const size_t m = std::min(chunk, n - i0);
-        if (atoms) hip_check(hipMemsetAsync(d_free, 0, (size_t)(d_bound - d_free) + counts, stream_), "hipMemset");  // atoms that take no part stay 0
+        if (atoms) {  // atoms that take no part stay 0; each array by itself: the padding between two is nobody's
+            hip_check(hipMemsetAsync(d_free, 0, counts, stream_), "hipMemset");
+            hip_check(hipMemsetAsync(d_bound, 0, counts, stream_), "hipMemset");
+        }
         hip_check(launch_complex_sasa(dev_, d, d_poses + i0 * stride, stride, m, std::min(slots, m), d_ws_.ptr, d_sums + i0 * 4, d_free,
                                       d_bound, d_overflow, stream_),
                   "complex_sasa launch");
@@ -459,7 +462,7 @@ struct RefSums {  // of a set of reference points, exact
 
 template <typename T>
 const T *upload_into(DeviceBuffer &buffer, const std::vector<T> &host) {
-    buffer.reserve(std::max<size_t>(1, host.size()) * sizeof(T));
+    reserve_exact(buffer, std::max<size_t>(1, host.size()) * sizeof(T));
     if (!host.empty()) hip_check(hipMemcpy(buffer.ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy H2D");
     return static_cast<const T *>(buffer.ptr);
 }

@@ -3,6 +3,13 @@
 // The out-of-line definitions (and the sanitizer build's poisoning of a buffer's growth headroom beside them) are still in
 // scorer.cpp: that file is under bench.kernel_source_hash(), so moving them restamps profiles/traffic.json.  The next change
 // that restamps the profile anyway should move them into a device_memory.cpp.
+//
+// reserve() poisons the headroom only where it allocates: a block that once held a bigger call would stay open to its old
+// extent.  The analysis half therefore reserves through reserve_exact() below (carve_into() and every direct reservation of
+// complex.cpp, ccs.cpp, xlink.cpp, saxs.cpp, emfit.cpp and fcc.cpp), which in the sanitizer build poisons [want, bytes) again
+// after every reservation: the poisoning follows every carve, so an offset beyond what THIS call asked for is reported
+// whatever the handle ran before (tests/asan/history_check.cpp).  The scorer's buffers can adopt it the same way.  A placing
+// Carver poisons the padding between two arrays too (the reservation before it opened the whole block).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,6 +20,10 @@
 #include <vector>
 
 #include "host/error.hpp"
+
+#if defined(__SANITIZE_ADDRESS__)
+#include <sanitizer/asan_interface.h>
+#endif
 
 namespace ld {
 
@@ -52,6 +63,14 @@ struct DeviceBuffer {
     void release();
 };
 
+// reserve(want), and in the sanitizer build the block closed beyond `want` again (a non-sanitizer build: reserve alone).
+inline void reserve_exact(DeviceBuffer &buffer, size_t want) {
+    buffer.reserve(want);
+#if defined(__SANITIZE_ADDRESS__)
+    if (buffer.bytes > want) ASAN_POISON_MEMORY_REGION(static_cast<char *>(buffer.ptr) + want, buffer.bytes - want);
+#endif
+}
+
 // Lays typed arrays one after another in a block, every array on a 16-byte boundary.  The layout of a block is written
 // once, as a function of a Carver&: constructed without a base the carver only measures (every address it returns is
 // null), constructed on the block it places; carve_into() below does both around the reservation, so a block's size and
@@ -69,6 +88,10 @@ class Carver {
         if (count == 0) return nullptr;
         const size_t start = (end_ + 15) / 16 * 16;  // end_ <= SIZE_MAX - 15, below
         if (count > (SIZE_MAX - 15 - start) / sizeof(T)) throw Error(LD_ERR_INVALID, "the bytes of a workspace overflow");
+#if defined(__SANITIZE_ADDRESS__)
+        // the sanitizer build closes the padding before the array as well: the array before, carved an element short, ends in it
+        if (base_ && start > end_) ASAN_POISON_MEMORY_REGION(base_ + end_, start - end_);
+#endif
         end_ = start + count * sizeof(T);
         return base_ ? reinterpret_cast<T *>(base_ + start) : nullptr;
     }
@@ -84,7 +107,7 @@ template <typename Layout>
 void carve_into(DeviceBuffer &buffer, Layout &&layout) {
     Carver measure;
     layout(measure);
-    buffer.reserve(measure.bytes());
+    reserve_exact(buffer, measure.bytes());
     Carver place(buffer.ptr);
     layout(place);
 }

@@ -68,7 +68,7 @@ int Density::min_step() const { return std::min(map_.step[0], std::min(map_.step
 
 EmfitMap Density::device() {
     if (!map_.E) {
-        d_E_.reserve(E_.size() * sizeof(uint16_t));
+        reserve_exact(d_E_, E_.size() * sizeof(uint16_t));
         hip_check(hipMemcpy(d_E_.ptr, E_.data(), E_.size() * sizeof(uint16_t), hipMemcpyHostToDevice), "hipMemcpy H2D map");
         map_.E = static_cast<const uint16_t *>(d_E_.ptr);
     }

@@ -44,8 +44,8 @@ void upload_sets(size_t n, const uint32_t *offsets, const uint32_t *keys, Upload
     check_sets(n, offsets, keys, &s.key_lo, &s.key_span);
     s.n = n;
     s.total = offsets[n];
-    u.offsets.reserve((n + 1) * sizeof(uint32_t));
-    u.keys.reserve(std::max<size_t>(1, s.total) * sizeof(uint32_t));
+    reserve_exact(u.offsets, (n + 1) * sizeof(uint32_t));
+    reserve_exact(u.keys, std::max<size_t>(1, s.total) * sizeof(uint32_t));
     hip_check(hipMemcpy(u.offsets.ptr, offsets, (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy H2D offsets");
     if (s.total) hip_check(hipMemcpy(u.keys.ptr, keys, s.total * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy H2D keys");
     s.d_offsets = static_cast<const uint32_t *>(u.offsets.ptr);
@@ -93,9 +93,9 @@ uint32_t fcc_threshold(double threshold) {
 // set as a bit row of W words.  Leaves sizes_ (by row), cols_ (a column a key) and freq_ (sets a column).
 size_t FccCluster::build_rows(const Sets &s, const uint32_t *d_row_of, hipStream_t stream) {
     const size_t n_rank = (size_t)((s.key_span + 32 * kFccRankWords - 1) / (32 * kFccRankWords));
-    status_.reserve(sizeof(FccStatus));
-    bitmap_.reserve(n_rank * kFccRankWords * sizeof(uint32_t));
-    rank_.reserve((n_rank + 1) * sizeof(uint32_t));
+    reserve_exact(status_, sizeof(FccStatus));
+    reserve_exact(bitmap_, n_rank * kFccRankWords * sizeof(uint32_t));
+    reserve_exact(rank_, (n_rank + 1) * sizeof(uint32_t));
     FccStatus *d_status = static_cast<FccStatus *>(status_.ptr);
     uint32_t *d_bitmap = static_cast<uint32_t *>(bitmap_.ptr), *d_rank = static_cast<uint32_t *>(rank_.ptr);
     hip_check(hipMemsetAsync(d_bitmap, 0, n_rank * kFccRankWords * sizeof(uint32_t), stream), "hipMemset");
@@ -108,10 +108,10 @@ size_t FccCluster::build_rows(const Sets &s, const uint32_t *d_row_of, hipStream
     const size_t U = (size_t)st.total, W = std::max<size_t>(1, (U + 31) / 32);
     if (s.n * W * sizeof(uint32_t) > kFccMaxRowBytes)
         throw Error(LD_ERR_INVALID, "the bit rows of " + std::to_string(s.n) + " sets over " + std::to_string(U) + " distinct keys would exceed 1 GiB");
-    rows_.reserve(s.n * W * sizeof(uint32_t));
-    cols_.reserve(std::max<size_t>(1, s.total) * sizeof(uint32_t));
-    freq_.reserve(std::max<size_t>(1, U) * sizeof(uint32_t));
-    sizes_.reserve(s.n * sizeof(uint32_t));
+    reserve_exact(rows_, s.n * W * sizeof(uint32_t));
+    reserve_exact(cols_, std::max<size_t>(1, s.total) * sizeof(uint32_t));
+    reserve_exact(freq_, std::max<size_t>(1, U) * sizeof(uint32_t));
+    reserve_exact(sizes_, s.n * sizeof(uint32_t));
     hip_check(hipMemsetAsync(rows_.ptr, 0, s.n * W * sizeof(uint32_t), stream), "hipMemset");
     hip_check(hipMemsetAsync(freq_.ptr, 0, std::max<size_t>(1, U) * sizeof(uint32_t), stream), "hipMemset");
     hip_check(launch_fcc_rows(s.d_offsets, s.d_keys, s.n, d_row_of, s.key_lo, d_bitmap, d_rank, W, static_cast<uint32_t *>(rows_.ptr),
@@ -141,7 +141,7 @@ void FccCluster::cluster(const Sets &s, const double *scoring, uint32_t T, uint3
     const size_t W = build_rows(s, d_row_of, stream);
 
     const size_t NW = (n + 31) / 32;
-    nbr_.reserve(n * NW * sizeof(uint32_t));
+    reserve_exact(nbr_, n * NW * sizeof(uint32_t));
     uint32_t *d_nbr = static_cast<uint32_t *>(nbr_.ptr);
     FccStatus *d_status = static_cast<FccStatus *>(status_.ptr);
     hip_check(launch_fcc_common(static_cast<const uint32_t *>(rows_.ptr), W, n, static_cast<const uint32_t *>(sizes_.ptr), T, d_nbr, nullptr,
@@ -152,7 +152,7 @@ void FccCluster::cluster(const Sets &s, const double *scoring, uint32_t T, uint3
     std::vector<int32_t> by_row(n), centre_rows(n);
     out.consensus.assign(consensus ? n : 0, 0);
     if (consensus) {
-        out_.reserve(n * sizeof(unsigned long long));
+        reserve_exact(out_, n * sizeof(unsigned long long));
         hip_check(launch_fcc_consensus(s.d_offsets, static_cast<const uint32_t *>(cols_.ptr), static_cast<const uint32_t *>(freq_.ptr), n,
                                        static_cast<unsigned long long *>(out_.ptr), stream),
                   "fcc_consensus launch");
@@ -174,7 +174,7 @@ void FccCluster::cluster(const Sets &s, const double *scoring, uint32_t T, uint3
 
 void FccCluster::common(const Sets &s, uint32_t *common_out, hipStream_t stream) {
     const size_t n = s.n, W = build_rows(s, nullptr, stream);
-    out_.reserve(n * n * sizeof(uint32_t));
+    reserve_exact(out_, n * n * sizeof(uint32_t));
     hip_check(launch_fcc_common(static_cast<const uint32_t *>(rows_.ptr), W, n, static_cast<const uint32_t *>(sizes_.ptr), 1, nullptr,
                                 static_cast<uint32_t *>(out_.ptr), stream),
               "fcc_common launch");
@@ -267,7 +267,7 @@ FccCluster::Sets Complex::pair_sets(size_t n, const double *poses, size_t stride
     if (fill) {
         if (cap < s.total)
             throw Error(LD_ERR_INVALID, "room for " + std::to_string(cap) + " keys, the list has " + std::to_string(s.total));
-        d_pair_keys_.reserve(std::max<size_t>(1, s.total) * sizeof(uint32_t));
+        reserve_exact(d_pair_keys_, std::max<size_t>(1, s.total) * sizeof(uint32_t));
         uint32_t *d_keys = static_cast<uint32_t *>(d_pair_keys_.ptr);
         hip_check(launch_complex_pair_sets(dev_, k, d_poses, stride, n, (uint32_t)(C * C), slots, d_atoms, d_boxes, d_pairs, d_offsets,
                                            d_counts, d_keys, d_overflow, stream_),

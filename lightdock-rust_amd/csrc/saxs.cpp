@@ -129,7 +129,7 @@ void saxs_debye_host(size_t n, const uint32_t *counts, uint32_t width, size_t bi
     const size_t row_words = (size_t)kSaxsPairClasses * bins, row_bytes = row_words * sizeof(uint32_t);
     const size_t chunk = chunk_of(row_bytes, n);
     DeviceBuffer d_counts, d_rest;
-    d_counts.reserve(chunk * row_bytes);
+    reserve_exact(d_counts, chunk * row_bytes);
     DeviceTables tables;
     double *d_intensity;
     carve_into(d_rest, [&](Carver &c) { tables = take_tables(t, c), d_intensity = c.take<double>(n * n_q); });
@@ -248,7 +248,7 @@ void Complex::saxs_run(size_t n, const double *poses, size_t stride, uint32_t wi
     DeviceTables t;
     double *d_intensity;  // without q: n_q is 0 and the tables are empty, so these are null
     carve_into(d_ws_, [&](Carver &c) { d_atoms = c.take<int4>(chunk * (size_t)d.n_part), d_rec_atoms = c.take<int4>(base ? (size_t)d.n_part_rec : 0); });
-    d_out_.reserve((chunk + 1) * row_bytes);  // one array: the rows of a chunk, then the base row
+    reserve_exact(d_out_, (chunk + 1) * row_bytes);  // one array: the rows of a chunk, then the base row
     uint32_t *d_counts = static_cast<uint32_t *>(d_out_.ptr), *d_base = d_counts + chunk * row_words;
     carve_into(d_ids_, [&](Carver &c) { d_overflow = c.take<int>(1), t = take_tables(tables, c), d_intensity = c.take<double>(n * n_q); });
     SaxsDebye sum;

@@ -196,9 +196,10 @@ hipError_t launch_complex_bsas(const int32_t *ws, const double *scoring, int n_s
     if (G < 1 || G > kMaxGlowworms) return hipErrorInvalidValue;   // the sort keys' LDS
     peek(ws, (size_t)n_swarms * n_bb * 3 * G);
     peek(scoring, (size_t)n_swarms * G);
-    touch(cluster_of, (size_t)n_swarms * G);
-    touch(representatives, (size_t)n_swarms * G);
-    touch(n_clusters, (size_t)n_swarms);
+    // cleared whole: what the call returns is then the same whatever the block held before (history_check compares it)
+    std::memset(cluster_of, 0, (size_t)n_swarms * G * sizeof(int32_t));
+    std::memset(representatives, 0, (size_t)n_swarms * G * sizeof(int32_t));
+    std::memset(n_clusters, 0, (size_t)n_swarms * sizeof(uint32_t));
     return hipSuccess;
 }
 hipError_t launch_complex_contacts(const ComplexDevice &m, const ContactsDevice &d, const double *poses, size_t stride, size_t n, uint32_t,
@@ -213,8 +214,8 @@ hipError_t launch_complex_contacts(const ComplexDevice &m, const ContactsDevice 
     peek(d.res_of_atom, (size_t)d.n_atoms);
     touch(atoms_ws, slots * d.n_atoms);                               // atoms_ws + blockIdx * n_atoms
     if (!d.boxes_in_lds) touch(boxes_ws, slots * 6 * n_boxes);        // boxes_ws + blockIdx * 6 * n_boxes
-    touch(rec_bits, n * rw);
-    touch(lig_bits, n * lw);
+    std::memset(rec_bits, 0, n * rw * sizeof(uint32_t));              // cleared whole, as launch_complex_bsas's outputs are
+    std::memset(lig_bits, 0, n * lw * sizeof(uint32_t));
     peek(overflow, 1);
     return hipSuccess;
 }

@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 
 REC = os.path.join(CZY, "lightdock_1czy_protein.pdb")
 LIG = os.path.join(CZY, "lightdock_1czy_peptide.pdb")
+COORDINATES_TOLERANCE = 1e-9     # A: ld_complex_coordinates against Restated.pose (shared with tests/test_gpu_handle_history.py)
 
 
 @pytest.fixture(scope="module")
@@ -71,13 +72,13 @@ def test_coordinates_agree_with_the_restatement_and_pose_ligand_modes_in_the_lig
     got = czy.coordinates(poses[:40])
     assert got.shape == (40, 1281 + 53, 3)
     want = np.stack([rs.pose(p) for p in poses[:40]])
-    assert np.max(np.abs(got - want)) < 1e-9
+    assert np.max(np.abs(got - want)) < COORDINATES_TOLERANCE
     # a rotated pose with large ligand extents: the ligand-frame convention, not the scoring one
     row = poses[0].copy()
     row[3:7] = [0.3, -0.5, 0.7, 0.4]
     row[17:27] = np.linspace(-3.0, 3.0, 10)
     got = czy.coordinates(row[None])[0]
-    assert np.max(np.abs(got - rs.pose(row))) < 1e-9
+    assert np.max(np.abs(got - rs.pose(row))) < COORDINATES_TOLERANCE
     assert np.max(np.abs(got[1281:] - rs.pose(row, ligand_frame=False)[1281:])) > 0.1
     assert czy.num_atoms(2) == 175
 
@@ -171,7 +172,7 @@ def test_rigid_1ppe_and_dna_1azp_against_the_restatement(pkg):
     want_of, want_reps, knife = rs.bsas(poses, scoring, 4.0)
     assert knife == 0
     check_swarm(got, 0, want_of, want_reps)
-    assert np.max(np.abs(cx.coordinates(poses[:5]) - np.stack([rs.pose(p) for p in poses[:5]]))) < 1e-9
+    assert np.max(np.abs(cx.coordinates(poses[:5]) - np.stack([rs.pose(p) for p in poses[:5]]))) < COORDINATES_TOLERANCE
 
 
 def perturbed_czy(rng, n_swarms):

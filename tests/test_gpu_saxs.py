@@ -23,6 +23,7 @@ FILL = 0xA5
 TILE = 256                       # kSaxsTile of kernels/saxs.hpp
 Q = np.array([0.0, 0.01, 0.05, 0.1, 0.2, 0.35, 0.5, 1.0])
 CO = sx.pair_class(1, 3)
+OWN_TABLES_RTOL = 1e-12           # a profile against the restatement on ITS OWN tables (shared with tests/test_gpu_handle_history.py)
 
 
 def rigid(t):
@@ -280,7 +281,7 @@ def test_saxs_is_the_debye_sum_of_its_own_counts(pkg, czy, czy_rs, ranked):
     assert same_bits(I, czy.saxs(poses, Q, 0.5, 400))
     # the restatement's own tables (math.exp, math.sin) differ from the library's by rounding at most
     mine = np.array([czy_rs.profile(c, sx.form_factors(Q), sx.sinc(Q, 500, 400)) for c in counts])
-    assert np.abs(I - mine).max() <= 1e-12 * np.abs(mine).max()
+    assert np.abs(I - mine).max() <= OWN_TABLES_RTOL * np.abs(mine).max()
 
 
 # ---- 6. the Debye sum, physically -------------------------------------------------------------------------------
