@@ -223,7 +223,12 @@ int ld_scorer_energy(ld_scorer *s, const double translation[3], const double rot
 
 /* Batched form of the same call: what Swarm::update_luciferin (src/swarm.rs:66-70) does
  * one glowworm at a time.  poses: n rows of `stride` doubles (stride >= pose_len).
- * Host-pointer version copies in/out and synchronises. */
+ * Host-pointer version copies in/out and synchronises.
+ *
+ * The results of every ld_scorer entry -- energies, pair counts, decompositions, refinements -- do not depend on earlier
+ * calls on the handle, whatever their size, options or outcome: the handle's device workspace only grows and is shared by
+ * all of them, but a call reads nothing that it has not written itself, and a refused call (LD_ERR_INVALID) writes no
+ * output and leaves the handle as it was.  A pose's energy is the same bits in every batch, on a new handle and on a used one. */
 int ld_scorer_energy_batch(ld_scorer *s, size_t n, const double *poses, size_t stride, double *energies_out);
 
 /* Device-pointer version: poses and energies already live in HBM (hipMalloc / a torch CUDA
@@ -249,6 +254,12 @@ int ld_scorer_last_block_counts(ld_scorer *s, size_t n, uint32_t *blocks_out_hos
  * nothing to any sum: the culling lists its blocks within the interface distance only (r <= 2.45 A, src/dfire.rs:339; never, when
  * neither it nor the ligand holds a restraint atom or a bead).  0 for a table without such rows and for the other kernels. */
 int ld_scorer_bm_quiet_subtiles(const ld_scorer *s, uint32_t *count_out);
+
+/* Diagnostics of the block-major DFIRE path: how a batch of n poses would run on this handle.  pass_poses_out: the poses of a pass,
+ * min(n, the pass size the scorer derived when it was built); sets_out: the workspace sets, 2 when the batch takes several passes
+ * (they alternate between two streams), else 1.  A batch of one pass that wants no pair counts runs the fused launch sequence.
+ * Either output may be NULL; both are 0 for a scorer of another route.  Launches nothing. */
+int ld_scorer_bm_passes(const ld_scorer *s, size_t n, size_t *pass_poses_out, size_t *sets_out);
 
 /* Per-launch facts for the measurement harness. */
 typedef struct ld_kernel_info {
@@ -412,7 +423,9 @@ typedef struct ld_gso ld_gso;
 
 /* positions: n_swarms x n_glowworms rows of pose_len doubles (src/swarm.rs:26-64).
  * seeds: one u64 per swarm (GSO::new's `seed`, src/lib.rs:38), or NULL for DEFAULT_SEED
- * 324324 (src/constants.rs:2) everywhere. */
+ * 324324 (src/constants.rs:2) everywhere.
+ * Several ld_gso may share one ld_scorer, and other calls on that scorer may come between their steps: they use its
+ * workspace one after the other (calls on one scorer are not thread-safe), and a GSO's state does not depend on them. */
 ld_gso *ld_gso_create(ld_scorer *scorer, size_t n_swarms, size_t n_glowworms, const double *positions,
                       const uint64_t *seeds);
 void ld_gso_destroy(ld_gso *g);

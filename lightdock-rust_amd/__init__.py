@@ -144,6 +144,7 @@ def load_library():
     lib.ld_scorer_kernel_info.argtypes = [vp, C.POINTER(_KernelInfo)]
     lib.ld_scorer_last_block_counts.argtypes = [vp, sz, vp]
     lib.ld_scorer_bm_quiet_subtiles.argtypes = [vp, vp]
+    lib.ld_scorer_bm_passes.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(sz)]
     lib.ld_scorer_enable_timing.argtypes = [vp, C.c_int]
     lib.ld_scorer_pair_kernel_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.ld_gso_create.restype = vp
@@ -643,6 +644,12 @@ class Scorer:
         n = C.c_uint32()
         _check(self.lib.ld_scorer_bm_quiet_subtiles(self._h, C.byref(n)))
         return n.value
+
+    def bm_passes(self, n):
+        """(poses per pass, workspace sets) of a batch of n poses on the block-major DFIRE path; (0, 0) on another route."""
+        pass_poses, sets = C.c_size_t(), C.c_size_t()
+        _check(self.lib.ld_scorer_bm_passes(self._h, n, C.byref(pass_poses), C.byref(sets)))
+        return pass_poses.value, sets.value
 
     def kernel_info(self):
         info = _KernelInfo()

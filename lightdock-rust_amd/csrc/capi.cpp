@@ -396,6 +396,14 @@ int ld_scorer_bm_quiet_subtiles(const ld_scorer *s, uint32_t *count_out) {
     });
 }
 
+int ld_scorer_bm_passes(const ld_scorer *s, size_t n, size_t *pass_poses_out, size_t *sets_out) {
+    return guarded([&] {
+        if (!s) throw ld::Error(LD_ERR_INVALID, "null scorer");
+        if (pass_poses_out) *pass_poses_out = s->impl.bm_pass_poses(n);
+        if (sets_out) *sets_out = s->impl.bm_sets(n);
+    });
+}
+
 int ld_scorer_kernel_info(const ld_scorer *s, ld_kernel_info *out) {
     return guarded([&] {
         if (!s || !out) throw ld::Error(LD_ERR_INVALID, "null argument");

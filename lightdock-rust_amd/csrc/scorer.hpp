@@ -212,11 +212,11 @@ class BlockMajorPath {
              const PoseOutputs &out, const TailTables &tail, double *d_energies, hipEvent_t pairs_done, hipStream_t stream);
     uint64_t generation() const { return ws_.generation(); }
     uint32_t quiet_subtiles() const { return quiet_subtiles_; }
+    size_t pass_poses(size_t n) const;   // poses per pass of a batch of n
+    size_t sets(size_t n) const;         // workspace sets a batch of n poses needs (2 while two passes are in flight)
 
    private:
     BlockMajorPath(const RouteInputs &in, const BmFrame &frame);
-    size_t pass_poses(size_t n) const;   // poses per pass of a batch of n
-    size_t sets(size_t n) const;         // workspace sets a batch of n poses needs (2 while two passes are in flight)
     BmShape shape(size_t n, bool counts, bool debug) const;
 
     DeviceArena arena_;                   // the model's uploads
@@ -266,6 +266,9 @@ class Scorer {
     // diagnostics of the last counting launch: 8x8 atom-pair blocks evaluated per pose (culled DFIRE kernels)
     void last_block_counts(size_t n, uint32_t *out_host);
     uint32_t bm_quiet_subtiles() const { return bm_ ? bm_->quiet_subtiles() : 0u; }
+    // how the block-major path would run a batch of n poses: poses per pass and workspace sets (0, 0 on the other routes)
+    size_t bm_pass_poses(size_t n) const { return bm_ ? bm_->pass_poses(n) : 0; }
+    size_t bm_sets(size_t n) const { return bm_ ? bm_->sets(n) : 0; }
     void enable_timing(bool on);
     void pair_kernel_time(double *total_ms, uint64_t *launches);
 

@@ -52,20 +52,31 @@ def _poses(rng, n, cols=7):
     return poses
 
 
+def small_complex(rng, table, directory):
+    """The files of the complex, drawn from `rng`, and the arguments both Scorer constructors take: (rec, lig, kw)."""
+    rec, lig = os.path.join(directory, "rec.pdb"), os.path.join(directory, "lig.pdb")
+    rec_atoms = _random_molecule(rng, 146, 28.0, "A", with_beads=4)
+    lig_atoms = _random_molecule(rng, 100, 18.0, "B")
+    assert len(rec_atoms) == 150 and len(lig_atoms) == 100
+    _write_pdb(rec, rec_atoms)
+    _write_pdb(lig, lig_atoms)
+    return rec, lig, dict(rec_active=["A.%s.%d" % (rec_atoms[0][1], rec_atoms[0][3])],
+                          lig_active=["B.%s.%d" % (lig_atoms[-1][1], lig_atoms[-1][3])], potential=table)
+
+
+def small_anm_kw(rng, kw):
+    """`kw` with 3 + 3 modes drawn from `rng`."""
+    return dict(kw, use_anm=True, rec_num_anm=3, lig_num_anm=3,
+                rec_nmodes=(rng.normal(size=(3, 150, 3)) * 0.4).ravel(), lig_nmodes=(rng.normal(size=(3, 100, 3)) * 0.4).ravel())
+
+
 class Small:
     """The complex, its poses and the oracle's answers, made once."""
 
     def __init__(self, pkg, orc, table, directory):
         self.pkg, self.orc, self.table = pkg, orc, table
         rng = np.random.default_rng(4242)
-        self.rec, self.lig = os.path.join(directory, "rec.pdb"), os.path.join(directory, "lig.pdb")
-        rec_atoms = _random_molecule(rng, 146, 28.0, "A", with_beads=4)
-        lig_atoms = _random_molecule(rng, 100, 18.0, "B")
-        assert len(rec_atoms) == 150 and len(lig_atoms) == 100
-        _write_pdb(self.rec, rec_atoms)
-        _write_pdb(self.lig, lig_atoms)
-        self.kw = dict(rec_active=["A.%s.%d" % (rec_atoms[0][1], rec_atoms[0][3])],
-                       lig_active=["B.%s.%d" % (lig_atoms[-1][1], lig_atoms[-1][3])], potential=table)
+        self.rec, self.lig, self.kw = small_complex(rng, table, directory)
         self.poses = _poses(rng, N_POSES)
         self.cpu = orc.Scorer("dfire", self.rec, self.lig, **self.kw)
         self.hip = pkg.Scorer.from_pdb("dfire", self.rec, self.lig, **self.kw)
@@ -76,8 +87,7 @@ class Small:
         self.stats.setflags(write=False)
         # molecules that flex: 3 + 3 modes, one wild pose
         mrng = np.random.default_rng(4243)
-        self.anm_kw = dict(self.kw, use_anm=True, rec_num_anm=3, lig_num_anm=3,
-                           rec_nmodes=(mrng.normal(size=(3, 150, 3)) * 0.4).ravel(), lig_nmodes=(mrng.normal(size=(3, 100, 3)) * 0.4).ravel())
+        self.anm_kw = small_anm_kw(mrng, self.kw)
         self.anm_poses = _poses(mrng, 30, 13)
         self.anm_poses[:, 7:] = mrng.normal(size=(30, 6)) * 2.0
         self.anm_poses[5, 7:] *= 40.0
